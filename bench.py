@@ -3,7 +3,7 @@
 bench.py -- the headline measurement of BASELINE.json: BN254 G1 MSM (G1-adds/s) + Fr NTT (butterflies/s) at k = 26
 on MI355X, one process per GPU.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input: ONE commitment = one G1 MSM over 2^k
@@ -17,6 +17,11 @@ not shard at k <= 26 (replicas only), so each rank runs its own copy.
 
 Synthetic data: basis g[i] = tau_r^i * G built on the device (ParamsKZG::setup restated, so every commitment can be
 checked in the field: commit(p) = p(tau) G); scalars uniform in [0, r) from a seeded generator.
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds every other leg and check: the
+create_proof replays (before the device is bound), then after the timed steps the field check of the result, the NTT
+and the other MSM legs and the CPU baselines.
+--dump-outputs DIR writes the last timed step's commitment as DIR/msm_commitment.npy (same arguments, same inputs).
 """
 from __future__ import annotations
 
@@ -300,7 +305,14 @@ def main() -> None:
     ap.add_argument("--no-witness-like", action="store_true", help="skip the witness-like column (with every other leg off the run then launches only the timed uniform MSMs: the profile whose per-kernel averages are comparable with roofline.avg_launch_ms)")
     ap.add_argument("--no-sizes", action="store_true", help="skip the k = 20 / 24 legs (MSM on prefix views of the basis + NTT)")
     ap.add_argument("--host-api", action="store_true", help=argparse.SUPPRESS)   # accepted for older command lines: the leg is on by default now
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline MSM: the field check of its result, the NTT, host-pointer, table-free, witness-like, "
+                    "k = 20 / 24 and batched legs, the CPU baselines, the create_proof replays and the released-proof check (each --no-* switch still drops its leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the commitment of the last timed step to DIR/msm_commitment.npy")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run is set-up, warm-up, the timed steps and the line: every other leg and check runs under --full only
+        for leg in ("no_proof_mix", "no_ntt", "no_host_api", "no_table_free", "no_witness_like", "no_sizes", "no_batch_legs", "no_cpu_baseline"):
+            setattr(args, leg, True)
 
     single = args.single_process          # N GPUs behind this one process (the reference's shape: one prover process, one params_map)
     if args.gpus > 1 and not single and "WORLD_SIZE" not in os.environ:
@@ -462,6 +474,10 @@ def main() -> None:
     dt = time.perf_counter() - t0
     check(lib.mi355_profile_enable(0))
     result = np.array(result, copy=True)   # `out` is reused by every later leg: keep the timed steps' result for the checks below
+    if args.dump_outputs and rank == 0:
+        # the 96 B the caller receives (normalised Jacobian x, y, z in Montgomery limbs) as its 24 little-endian 32-bit words, exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_commitment.npy"), np.ascontiguousarray(result, dtype=np.uint64).view(np.uint32).astype(np.float64))
     multi = None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if share else dev)
@@ -498,7 +514,7 @@ def main() -> None:
 
     # ---- correctness of what was timed: commit(p) = p(tau) G checked in the field (rank-local shard, oracle = checker only)
     verified = None
-    if rank == 0 and k <= 26 and world == 1:   # ~3 s of host time at 2^26 (one Horner pass over the scalars), outside the timed region
+    if args.full and rank == 0 and k <= 26 and world == 1:   # ~3 s of host time at 2^26 (one Horner pass over the scalars), outside the timed region
         from oracle import cref
         sc_host = scalars.cpu().numpy().view(np.uint64)
         p_tau = cref.eval_polynomial(sc_host, tau_m)
@@ -507,7 +523,7 @@ def main() -> None:
 
     # N > 1: every rank evaluates its slice of the polynomial in the field, p_r(tau) tau^(r n) (oracle = checker only, outside the timed region), the 32-byte
     # values are gathered, and rank 0 checks  result == (sum_r tau^(r n) p_r(tau)) G = p(tau) G  for the ONE polynomial p the ranks hold together
-    if world > 1 and k <= 26:
+    if args.full and world > 1 and k <= 26:
         from oracle import cref
         e_r = cref.f_mul(cref.FR, cref.eval_polynomial(scalars.cpu().numpy().view(np.uint64), tau_m), h2.fr(pow(tau, rank * n, h2.R_MOD)))
         mine = torch.from_numpy(e_r.view(np.uint8).copy()).to("cpu" if share else dev)
@@ -829,7 +845,7 @@ def main() -> None:
             if rp is not None:
                 cfg["verifier_accepts_released_reference_proofs"] = "%d of %d" % rp
                 checks.append(rp[0] == rp[1])
-        cfg["all_checks"] = all(bool(c) for c in checks)
+        cfg["all_checks"] = all(bool(c) for c in checks) if args.full else None   # a plain run checks nothing
         emit(line)
     if world > 1:
         dist.destroy_process_group()

@@ -61,9 +61,40 @@ def test_ranks_share_one_srs_and_prove_one_commitment(ranks):
         env.pop(k, None)
     env["MI355_BENCH_SHARE_GPU"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(29700 + ranks),
-           "bench.py", "--gpus", str(ranks), "--logn", "20", "--steps", "2", "--warmup", "1", "--no-proof-mix", "--no-cpu-baseline", "--no-ntt", "--no-precompute"]
+           "bench.py", "--gpus", str(ranks), "--logn", "20", "--steps", "2", "--warmup", "1", "--full", "--no-proof-mix", "--no-cpu-baseline", "--no-ntt", "--no-precompute"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout + out.stderr)[-1500:]
     line = json.loads(next(l for l in out.stdout.splitlines() if l.startswith('{"metric"')))
     assert line["n_gpus"] == ranks and line["verified_against_field_check"] is True, line
     assert len(line["multi_gpu"]["per_rank_ms_per_step"]) == ranks
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_timed_commitment_and_repeats():
+    """--dump-outputs: the last timed step's commitment, the same whatever --steps is (the inputs are seeded), and equal to p(tau) G for the scalars the run generated"""
+    import importlib.util
+    import tempfile
+    import numpy as np
+    import torch
+    from oracle import cref
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
+        env.pop(k, None)
+    dumps = []
+    with tempfile.TemporaryDirectory(prefix="mi355_dump_") as tmp:
+        for steps in (2, 3):
+            d = os.path.join(tmp, str(steps))
+            out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--logn", "20", "--steps", str(steps), "--warmup", "1", "--dump-outputs", d],
+                                 cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+            assert out.returncode == 0, (out.stdout + out.stderr)[-1500:]
+            line = json.loads(next(l for l in out.stdout.splitlines() if l.startswith('{"metric"')))
+            assert line["steps"] == steps and line["ms_per_step"] > 0
+            dumps.append(np.load(os.path.join(d, "msm_commitment.npy")))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (24,) and (dumps[0] == dumps[1]).all()
+    spec = importlib.util.spec_from_file_location("_bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    sc = bench.rand_scalars(1 << 20, 0x5343524F4C4C0002, torch.device("cuda", 0)).cpu().numpy().view(np.uint64)
+    want = cref.g1_to_affine(cref.g1_mul(cref.g1_generator(), cref.eval_polynomial(sc, cref.fr_mont(0x5343524F4C4C0001))))
+    got = dumps[0].astype(np.uint64).astype(np.uint32).view(np.uint64)
+    assert (got[:8] == want).all()

@@ -12,7 +12,7 @@ TAG=${1:-r05}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-LEGS="--no-cpu-baseline --no-host-api --no-table-free --no-proof-mix --no-sizes --no-witness-like --no-batch-legs"
+LEGS="--full --no-cpu-baseline --no-host-api --no-table-free --no-proof-mix --no-sizes --no-witness-like --no-batch-legs"
 Q="python $ROOT/tools/pmc_query.py"
 # ---- A
 rm -rf /tmp/p_stats; rocprofv3 --kernel-trace --stats -d /tmp/p_stats -o bench -- python $ROOT/bench.py --steps 5 --warmup 1 $LEGS > $OUT/${TAG}_stats_bench_line.json 2> /dev/null

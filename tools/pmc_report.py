@@ -72,7 +72,7 @@ ks = lines("kernel_stats.txt")
 if ks:
     with open(os.path.join(PROF, f"{TAG}_kernel_stats.md"), "w") as f:
         f.write(f"# Round {TAG[1:].lstrip('0')} -- per-kernel statistics of the headline legs (`rocprofv3 --kernel-trace --stats`)\n\n"
-                "`cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host-api --no-table-free --no-proof-mix "
+                "`cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-host-api --no-table-free --no-proof-mix "
                 "--no-sizes --no-witness-like --no-batch-legs` (`tools/collect_profiles.sh`): six uniform MSMs at 2^26 (1 warm-up + 5 timed) and the NTT leg.  `k_msm_accumulate`'s average is the "
                 "figure `roofline.avg_launch_ms` of the bench line must agree with; `k_srs_precompute` / `k_fixed_base_mul` / `k_srs_scalars` are registration-time set-up.\n\n")
         f.write("\n".join(ks) + "\n")
@@ -85,7 +85,7 @@ if ks:
 acc_f, acc_w = by_kernel(fetch, "k_msm_accumulate"), by_kernel(write, "k_msm_accumulate")
 acc_bytes = None
 md = [f"# Round {TAG[1:].lstrip('0')} -- HBM traffic counters at 2^26 on the {TAG} tree: the MSM kernels, the three NTT passes, and the same passes through the batched entry points\n",
-      "`tools/collect_profiles.sh r05` (FETCH_SIZE and WRITE_SIZE in separate `rocprofv3 --kernel-trace --pmc` passes over `bench.py --steps 1 --warmup 0` with the headline legs only, "
+      "`tools/collect_profiles.sh r05` (FETCH_SIZE and WRITE_SIZE in separate `rocprofv3 --kernel-trace --pmc` passes over `bench.py --full --steps 1 --warmup 0` with the headline legs only, "
       "then over one layer-4 `create_proof`); per-dispatch sums by `tools/pmc_query.py`, this table by `tools/pmc_report.py`.  Counter units are KiB.  Corrections: wide coalesced "
       "streaming reads are counted at 1/2 (doubled below), 64-byte gathers and strided 128-byte runs 1:1, writes 1:1 (guide, \"HBM\"; calibration in `profiles/r01_pmc_msm_k26.md`).\n",
       f"Source hashes the figures belong to (bench.py re-emits `roofline.traffic` only while they match): msm `{source_hash('msm')}`, ntt `{source_hash('ntt')}`.\n"]
