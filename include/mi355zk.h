@@ -266,9 +266,22 @@ int mi355_g1_fixed_base_mul_dev(void *points_affine_dev, const void *scalars_dev
 /* ---- G2: out = scalar * p on the twist y^2 = x^3 + 3 / (9 + u) over Fq2.  Points are 128-byte halo2curves G2Affine values
  * (x.c0 | x.c1 | y.c0 | y.c1, Montgomery limbs; identity = all zero) -- the layout of `g2` / `s_g2` in a RawBytes params file.  The one G2
  * operation on the path: ParamsKZG::setup's s_g2 = tau * G2 [EXT-recalled poly/kzg/commitment.rs]; a G2 MSM does not exist in create_proof
- * (SURVEY 8a a7).  MI355_EBADARG when p is not on the twist.  The generator constant is halo2curves' G2 generator, pinned by the
- * pairing input of the released verifier [REF release-v0.13.1/evm_verifier.yul:1230-1233].                                             */
+ * (SURVEY 8a a7), but the library provides one below for callers that commit in G2.  MI355_EBADARG when p is not on the twist.  The
+ * generator constant is halo2curves' G2 generator, pinned by the pairing input of the released verifier
+ * [REF release-v0.13.1/evm_verifier.yul:1230-1233].                                                                                    */
 int mi355_g2_mul_host(const void *p_g2affine_host, const void *scalar_fr, void *out_g2affine_host);
+/* ---- G2 MSM: out = sum_i scalars[i] * bases[i] on the twist (Pippenger; the digit and sort stages of the G1 MSM, G2 bucket kernels).
+ * bases: n x 128-byte G2Affine as above (identity = all zero); scalars: n x 32-byte Fr, Montgomery form as for mi355_msm_g1_*; out: one
+ * normalised G2Affine (identity = 128 zero bytes; n == 0 gives the identity).  Every base is checked to be on the twist in a device pass:
+ * MI355_EBADARG, and mi355_last_error() names the first bad index, when one is not.  Bases are NOT checked for subgroup membership (a
+ * point of the twist outside the r-torsion is summed like any other).  One device (the primary), no CPU fallback (MI355_ENODEVICE
+ * without a gfx950 device); same locking and stream order as the G1 entry points.  mi355_msm_last_plan reports the call's window
+ * bits, windows and entries; mi355_msm_set_window_bits applies as for G1.  The kernels report under msm_g2_* in mi355_profile_get.
+ *   _adhoc_host: bases and scalars in host memory.   _dev: both in device memory of the primary device (mi355_buf_alloc blocks or any
+ *   device pointer).   _batch_dev: `batch` scalar vectors over one basis, out = batch x 128 B.                                          */
+int mi355_msm_g2_adhoc_host(const void *bases_g2affine_host, const void *scalars_host, uint64_t n, void *out_g2affine_host);
+int mi355_msm_g2_dev(const void *bases_g2affine_dev, const void *scalars_dev, uint64_t n, void *out_g2affine_host);
+int mi355_msm_g2_batch_dev(const void *bases_g2affine_dev, const void *const *scalars_dev, uint32_t batch, uint64_t n, void *out_g2affine_host);
 
 /* ---- best_fft::<Fr, G1> -- the same DFT over G1 points, a'[i] = sum_j omega^(ij) a[j] -- and its one caller, g_to_lagrange, which
  * ParamsKZG::downsize(k) [REF integration/tests/integration.rs:17-22] and ParamsKZG::setup run to rebuild g_lagrange from

@@ -72,6 +72,9 @@ extern "C" {
     pub fn mi355_mem_info(device_slot: c_int, free_bytes: *mut u64, total_bytes: *mut u64, live_buf_bytes: *mut u64, pooled_bytes: *mut u64, workspace_bytes: *mut u64) -> c_int;
     pub fn mi355_msm_g1_dev(srs: u64, base_offset: u64, scalars_dev: *const c_void, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g1_batch_dev(srs: u64, base_offset: u64, scalars_dev: *const *const c_void, batch: u32, n: u64, out_g1_host: *mut c_void) -> c_int;
+    pub fn mi355_msm_g2_adhoc_host(bases_g2affine_host: *const c_void, scalars_host: *const c_void, n: u64, out_g2affine_host: *mut c_void) -> c_int;
+    pub fn mi355_msm_g2_dev(bases_g2affine_dev: *const c_void, scalars_dev: *const c_void, n: u64, out_g2affine_host: *mut c_void) -> c_int;
+    pub fn mi355_msm_g2_batch_dev(bases_g2affine_dev: *const c_void, scalars_dev: *const *const c_void, batch: u32, n: u64, out_g2affine_host: *mut c_void) -> c_int;
     pub fn mi355_intt_fr_dev(data_dev: *mut c_void, log_n: u32, omega_inv: *const c_void, divisor: *const c_void) -> c_int;
     pub fn mi355_ntt_fr_batch_host(data_host: *const *mut c_void, batch: u32, log_n: u32, omega: *const c_void, divisor: *const c_void) -> c_int;
     pub fn mi355_ntt_fr_batch_dev(data_dev: *const *mut c_void, batch: u32, log_n: u32, omega: *const c_void, divisor: *const c_void) -> c_int;

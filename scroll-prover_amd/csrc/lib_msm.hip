@@ -5,6 +5,8 @@
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #define ZK_FRSCAN_DEVICE_ONLY 1   // msm.hpp needs the block scans of frscan.hpp, not its kernels (those belong to lib_aux.hip)
 #include "msm.hpp"
+#define ZK_G2_DEVICE_ONLY 1      // msm_g2.hpp needs the twist arithmetic of g2.hpp, not k_g2_mul (that kernel belongs to lib_aux.hip)
+#include "msm_g2.hpp"
 #include "lib_common.hpp"
 
 namespace mi355 {
@@ -116,6 +118,79 @@ int msm_reduce_tail(const MsmShape &sh, uint32_t M, const g1_xyzz29_t *buckets, 
   return MI355_OK;
 }
 
+// Stage A of one MSM pass: digits -> two-level counting sort of (window, bucket) keys.  It never looks at a point, so the G1 and the G2
+// MSM share it.  Out: offsets[nbuckets + 1] (exclusive bucket starts) and sorted[emax] (point index | sign << 31, grouped by bucket; with
+// window tables the payload names a table row, see SortPlan::nshift).  g2: the profile spans carry G2 names.
+int msm_sort_stage(const PolyPtrs &inl, const fe_t *const *polys_dev, uint32_t M, uint64_t n, const MsmShape &sh, const MsmPlan &P, uint32_t *offsets, uint32_t *sorted,
+                   hipStream_t s, bool g2 = false) {
+  const bool shared = sh.shared;
+  const uint64_t emax = sh.emax;
+  const uint32_t nbuckets = (uint32_t)sh.nbuckets;
+  // sort plan: fine bits fb (<= 12, LDS histogram of 2^fb bins), coarse bits = the rest
+  SortPlan S; S.n = P.n; S.windows = M * P.windows; S.wpp = P.windows; S.nb = P.nb;
+  S.fb = sh.fb; S.cb_bits = sh.cb_bits;
+  S.shared = shared ? 1 : 0; S.nshift = log2_ceil(n);
+  S.regions = sh.regions;
+  S.t1 = g.sort_t1;                           // level-1 tile: 1024 threads x 8 or 16 entries (64 / 128 KiB of LDS staging)
+  // split records (payload u32 + fine key u16 as two streams, MI355_SORT_SPLIT): 6 bytes of staging per entry -> 24 576-entry tiles where the bin
+  // bookkeeping leaves room (<= 1024 coarse bins)
+  if (g.sort_split == 1 && S.t1 == 16384 && (1u << S.cb_bits) <= 1024 && emax >= (1ull << 24)) S.t1 = 24576;   // MI355_SORT_SPLIT=2: split records, 16 384-entry tiles
+  // level-2 tile (6 B of LDS per entry next to the 3 x 2^fb words of bin bookkeeping): 16384 entries give twice the run length in
+  // `sorted` (fewer partial-line store transactions, the limiter of this kernel) at one workgroup per CU; worth it for big sorts
+  S.t2 = g.sort_t2 ? g.sort_t2 : (emax >= (1ull << 27) && S.fb <= 11 ? 16384 : 8192);
+  const uint32_t tiles1 = ceil_div(n, S.t1), l2_tiles_max = ceil_div(emax, S.t2) + S.regions + 8;   // + 8: the XCD-aware tile order rounds the tile count up to a multiple of 8
+  const uint32_t vwindows = M * P.windows;   // (polynomial, window) pairs
+
+  // stage-A-only buffers are shared by all slots (the sort stages of successive chunks run one after the other on one stream)
+  uint32_t *enc, *hist, *cursor, *scan_sums, *coarse_hist, *coarse_off, *coarse_cursor, *tile_start;
+  CHK(ws_get("msm.digits", emax * 4, (void **)&enc));
+  uint32_t *pairs_lo = nullptr; uint16_t *pairs_hi = nullptr;
+  CHK(ws_get("msm.pairs_lo", emax * 4 + 64, (void **)&pairs_lo)); CHK(ws_get("msm.pairs_hi", emax * 2 + 64, (void **)&pairs_hi));
+  CHK(ws_get("msm.hist", ((size_t)nbuckets + 1) * 4, (void **)&hist));
+  CHK(ws_get("msm.cursor", ((size_t)nbuckets + 1) * 4, (void **)&cursor));
+  CHK(ws_get("msm.coarse_hist", ((size_t)S.regions + 1) * 4, (void **)&coarse_hist));
+  CHK(ws_get("msm.coarse_off", ((size_t)S.regions + 1) * 4, (void **)&coarse_off));
+  CHK(ws_get("msm.coarse_cursor", ((size_t)S.regions + 1) * 4, (void **)&coarse_cursor));
+  CHK(ws_get("msm.tile_start", ((size_t)S.regions + 1) * 4, (void **)&tile_start));
+  const uint32_t scan_n = nbuckets + 1, scan_blocks = ceil_div(scan_n, SCAN_BLOCK * SCAN_ITEMS);
+  const uint32_t cscan_n = S.regions + 1, cscan_blocks = ceil_div(cscan_n, SCAN_BLOCK * SCAN_ITEMS);
+  CHK(ws_get("msm.scan_sums", (size_t)(scan_blocks + cscan_blocks) * 4, (void **)&scan_sums));
+  const int grid_stream = g.prop.multiProcessorCount * 8;
+  {
+    Scope sc(g2 ? "msm_g2_digits" : "msm_digits", s);
+    HIPCHK(hipMemsetAsync(coarse_hist, 0, ((size_t)S.regions + 1) * 4, s));
+    hipLaunchKernelGGL(k_msm_digits, dim3(grid_stream / M > 0 ? grid_stream / M : 1, M), dim3(256), (size_t)S.regions * 4, s, inl, polys_dev, enc, P, coarse_hist, S.fb, S.cb_bits, S.shared);
+  }
+  {
+    Scope sc(g2 ? "msm_g2_sort" : "msm_sort", s);
+    HIPCHK(hipMemsetAsync(hist, 0, ((size_t)nbuckets + 1) * 4, s));
+    hipLaunchKernelGGL(k_scan_partial, dim3(cscan_blocks), dim3(SCAN_BLOCK), 0, s, coarse_hist, scan_sums + scan_blocks, cscan_n);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(SCAN_BLOCK), 0, s, scan_sums + scan_blocks, cscan_blocks);
+    hipLaunchKernelGGL(k_scan_final, dim3(cscan_blocks), dim3(SCAN_BLOCK), 0, s, coarse_hist, scan_sums + scan_blocks, coarse_off, coarse_cursor, cscan_n);
+    {
+      Scope s1(g2 ? "g2_sort_l1" : "sort_l1", s);
+      const uint32_t CBp = ((1u << S.cb_bits) + 1) & ~1u;
+      const size_t lds1 = (size_t)(3 * CBp + 32 + SORT_SPLIT_TMAX) * 4 + (size_t)S.t1 * 6;
+      if (S.t1 == 24576) hipLaunchKernelGGL(k_sort_l1_scatter_split<24>, dim3(tiles1 * vwindows), dim3(1024), lds1, s, enc, coarse_cursor, pairs_lo, pairs_hi, S);
+      else if (S.t1 == 16384) hipLaunchKernelGGL(k_sort_l1_scatter_split<16>, dim3(tiles1 * vwindows), dim3(1024), lds1, s, enc, coarse_cursor, pairs_lo, pairs_hi, S);
+      else hipLaunchKernelGGL(k_sort_l1_scatter_split<8>, dim3(tiles1 * vwindows), dim3(1024), lds1, s, enc, coarse_cursor, pairs_lo, pairs_hi, S);
+    }
+    hipLaunchKernelGGL(k_sort_tile_prefix, dim3(1), dim3(SCAN_BLOCK), 0, s, coarse_off, tile_start, S);
+    { Scope s2(g2 ? "g2_sort_hist" : "sort_hist", s);
+    hipLaunchKernelGGL(k_sort_l2_hist_split, dim3(l2_tiles_max), dim3(256), 0, s, (const uint16_t *)pairs_hi, coarse_off, tile_start, hist, S); }
+    hipLaunchKernelGGL(k_scan_partial, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, s, hist, scan_sums, scan_n);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(SCAN_BLOCK), 0, s, scan_sums, scan_blocks);
+    hipLaunchKernelGGL(k_scan_final, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, s, hist, scan_sums, offsets, cursor, scan_n);
+    {
+      Scope s3(g2 ? "g2_sort_l2" : "sort_l2", s);
+      const size_t lds2 = (size_t)(3 * (1u << S.fb) + 32) * 4 + (size_t)S.t2 * 6;   // histogram / offsets / bases + staged indices (4 B) and their bins (2 B)
+      if (S.t2 == 8192) hipLaunchKernelGGL(k_sort_l2_scatter_split<8>, dim3(l2_tiles_max), dim3(1024), lds2, s, (const uint32_t *)pairs_lo, (const uint16_t *)pairs_hi, coarse_off, tile_start, cursor, sorted, S);
+      else hipLaunchKernelGGL(k_sort_l2_scatter_split<16>, dim3(l2_tiles_max), dim3(1024), lds2, s, (const uint32_t *)pairs_lo, (const uint16_t *)pairs_hi, coarse_off, tile_start, cursor, sorted, S);
+    }
+  }
+  return MI355_OK;
+}
+
 // One MSM (or one chunk of a pipelined MSM) enqueued on three streams: st.a digits + sort (HBM-bound), st.b bucket accumulation
 // (ALU-bound), st.c fix-up + bucket reduction (latency-bound).  With st.a == st.b == st.c this is the plain serial schedule.
 // M commitments over the same basis slice in one pass: (polynomial m, window w) is window m * W + w of one big bucket problem, so the
@@ -148,36 +223,8 @@ int msm_enqueue(const g1_affine_t *bases, const PolyPtrs &inl, const fe_t *const
   const uint32_t nbuckets = (uint32_t)sh.nbuckets;
   const uint32_t acc_threads = ceil_div(emax, seg), acc_blocks = ceil_div(acc_threads, 256);
   const uint32_t tn = acc_blocks * 256;
-  // sort plan: fine bits fb (<= 12, LDS histogram of 2^fb bins), coarse bits = the rest
-  SortPlan S; S.n = P.n; S.windows = M * P.windows; S.wpp = P.windows; S.nb = P.nb;
-  S.fb = sh.fb; S.cb_bits = sh.cb_bits;
-  S.shared = shared ? 1 : 0; S.nshift = log2_ceil(n);
-  S.regions = sh.regions;
-  S.t1 = g.sort_t1;                           // level-1 tile: 1024 threads x 8 or 16 entries (64 / 128 KiB of LDS staging)
-  // split records (payload u32 + fine key u16 as two streams, MI355_SORT_SPLIT): 6 bytes of staging per entry -> 24 576-entry tiles where the bin
-  // bookkeeping leaves room (<= 1024 coarse bins)
-  if (g.sort_split == 1 && S.t1 == 16384 && (1u << S.cb_bits) <= 1024 && emax >= (1ull << 24)) S.t1 = 24576;   // MI355_SORT_SPLIT=2: split records, 16 384-entry tiles
-  // level-2 tile (6 B of LDS per entry next to the 3 x 2^fb words of bin bookkeeping): 16384 entries give twice the run length in
-  // `sorted` (fewer partial-line store transactions, the limiter of this kernel) at one workgroup per CU; worth it for big sorts
-  S.t2 = g.sort_t2 ? g.sort_t2 : (emax >= (1ull << 27) && S.fb <= 11 ? 16384 : 8192);
-  const uint32_t tiles1 = ceil_div(n, S.t1), l2_tiles_max = ceil_div(emax, S.t2) + S.regions + 8;   // + 8: the XCD-aware tile order rounds the tile count up to a multiple of 8
-  const uint32_t vwindows = M * P.windows;   // (polynomial, window) pairs
-
-  uint32_t *enc, *hist, *offsets, *cursor, *sorted, *scan_sums, *coarse_hist, *coarse_off, *coarse_cursor, *tile_start;
+  uint32_t *offsets, *sorted;
   g1_xyzz29_t *buckets, *part; int32_t *part_id;
-  // stage-A-only buffers are shared by all slots (the sort stages of successive chunks run one after the other on st.a)
-  CHK(ws_get("msm.digits", emax * 4, (void **)&enc));
-  uint32_t *pairs_lo = nullptr; uint16_t *pairs_hi = nullptr;
-  CHK(ws_get("msm.pairs_lo", emax * 4 + 64, (void **)&pairs_lo)); CHK(ws_get("msm.pairs_hi", emax * 2 + 64, (void **)&pairs_hi));
-  CHK(ws_get("msm.hist", ((size_t)nbuckets + 1) * 4, (void **)&hist));
-  CHK(ws_get("msm.cursor", ((size_t)nbuckets + 1) * 4, (void **)&cursor));
-  CHK(ws_get("msm.coarse_hist", ((size_t)S.regions + 1) * 4, (void **)&coarse_hist));
-  CHK(ws_get("msm.coarse_off", ((size_t)S.regions + 1) * 4, (void **)&coarse_off));
-  CHK(ws_get("msm.coarse_cursor", ((size_t)S.regions + 1) * 4, (void **)&coarse_cursor));
-  CHK(ws_get("msm.tile_start", ((size_t)S.regions + 1) * 4, (void **)&tile_start));
-  const uint32_t scan_n = nbuckets + 1, scan_blocks = ceil_div(scan_n, SCAN_BLOCK * SCAN_ITEMS);
-  const uint32_t cscan_n = S.regions + 1, cscan_blocks = ceil_div(cscan_n, SCAN_BLOCK * SCAN_ITEMS);
-  CHK(ws_get("msm.scan_sums", (size_t)(scan_blocks + cscan_blocks) * 4, (void **)&scan_sums));
   // per-slot: what the accumulation and the reduction of this chunk read while the next chunk is being sorted
   WS("msm.offsets", ((size_t)nbuckets + 1) * 4, offsets);
   WS("msm.sorted", emax * 4, sorted);
@@ -195,43 +242,11 @@ int msm_enqueue(const g1_affine_t *bases, const PolyPtrs &inl, const fe_t *const
   WS("msm.huge_part", (size_t)huge_cap * FIXUP_SLICES * sizeof(g1_xyzz29_t), huge_part);
 #undef WS
 
-  const int grid_stream = g.prop.multiProcessorCount * 8;
   {
     hipStream_t s = st.a;
     // the accumulation and the fix-up of the chunk that used this slot before must be done with `sorted` / `offsets`
     if (piped && slot.used) { HIPCHK(hipStreamWaitEvent(s, slot.acc_done, 0)); HIPCHK(hipStreamWaitEvent(s, slot.red_done, 0)); }
-    {
-      Scope sc("msm_digits", s);
-      HIPCHK(hipMemsetAsync(coarse_hist, 0, ((size_t)S.regions + 1) * 4, s));
-      hipLaunchKernelGGL(k_msm_digits, dim3(grid_stream / M > 0 ? grid_stream / M : 1, M), dim3(256), (size_t)S.regions * 4, s, inl, polys_dev, enc, P, coarse_hist, S.fb, S.cb_bits, S.shared);
-    }
-    {
-      Scope sc("msm_sort", s);
-      HIPCHK(hipMemsetAsync(hist, 0, ((size_t)nbuckets + 1) * 4, s));
-      hipLaunchKernelGGL(k_scan_partial, dim3(cscan_blocks), dim3(SCAN_BLOCK), 0, s, coarse_hist, scan_sums + scan_blocks, cscan_n);
-      hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(SCAN_BLOCK), 0, s, scan_sums + scan_blocks, cscan_blocks);
-      hipLaunchKernelGGL(k_scan_final, dim3(cscan_blocks), dim3(SCAN_BLOCK), 0, s, coarse_hist, scan_sums + scan_blocks, coarse_off, coarse_cursor, cscan_n);
-      {
-        Scope s1("sort_l1", s);
-        const uint32_t CBp = ((1u << S.cb_bits) + 1) & ~1u;
-        const size_t lds1 = (size_t)(3 * CBp + 32 + SORT_SPLIT_TMAX) * 4 + (size_t)S.t1 * 6;
-        if (S.t1 == 24576) hipLaunchKernelGGL(k_sort_l1_scatter_split<24>, dim3(tiles1 * vwindows), dim3(1024), lds1, s, enc, coarse_cursor, pairs_lo, pairs_hi, S);
-        else if (S.t1 == 16384) hipLaunchKernelGGL(k_sort_l1_scatter_split<16>, dim3(tiles1 * vwindows), dim3(1024), lds1, s, enc, coarse_cursor, pairs_lo, pairs_hi, S);
-        else hipLaunchKernelGGL(k_sort_l1_scatter_split<8>, dim3(tiles1 * vwindows), dim3(1024), lds1, s, enc, coarse_cursor, pairs_lo, pairs_hi, S);
-      }
-      hipLaunchKernelGGL(k_sort_tile_prefix, dim3(1), dim3(SCAN_BLOCK), 0, s, coarse_off, tile_start, S);
-      { Scope s2("sort_hist", s);
-      hipLaunchKernelGGL(k_sort_l2_hist_split, dim3(l2_tiles_max), dim3(256), 0, s, (const uint16_t *)pairs_hi, coarse_off, tile_start, hist, S); }
-      hipLaunchKernelGGL(k_scan_partial, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, s, hist, scan_sums, scan_n);
-      hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(SCAN_BLOCK), 0, s, scan_sums, scan_blocks);
-      hipLaunchKernelGGL(k_scan_final, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, s, hist, scan_sums, offsets, cursor, scan_n);
-      {
-        Scope s3("sort_l2", s);
-        const size_t lds2 = (size_t)(3 * (1u << S.fb) + 32) * 4 + (size_t)S.t2 * 6;   // histogram / offsets / bases + staged indices (4 B) and their bins (2 B)
-        if (S.t2 == 8192) hipLaunchKernelGGL(k_sort_l2_scatter_split<8>, dim3(l2_tiles_max), dim3(1024), lds2, s, (const uint32_t *)pairs_lo, (const uint16_t *)pairs_hi, coarse_off, tile_start, cursor, sorted, S);
-        else hipLaunchKernelGGL(k_sort_l2_scatter_split<16>, dim3(l2_tiles_max), dim3(1024), lds2, s, (const uint32_t *)pairs_lo, (const uint16_t *)pairs_hi, coarse_off, tile_start, cursor, sorted, S);
-      }
-    }
+    CHK(msm_sort_stage(inl, polys_dev, M, n, sh, P, offsets, sorted, s));
     if (piped) { HIPCHK(hipEventRecord(slot.sorted, s)); HIPCHK(hipStreamWaitEvent(st.b, slot.sorted, 0)); }
   }
   {
@@ -241,7 +256,7 @@ int msm_enqueue(const g1_affine_t *bases, const PolyPtrs &inl, const fe_t *const
     {
       Scope sc("msm_accumulate", s);
       HIPCHK(hipMemsetAsync(buckets, 0, (size_t)nbuckets * sizeof(g1_xyzz29_t), s));
-#define ACC_LAUNCH(V) hipLaunchKernelGGL(k_msm_accumulate<V>, dim3(acc_blocks), dim3(256), 0, s, bases, sorted, offsets, nbuckets, buckets, part, part_id, seg_arg, S.nshift, shared ? pre->row_stride : (uint64_t)0, g.debug_gather_mask)
+#define ACC_LAUNCH(V) hipLaunchKernelGGL(k_msm_accumulate<V>, dim3(acc_blocks), dim3(256), 0, s, bases, sorted, offsets, nbuckets, buckets, part, part_id, seg_arg, log2_ceil(n), shared ? pre->row_stride : (uint64_t)0, g.debug_gather_mask)
       ACC_LAUNCH(4);   // <4>: limb products as explicitly chained v_mad (fp29.hpp mac_*).  The C++-multiplier variant <0> (59.5 vs 57.1 ms at 2^26, round 3) and the older A/B variants are no longer instantiated (round 6)
 #undef ACC_LAUNCH
     }
@@ -442,6 +457,120 @@ int msm_host_single(const g1_affine_t *bases, const fe_t *const *polys_host, uin
   resolve_spans();
   { char buf[64]; snprintf(buf, sizeof buf, " host slices=%u c=%d W=%d", K, g.last_c, g.last_w); tr.done(buf); }
   return MI355_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ G2 MSM
+// M MSMs over one G2 basis in device memory (already validated), scalars in device memory; out_host: M x 128 B (normalised G2Affine).
+// One device, one stream: digits + sort (msm_sort_stage, shared = 0: no window tables for G2), segmented accumulation, segmented fix-up,
+// running sums + trees, Horner.  The window size comes from the G1 cost model (msm_shape); workspace roles msm2.* hold 256-byte records.
+static int msm_g2_impl(const g2_affine_t *bases, const fe_t *const *polys, uint32_t M, uint64_t n, void *out_host, bool accumulate_plan = false) {
+  if (M == 0) return MI355_OK;
+  if (n == 0) { memset(out_host, 0, (size_t)M * sizeof(g2_affine_t)); return MI355_OK; }
+  if (n >= (1ull << 31)) return fail(MI355_EBADARG, "msm_g2: n must be < 2^31");
+  MsmShape sh;
+  if (M > 1) {   // a batch that overflows the entry index, the coarse histogram or 8 GiB of bucket records runs as two half batches
+    const int rc0 = msm_shape(n, M, nullptr, sh);
+    if (rc0 != MI355_OK || sh.emax > (1ull << 29) || sh.nbuckets * sizeof(g2_xyzz_t) > (8ull << 30)) {
+      const uint32_t h = M / 2;
+      CHK(msm_g2_impl(bases, polys, h, n, out_host, accumulate_plan));
+      return msm_g2_impl(bases, polys + h, M - h, n, (char *)out_host + (size_t)h * sizeof(g2_affine_t), true);
+    }
+  }
+  CHK(msm_shape(n, M, nullptr, sh));
+  if (!accumulate_plan) { g.last_entries = 0; g.last_host_slices = 1; }
+  CallTrace tr("msm_g2", (uint64_t)M * n, 160.0);
+  hipStream_t s = g.stream;
+  Scope total("msm_g2_total", s);
+  MsmPlan P; P.n = (uint32_t)n; P.batch = M; P.c = sh.c; P.windows = sh.W; P.nb = 1u << (P.c - 1);
+  const uint64_t emax = sh.emax;
+  const uint64_t want_threads = (uint64_t)g.prop.multiProcessorCount * 256 * g.seg_factor;
+  uint64_t seg = (emax + want_threads - 1) / want_threads; if (seg < 16) seg = 16; if (seg > 4096) seg = 4096;
+  P.seg = (uint32_t)seg;
+  const uint32_t nbuckets = (uint32_t)sh.nbuckets, acc_blocks = ceil_div(ceil_div(emax, seg), 256), tn = acc_blocks * 256;
+  PolyPtrs inl; for (int i = 0; i < 8; i++) inl.p[i] = nullptr;
+  const fe_t **polys_dev = nullptr;
+  if (M <= 8) for (uint32_t m = 0; m < M; m++) inl.p[m] = polys[m];
+  else {   // the pointer array is staged through a buffer the library owns (the caller's array may be a temporary)
+    CHK(ws_get("msm2.polys", (size_t)M * sizeof(void *), (void **)&polys_dev));
+    g.polys_stage.assign(polys, polys + M);
+    HIPCHK(hipMemcpyAsync(polys_dev, g.polys_stage.data(), (size_t)M * sizeof(void *), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  uint32_t *offsets, *sorted; g2_xyzz_t *buckets, *part; int32_t *part_id;
+  CHK(ws_get("msm2.offsets", ((size_t)nbuckets + 1) * 4, (void **)&offsets));
+  CHK(ws_get("msm2.sorted", emax * 4, (void **)&sorted));
+  CHK(ws_get("msm2.buckets", (size_t)nbuckets * sizeof(g2_xyzz_t), (void **)&buckets));
+  CHK(ws_get("msm2.part", (size_t)tn * 2 * sizeof(g2_xyzz_t), (void **)&part));
+  CHK(ws_get("msm2.part_id", (size_t)tn * 2 * 4, (void **)&part_id));
+  CHK(msm_sort_stage(inl, polys_dev, M, n, sh, P, offsets, sorted, s, true));
+  {
+    Scope sc("msm_g2_accumulate", s);
+    HIPCHK(hipMemsetAsync(buckets, 0, (size_t)nbuckets * sizeof(g2_xyzz_t), s));   // all zero = the XYZZ identity: empty buckets
+    hipLaunchKernelGGL(k_msm_g2_accumulate, dim3(acc_blocks), dim3(256), 0, s, bases, sorted, offsets, nbuckets, buckets, part, part_id, P.seg, std::min(g.seg_min, P.seg));
+  }
+  {
+    Scope sc("msm_g2_fixup", s);
+    uint32_t N = 2 * tn; const uint32_t waves1 = ceil_div(N, 64);
+    const size_t cap = (size_t)2 * waves1 + (size_t)waves1 / 8 + 512;
+    int32_t *lv_ids; g2_xyzz_t *lv_recs;
+    CHK(ws_get("msm2.segfix_ids", cap * 4, (void **)&lv_ids)); CHK(ws_get("msm2.segfix_recs", cap * sizeof(g2_xyzz_t), (void **)&lv_recs));
+    const int32_t *cur_ids = part_id; const g2_xyzz_t *cur_recs = part; size_t used = 0;
+    while (N > 64) {
+      const uint32_t waves = ceil_div(N, 64);
+      hipLaunchKernelGGL(k_msm_g2_segfix, dim3(ceil_div(N, 256)), dim3(256), 0, s, cur_ids, cur_recs, N, buckets, lv_ids + used, lv_recs + used, 0);
+      cur_ids = lv_ids + used; cur_recs = lv_recs + used; used += (size_t)2 * waves; N = 2 * waves;
+    }
+    hipLaunchKernelGGL(k_msm_g2_segfix, dim3(1), dim3(64), 0, s, cur_ids, cur_recs, N, buckets, (int32_t *)nullptr, (g2_xyzz_t *)nullptr, 1);
+  }
+  g2_affine_t *out_dev; CHK(ws_get("msm2.out", (size_t)M * sizeof(g2_affine_t), (void **)&out_dev));
+  {
+    Scope sc("msm_g2_reduce", s);
+    const uint32_t nb = P.nb, sets = M * P.windows;
+    uint32_t chunk = 64; while (chunk > nb) chunk >>= 1;   // running-sum chains as msm_reduce_tail cuts them
+    while (chunk > g.reduce_min_chunk && (uint64_t)(nb / chunk) * sets < g.reduce_chains) chunk >>= 1;
+    const uint32_t chunks_per_set = nb / chunk, nchunks = chunks_per_set * sets;
+    g2_xyzz_t *chunk_out, *tree_a, *tree_b, *window_sums;
+    CHK(ws_get("msm2.chunk_out", (size_t)nchunks * sizeof(g2_xyzz_t), (void **)&chunk_out));
+    { const size_t lvl = (size_t)ceil_div(chunks_per_set, 256 * TREE_PER_THREAD) * sets + 1;
+      CHK(ws_get("msm2.tree_a", lvl * sizeof(g2_xyzz_t), (void **)&tree_a)); CHK(ws_get("msm2.tree_b", lvl * sizeof(g2_xyzz_t), (void **)&tree_b)); }
+    CHK(ws_get("msm2.window_sums", (size_t)sets * sizeof(g2_xyzz_t), (void **)&window_sums));
+    hipLaunchKernelGGL(k_msm_g2_bucket_reduce, dim3(ceil_div(nchunks, 128)), dim3(128), 0, s, (const g2_xyzz_t *)buckets, chunk_out, nb, sets, chunk);
+    const g2_xyzz_t *cur = chunk_out; uint32_t cnt = chunks_per_set; g2_xyzz_t *bufs[2] = {tree_a, tree_b}; int which = 0;
+    while (true) {
+      const uint32_t outn = ceil_div(cnt, 256 * TREE_PER_THREAD);
+      g2_xyzz_t *dst = outn == 1 ? window_sums : bufs[which];
+      hipLaunchKernelGGL(k_msm_g2_tree_sum, dim3(outn, sets), dim3(256), 0, s, cur, cnt, dst, outn);
+      if (outn == 1) break;
+      cur = dst; cnt = outn; which ^= 1;
+    }
+    hipLaunchKernelGGL(k_msm_g2_final, dim3(M), dim3(64), 0, s, (const g2_xyzz_t *)window_sums, P.windows, P.c, out_dev);
+  }
+  HIPCHK(hipGetLastError());
+  total.close();
+  HIPCHK(hipMemcpyAsync(out_host, out_dev, (size_t)M * sizeof(g2_affine_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  resolve_spans();
+  g.last_c = (int)P.c; g.last_w = (int)P.windows; g.last_entries += emax; g.last_shared = false; g.last_chunks = 1;
+  { char buf[64]; snprintf(buf, sizeof buf, " batch=%u c=%d W=%d", M, g.last_c, g.last_w); tr.done(buf); }
+  return MI355_OK;
+}
+// every base on the twist (device pass), then the MSMs.  EBADARG names the first base that is not.
+static int msm_g2_run(const g2_affine_t *bases, const fe_t *const *polys, uint32_t M, uint64_t n, void *out_host) {
+  if (n) {
+    uint32_t *bad; CHK(ws_get("msm2.validate", 4, (void **)&bad));
+    Scope sc("msm_g2_validate", g.stream);
+    HIPCHK(hipMemsetAsync(bad, 0xff, 4, g.stream));
+    const uint32_t blocks = std::min<uint64_t>(ceil_div(n, 256), (uint64_t)g.prop.multiProcessorCount * 8);
+    hipLaunchKernelGGL(k_msm_g2_validate, dim3(blocks), dim3(256), 0, g.stream, bases, n, g2_twist_b(), bad);
+    HIPCHK(hipGetLastError());
+    uint32_t first_bad = 0xffffffffu;
+    HIPCHK(hipMemcpyAsync(&first_bad, bad, 4, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    sc.close();
+    if (first_bad != 0xffffffffu) return fail(MI355_EBADARG, "msm_g2: base " + std::to_string(first_bad) + " is not on the twist y^2 = x^3 + 3 / (9 + u)");
+  }
+  g_last_devices = 1; g_last_exchange = "none";
+  return msm_g2_impl(bases, polys, M, n, out_host);
 }
 
 }  // namespace mi355
@@ -841,6 +970,52 @@ int mi355_msm_last_run(int *devices_out, const char **exchange_out, int *shared_
   if (devices_out) *devices_out = g_last_devices; if (exchange_out) *exchange_out = g_last_exchange;
   if (shared_tables_out) *shared_tables_out = g_ctx[0].last_shared ? 1 : 0; if (host_slices_out) *host_slices_out = g_ctx[0].last_host_slices;
   return MI355_OK;
+  });
+}
+
+// ---- G2 MSM (single device; bases checked on the twist, not for subgroup membership)
+int mi355_msm_g2_adhoc_host(const void *bases_g2affine_host, const void *scalars_host, uint64_t n, void *out_g2affine_host) {
+  return guarded([&]() -> int {
+  MsmGuard lk;
+  CHK(need_init());
+  if (!out_g2affine_host || (n && (!scalars_host || !bases_g2affine_host))) return fail(MI355_EBADARG, "msm_g2: null pointer");
+  if (n >= (1ull << 31)) return fail(MI355_EBADARG, "msm_g2: n must be < 2^31");
+  fe_t *sc = nullptr; g2_affine_t *bs = nullptr;
+  if (n) {
+    CHK(ws_get("io.scalars", n * sizeof(fe_t), (void **)&sc)); CHK(ws_get("io.g2_bases", n * sizeof(g2_affine_t), (void **)&bs));
+    HIPCHK(hipMemcpyAsync(sc, scalars_host, n * sizeof(fe_t), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(bs, bases_g2affine_host, n * sizeof(g2_affine_t), hipMemcpyHostToDevice, g.stream));
+  }
+  const fe_t *p = sc;
+  return msm_g2_run(bs, &p, 1, n, out_g2affine_host);
+  });
+}
+// device-resident bases and scalars: both must live on the primary device (the G2 MSM runs on one device)
+static int g2_dev_operand(const void *p) {
+  if (slot_of(p, true) != 0) return fail(MI355_EBADARG, "msm_g2: bases and scalars must live on the primary device (G2 MSMs run on one device)");
+  return MI355_OK;
+}
+int mi355_msm_g2_dev(const void *bases_g2affine_dev, const void *scalars_dev, uint64_t n, void *out_g2affine_host) {
+  return guarded([&]() -> int {
+  MsmGuard lk;
+  CHK(need_init());
+  if (!out_g2affine_host || (n && (!scalars_dev || !bases_g2affine_dev))) return fail(MI355_EBADARG, "msm_g2: null pointer");
+  if (n) { CHK(g2_dev_operand(bases_g2affine_dev)); CHK(g2_dev_operand(scalars_dev)); }
+  CHK(bind_ctx(0));
+  const fe_t *p = (const fe_t *)scalars_dev;
+  return msm_g2_run((const g2_affine_t *)bases_g2affine_dev, &p, 1, n, out_g2affine_host);
+  });
+}
+int mi355_msm_g2_batch_dev(const void *bases_g2affine_dev, const void *const *scalars_dev, uint32_t batch, uint64_t n, void *out_g2affine_host) {
+  return guarded([&]() -> int {
+  MsmGuard lk;
+  CHK(need_init());
+  if (!out_g2affine_host || (batch && !scalars_dev) || (batch && n && !bases_g2affine_dev)) return fail(MI355_EBADARG, "msm_g2_batch: null pointer");
+  for (uint32_t m = 0; m < batch; m++) if (n && !scalars_dev[m]) return fail(MI355_EBADARG, "msm_g2_batch: null polynomial pointer");
+  if (batch && n) { CHK(g2_dev_operand(bases_g2affine_dev)); for (uint32_t m = 0; m < batch; m++) CHK(g2_dev_operand(scalars_dev[m])); }
+  CHK(bind_ctx(0));
+  if (batch == 0) return MI355_OK;
+  return msm_g2_run((const g2_affine_t *)bases_g2affine_dev, (const fe_t *const *)scalars_dev, batch, n, out_g2affine_host);
   });
 }
 

@@ -317,6 +317,34 @@ def g2_mul(point: np.ndarray, scalar: np.ndarray) -> np.ndarray:
     return out
 
 
+def g2_msm(bases: np.ndarray, scalars: np.ndarray) -> np.ndarray:
+    """sum_i scalars[i] * bases[i] on the twist (mi355_msm_g2_adhoc_host): bases [n,16] u64 G2Affine, scalars [n,4] u64 Fr (Montgomery)
+    -> normalised G2Affine (16 u64, identity = zeros).  Every base must lie on the twist (Mi355Error EBADARG names the first that does not)."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 16)
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    n = int(scalars.shape[0])
+    assert n == int(bases.shape[0]), "g2_msm: scalars.len() != bases.len()"
+    out = np.zeros(16, dtype=np.uint64)
+    check(lib().mi355_msm_g2_adhoc_host(ptr(bases), ptr(scalars), n, ptr(out)))
+    return out
+
+
+def g2_msm_dev(bases, scalars, n: int) -> np.ndarray:
+    """mi355_msm_g2_dev: bases (n x 128 B) and scalars (n x 32 B) in device memory (DeviceBuffer, torch tensor or address) -> G2Affine."""
+    out = np.zeros(16, dtype=np.uint64)
+    check(lib().mi355_msm_g2_dev(ptr(bases), ptr(scalars), n, ptr(out)))
+    return out
+
+
+def g2_msm_batch_dev(bases, scalars_list, n: int) -> np.ndarray:
+    """mi355_msm_g2_batch_dev: len(scalars_list) scalar vectors over one device basis -> [batch, 16] u64."""
+    m = len(scalars_list)
+    arr = (C.c_void_p * max(m, 1))(*[ptr(s).value for s in scalars_list])
+    out = np.zeros((max(m, 1), 16), dtype=np.uint64)
+    check(lib().mi355_msm_g2_batch_dev(ptr(bases), arr, m, n, ptr(out)))
+    return out[:m]
+
+
 def g1_sum(points: np.ndarray) -> np.ndarray:
     """fold of per-GPU partial results: results.iter().fold(identity, |a, b| a + b)."""
     points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
