@@ -248,6 +248,18 @@ int mi355_fr_prefix_product_dev(void *dst_dev, const void *src_dev, uint64_t n, 
  * scroll fork [EXT-recalled halo2_proofs src/plonk/mv_lookup/prover.rs: phi[i + 1] = phi[i] + sum_j 1 / (beta + f_j[i]) - m[i] / (beta + t[i]);
  * SURVEY 3.2 step 4 "lookup grand-sum"].  Same aliasing and total_out_host rules (the total must be zero for a valid argument).       */
 int mi355_fr_prefix_sum_dev(void *dst_dev, const void *src_dev, uint64_t n, void *total_out_host);
+/* the multiplicity column m of the log-derivative (mv) lookup argument, which the scroll fork computes inside the prover after theta
+ * [EXT-recalled halo2_proofs src/plonk/mv_lookup/prover.rs, `prepare`: a map from each compressed table value to a row of the usable range,
+ * m[row] += 1 per compressed input cell, Error::ConstraintSystemFailure for an input value the table lacks].  m_dev: n words out;
+ * table_dev: n words, rows < table_rows are the table; inputs_dev: host array of n_inputs device pointers, rows < input_rows are read.
+ * m[r] counts the input cells (every column, rows < input_rows) equal to the value table row r holds, where r is the FIRST row of the
+ * table holding that value (flags bit 0: the LAST row); rows >= table_rows of m are zero.  Values are compared as 32-byte words, which
+ * is field equality because Fr words are fully reduced (Data conventions above).  A value absent from the table: MI355_EBADARG,
+ * *missing_out (optional) = (input index << 40) | row of the smallest such pair, m_dev unspecified; otherwise *missing_out = ~0.
+ * n < 2^31, n_inputs x input_rows < 2^32.  Workspace: one pooled mi355_buf block of ~12 B per row (mi355_mem_info counts it, mi355_buf_trim
+ * returns it).  Runs on the library stream of the device that owns m_dev and returns when m is written (the result decides the error).  */
+int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *table_dev, uint64_t table_rows, const void *const *inputs_dev,
+                                       uint32_t n_inputs, uint64_t input_rows, uint32_t flags, uint64_t *missing_out);
 
 /* ---- halo2_proofs::arithmetic::eval_polynomial(poly, point) = sum_i poly[i] * point^i  (the evaluations written to the
  *      transcript in step 9 of create_proof); out_fr_host receives 32 B.  First widening into SURVEY 8f-3.   */

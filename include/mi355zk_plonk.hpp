@@ -402,6 +402,9 @@ inline std::unique_ptr<ProvingKey> keygen(const Protocol &P, const Circuit &C, u
 struct ProofOptions { int devices = 1; int threads = 8; uint32_t commit_batch = 0 /* 0: by column count */; int upload_threads = 1; int early_intt = -1 /* -1: by column count */;
                       bool sparse_uploads = false /* columns that are at least half zeros cross PCIe as (index, value) pairs */;
                       bool packed_multiplicities = false /* the lookup multiplicities cross PCIe as the 4-byte counts they are (mi355_buf_upload_packed); their blinding rows follow as 32-byte words */;
+                      bool device_multiplicities = false /* step 3 computes the multiplicity columns on the device after theta (mi355_fr_lookup_multiplicities_dev), as the scroll fork's
+                                                            mv_lookup prover does on the CPU: the caller's `m` columns are not read (they may be empty), only Circuit::m_blind */;
+                      bool multiplicity_rule_last = false /* with device_multiplicities: a repeated table value's count goes to its LAST usable row (default: the first) */;
                       TranscriptKind transcript = TranscriptKind::ByLayer /* the reference's choice for the protocol's layer (reference_transcript below): Poseidon for 0-5, Evm for 6; or name one */; };
 // the transcript the reference proves a layer with: Poseidon for every proof the next layer verifies in-circuit (layers 0-5, [REF integration/src/prove.rs:30-43,67,95-97] -> snark-verifier-sdk
 // gen_snark_shplonk), Keccak in the EVM layout for layer 6 (gen_evm_proof_shplonk: what the released verifier contract reads).  Files without a layer number are the reference's fixtures (layers 2, 4).
@@ -417,6 +420,7 @@ struct ProofResult {
   double step_ms[11] = {0}; double total_ms = 0;
   uint64_t peak_hbm_bytes = 0, hbm_total_bytes = 0;
   uint64_t sparse_columns = 0, packed_columns = 0, witness_link_bytes = 0;
+  double multiplicity_ms = 0;   // device_multiplicities: compression, counting and blinding rows of every lookup (host wall time, the commitments excluded)
   uint32_t msm = 0, intt = 0, coset_ntt = 0, gate_launches = 0, evals = 0, plan_launches = 0, plan_terms = 0, plan_tmps = 0, plan_constraints = 0, plan_prefix_groups = 0, rotation_sets = 0;
 };
 
@@ -471,10 +475,13 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
   // ---- steps 1-3: the witness crosses PCIe on other host threads (rayon workers in the real caller); commitments as the columns arrive
   std::vector<std::pair<uint32_t, const Column *>> uploads;
   for (uint32_t i = 0; i < A; i++) uploads.push_back({P.phase0[0] + i, &wit.advice[i]});
-  for (uint32_t l = 0; l < NL; l++) uploads.push_back({P.phase0[1] + l, &wit.m[l]});
+  const bool dev_m = opt.device_multiplicities && NL > 0;
+  if (dev_m && wit.m_blind.size() != NL) throw std::invalid_argument("create_proof: device_multiplicities needs the blinding values of every multiplicity column (Circuit::m_blind)");
+  if (!dev_m) for (uint32_t l = 0; l < NL; l++) uploads.push_back({P.phase0[1] + l, &wit.m[l]});
   uploads.push_back({P.random_poly, &wit.random_poly});                                   // step 5's polynomial (coefficients): needed last, crosses last
   for (const auto &up : uploads) poly[up.first];
   poly[P.inst0];
+  for (uint32_t l = 0; l < NL; l++) poly[P.phase0[1] + l];
   for (const auto &c : P.perm) poly[c.z];                                                 // every entry exists before the uploaders start: the map's structure does not change under them
   for (const auto &l : P.lookups) poly[l.phi];
   std::mutex mu; std::condition_variable cv; std::vector<char> arrived(uploads.size(), 0); std::string upload_error;
@@ -537,7 +544,45 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
   std::vector<Fr> ch;
   commit_phase(0, A);                                                                   // step 2
   for (uint32_t i = 0; i < P.num_challenge[0]; i++) ch.push_back(T.squeeze_challenge()); // theta
-  commit_phase(A, A + NL);                                                              // step 3 (the multiplicities are the caller's: they do not depend on theta for the lookups halo2 compresses)
+  if (!dev_m) commit_phase(A, A + NL);                                                  // step 3 (the multiplicities are the caller's: they do not depend on theta for the lookups halo2 compresses)
+  else {
+    // step 3 as the scroll fork's mv_lookup prover runs it [EXT-recalled halo2_proofs src/plonk/mv_lookup/prover.rs, `prepare`]: table and input compressed with theta (the
+    // expressions of step 4 without the beta term, into TMP 0 / 1), every input cell of the usable rows looked up in the table's usable rows on the device, the rng's blinding
+    // values into the last rows.  The instance column still holds its Lagrange values here (step 1's inverse transform comes after step 3).  Commitments as commit_phase makes them.
+    const auto t_m = Clock::now();
+    Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, ch);
+    std::vector<DevicePoly> tmp;
+    auto tmp_at = [&](uint32_t i) -> DevicePoly & { while (tmp.size() <= i) tmp.emplace_back(n, 0); return tmp[i]; };
+    auto resolve = [&](const Atom &a) -> const void * {
+      if (a.kind == A_TMP) return tmp_at(a.idx).p;
+      if (a.kind == A_COMMON) { if (a.idx != pk.identity_common) throw std::invalid_argument("step 3 reads no common polynomial but X"); return pk.common_lagrange[a.idx].p; }
+      if (P.is_pre(a.idx)) { if (!pk.pre_lagrange[a.idx].p) throw std::invalid_argument("step 3: Lagrange values of a preprocessed polynomial were not kept"); return pk.pre_lagrange[a.idx].p; }
+      return poly.at(a.idx).p;   // advice (committed in step 2) or the instance column (Lagrange values)
+    };
+    std::vector<uint32_t> made;
+    for (uint32_t l = 0; l < NL; l++) {
+      const Lookup &lk = P.lookups[l];
+      cmp.tmp_base = 2; cmp.tmp_next = 0;
+      cmp.emit(0, cmp.compile(*lk.table)); cmp.emit(1, cmp.compile(*lk.input));
+      for (const auto &L : cmp.out) { run_launch(L, tmp_at((uint32_t)L.dst).p, n, fr_one(), L.accumulate, resolve); R.gate_launches++; }
+      cmp.out.clear();
+      DevicePoly m(n, 0);
+      const void *inputs[1] = {tmp_at(1).p}; uint64_t missing = ~0ull;
+      const int rc = mi355_fr_lookup_multiplicities_dev(m.p, n, tmp_at(0).p, u, inputs, 1, u, opt.multiplicity_rule_last ? 1u : 0u, &missing);
+      if (rc == MI355_EBADARG && missing != ~0ull) throw Error(MI355_EBADARG, "lookup " + std::to_string(l) + ": input row " + std::to_string(missing & ((uint64_t(1) << 40) - 1)) + " is not in the table");
+      check(rc);
+      if (P.blind) check(mi355_buf_upload(m.at(u + 1), wit.m_blind[l].data(), P.blind * 32));
+      { std::lock_guard<std::mutex> lk_(mu); poly.at(P.phase0[1] + l) = std::move(m); }
+      made.push_back(P.phase0[1] + l);
+    }
+    tmp.clear();
+    R.multiplicity_ms = ms_since(t_m);
+    std::vector<uint32_t> pending;
+    for (size_t i = 0; i < made.size(); i++) {
+      if (!batch_cols) { commit_one(h_g_lagrange, poly.at(made[i]).p); to_coeff_early({made[i]}); }
+      else { pending.push_back(made[i]); if (pending.size() == batch_cap || i + 1 == made.size()) { commit_many(h_g_lagrange, pending); to_coeff_early(pending); pending.clear(); } }
+    }
+  }
   for (uint32_t i = 0; i < P.num_challenge[1]; i++) ch.push_back(T.squeeze_challenge()); // beta, gamma
   const Fr beta = ch.at(1), gamma = ch.at(2);
   lap(2);

@@ -36,6 +36,7 @@ struct Circuit {
   std::vector<Fr> instances;
   std::vector<Column> advice, m;
   std::vector<std::vector<uint32_t>> m_counts;   // the multiplicities as the integers they are (rows below the l_last row; the blinding rows of `m` are random field elements)
+  std::vector<std::vector<Fr>> m_blind;           // per lookup the blinding rows u + 1 .. n - 1 of `m`: all a prover that counts the multiplicities itself needs of it
   std::vector<std::vector<Fr>> z_blind, phi_blind;
   Column random_poly;                 // coefficients
   std::vector<CopyPair> pairs; std::vector<PermColumn> pcols; std::vector<Fr> omega_pow;
@@ -277,6 +278,7 @@ inline std::unique_ptr<Circuit> build_circuit(const Protocol &P, const CircuitOp
     C->parallel(table_rows, [&](uint64_t lo, uint64_t hi) { for (uint64_t i = lo; i < hi; i++) mc[i] = fr_small(cnt[i]); });
     cnt.resize(n, 0); C->m_counts.push_back(std::move(cnt));
     Rng g(blind_stream()); for (uint64_t r = u + 1; r < n; r++) mc[r] = opt.zero_blinding ? fr_zero() : g.uniform();
+    C->m_blind.emplace_back(mc.begin() + (long)(u + 1), mc.end());
   }
   // ---- whatever preprocessed polynomial nothing assigned stays all-zero (materialised), the permutation's bookkeeping, the prover's randomness
   for (uint32_t p = 0; p < P.num_pre; p++) { bool sig = false; for (const auto &c : C->pcols) sig = sig || c.sigma == p; if (!sig) (void)pre_col(p); }

@@ -53,6 +53,29 @@ pub fn commit_columns(basis: &Arc<GpuBasis>, cols: &[&DevicePoly]) -> Option<Vec
     if cols.len() == 1 { basis.multiexp_dev(cols[0]).map(|c| vec![c]) } else { basis.multiexp_many_dev(cols) }
 }
 
+/// R2b (hpp: step 3 with `ProofOptions::device_multiplicities`): the multiplicity column of one mv-lookup, computed on the device after theta -- what the
+/// fork's `mv_lookup::prover::prepare` builds with a hash map on the CPU, so the caller no longer supplies `m`.  `launches` (the lookup's table and input
+/// expressions compiled with theta only, no beta term) leave the compressed table in TMP[0] and the compressed input in TMP[1]; rows `0 .. usable` of both
+/// are looked at (the usable rows), the first table row of a repeated value takes its count (`last_rule`: the last one), rows from `usable` on are zero and the
+/// rng's blinding values go into the last `blind.len()` rows.  Err((0, row)): the input of that row is not in the table -- halo2's
+/// `Error::ConstraintSystemFailure`, no proof.  The caller commits the returned columns with R2, batched like the advice columns.
+pub fn lookup_multiplicities(launches: &[Launch], operand: &dyn Fn(Atom) -> *const c_void, tmp: &mut [DevicePoly], n: usize, usable: usize, last_rule: bool, blind: &[Fr]) -> Result<DevicePoly, (u64, u64)> {
+    let fail = (u64::MAX, u64::MAX);
+    let tmp_ptr: Vec<*mut c_void> = tmp.iter_mut().map(|t| t.as_mut_ptr()).collect();
+    for l in launches { run_launch(l, tmp_ptr[l.dst.ok_or(fail)?], n, None, l.accumulate, operand).ok_or(fail)?; }
+    let mut m = DevicePoly::zeroed(n, 0).ok_or(fail)?;
+    let inputs: [*const c_void; 1] = [tmp_ptr[1] as *const c_void];
+    let mut missing: u64 = u64::MAX;
+    unsafe {
+        let rc = mi355zk::mi355_fr_lookup_multiplicities_dev(m.as_mut_ptr(), n as u64, tmp_ptr[0] as *const c_void, usable as u64, inputs.as_ptr(), 1, usable as u64,
+                                                             last_rule as u32, &mut missing);
+        if rc == 1 && missing != u64::MAX { return Err((missing >> 40, missing & ((1u64 << 40) - 1))); }
+        if rc != 0 { return Err(fail); }
+        if !blind.is_empty() && mi355zk::mi355_buf_upload((m.as_mut_ptr() as *mut u8).add(32 * (usable + 1)) as *mut c_void, blind.as_ptr() as *const c_void, 32 * blind.len() as u64) != 0 { return Err(fail); }
+    }
+    Ok(m)
+}
+
 /// R3 (hpp: step 4, permutation).  One chunk's grand product from Lagrange values: `launches` leave prod_j (c_j + beta delta^j X + gamma) in TMP[0] and
 /// prod_j (c_j + beta sigma_j + gamma) in TMP[1]; z[i + 1] = z[i] TMP[0][i] / TMP[1][i], scaled by `carry` = the previous chunk's value at the l_last row
 /// (the z_c(X) - z_(c-1)(omega^last X) link of the protocol), the last `blind.len()` rows overwritten with the prover's blinding values.

@@ -1,10 +1,12 @@
 // lib_aux.hip -- libmi355zk.so, the translation unit of the kernels either side of MSM / NTT: the DFT over G1 points
 // (g1fft.hpp: g_to_lagrange, ParamsKZG::downsize), the multiplicative scans of the permutation / lookup arguments and kate_division
-// (frscan.hpp), Curve::batch_normalize, and the one G2 scalar multiple of ParamsKZG::setup (g2.hpp).  Host logic only.
+// (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), and the multiplicities of the mv-lookup argument
+// (lookup.hpp).  Host logic only.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #include "g1fft.hpp"
 #include "frscan.hpp"
 #include "g2.hpp"
+#include "lookup.hpp"
 #include "lib_common.hpp"
 #include <thread>
 
@@ -308,6 +310,62 @@ int mi355_host_compact_nonzero(const void *src_host, uint64_t n, uint32_t *idx_o
   { std::vector<std::thread> th; for (int t = 1; t < T; t++) th.emplace_back(write_job, t); write_job(0); for (auto &x : th) x.join(); }
   *count_out = cnt[T];
   return MI355_OK;
+  });
+}
+
+// ---- the multiplicity column m of the mv-lookup argument (lookup.hpp): hash set of the table rows -> counts per row -> Montgomery Fr.  Workspace: ONE pooled
+// mi355_buf block (8 B of error word, 4 B per slot for the next power of two >= 2 x table_rows, 4 B per row of m: ~12 B per row), handed back to the pool on return
+// (mi355_mem_info counts it; mi355_buf_trim gives it back to HIP).  Synchronous: the error word is read back before the call returns.
+int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *table_dev, uint64_t table_rows, const void *const *inputs_dev, uint32_t n_inputs, uint64_t input_rows,
+                                       uint32_t flags, uint64_t *missing_out) {
+  return guarded([&]() -> int {
+  int slot; CHK(common_slot({m_dev, table_dev}, &slot, "fr_lookup_multiplicities"));
+  for (uint32_t c = 0; inputs_dev && c < n_inputs; c++) { int s2; CHK(common_slot({m_dev, table_dev, inputs_dev[c]}, &s2, "fr_lookup_multiplicities")); }
+  DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (missing_out) *missing_out = ~0ull;
+  if (n == 0) return MI355_OK;
+  if (!m_dev || !table_dev || (n_inputs && !inputs_dev)) return fail(MI355_EBADARG, "fr_lookup_multiplicities: null pointer");
+  for (uint32_t c = 0; c < n_inputs; c++) if (!inputs_dev[c] && input_rows) return fail(MI355_EBADARG, "fr_lookup_multiplicities: null input column " + std::to_string(c));
+  if (n >= (1ull << 31)) return fail(MI355_EBADARG, "fr_lookup_multiplicities: n must be < 2^31");
+  if (table_rows > n || input_rows > n) return fail(MI355_EBADARG, "fr_lookup_multiplicities: table_rows and input_rows must not exceed n");
+  if (n_inputs >= (1u << 24)) return fail(MI355_EBADARG, "fr_lookup_multiplicities: more than 2^24 input columns");
+  if ((uint64_t)n_inputs * input_rows >= (1ull << 32)) return fail(MI355_EBADARG, "fr_lookup_multiplicities: n_inputs x input_rows must be < 2^32 (u32 counts)");
+  if (flags & ~1u) return fail(MI355_EBADARG, "fr_lookup_multiplicities: unknown flag bits");
+  const bool last = flags & 1u;
+  const uint64_t S = std::max<uint64_t>(64, 1ull << log2_ceil(2 * table_rows));
+  const uint32_t mask = (uint32_t)(S - 1);
+  const uint64_t off_slots = 256, off_cnt = off_slots + ((S * 4 + 255) & ~255ull), bytes = off_cnt + n * 4;
+  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
+  int rc = MI355_OK; unsigned long long err_host = ~0ull;
+  [&]() {
+    hipStream_t s = g.stream;
+    unsigned long long *err = (unsigned long long *)ws; uint32_t *slots = (uint32_t *)((char *)ws + off_slots), *cnt = (uint32_t *)((char *)ws + off_cnt);
+    if (hipMemsetAsync(ws, 0xff, off_cnt, s) != hipSuccess || hipMemsetAsync(cnt, 0, n * 4, s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_lookup_multiplicities: memset failed"); return; }
+    Scope sc("lookup_multiplicities");
+    const fe_t *T = (const fe_t *)table_dev;
+    if (table_rows) {
+      const dim3 grid((uint32_t)std::min<uint64_t>(ceil_div(table_rows, LK_THREADS), 65535u * 4));
+      if (last) hipLaunchKernelGGL(k_lk_insert<true>, grid, dim3(LK_THREADS), 0, s, T, table_rows, slots, mask);
+      else hipLaunchKernelGGL(k_lk_insert<false>, grid, dim3(LK_THREADS), 0, s, T, table_rows, slots, mask);
+    }
+    // ~8 192 waves per column at most (one resident wave per SIMD slot of the chip, a few over): the hot row of each is one atomic at the end
+    const uint64_t wave_rows = std::max<uint64_t>(2048, (ceil_div(input_rows, 8192) + 63) & ~63ull);
+    const uint64_t waves = ceil_div(input_rows, wave_rows);
+    for (uint32_t c = 0; c < n_inputs && input_rows; c++)
+      hipLaunchKernelGGL(k_lk_probe, dim3(ceil_div(waves, LK_THREADS / 64)), dim3(LK_THREADS), 0, s, (const fe_t *)inputs_dev[c], input_rows, (uint64_t)c, T, (const uint32_t *)slots, mask, cnt, err, wave_rows);
+    hipLaunchKernelGGL(k_expand_packed<4>, dim3((uint32_t)std::min<uint64_t>(ceil_div(n, 256), 65535u * 4)), dim3(256), 0, s, (fe_t *)m_dev, (const uint8_t *)cnt, n);
+    sc.close();
+    if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_lookup_multiplicities: kernel launch failed"); return; }
+    if (hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_lookup_multiplicities: stream synchronize failed"); return; }
+  }();
+  (void)mi355_buf_free(ws);
+  if (rc != MI355_OK) return rc;
+  if (err_host != ~0ull) {
+    if (missing_out) *missing_out = err_host;
+    return fail(MI355_EBADARG, "fr_lookup_multiplicities: input " + std::to_string(err_host >> 40) + ", row " + std::to_string(err_host & ((1ull << 40) - 1)) + " is not in the table");
+  }
+  return finish_async();
   });
 }
 

@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import check, lib, ptr
+from ._capi import Mi355Error, check, lib, ptr
 
 R_MOD = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 P_MOD = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
@@ -292,6 +292,28 @@ def prefix_sum(src, dst=None, want_total: bool = False):
     total = np.zeros(4, dtype=np.uint64) if want_total else None
     check(lib().mi355_fr_prefix_sum_dev(ptr(dst), ptr(src), src.numel() * src.element_size() // 32, ptr(total) if want_total else None))
     return (dst, total) if want_total else dst
+
+
+def lookup_multiplicities(table, inputs, table_rows: int, input_rows: int, last: bool = False):
+    """the multiplicity column m of the mv-lookup argument (mi355_fr_lookup_multiplicities_dev) on device tensors: `table` holds n words (rows < table_rows
+    are the table), `inputs` is one tensor or a list of them (rows < input_rows read).  m[r] = how many input cells equal the value of table row r, where r is
+    the first row holding that value (last=True: the last); rows >= table_rows are zero.  Returns m as a new tensor like `table`.  A value missing from the
+    table raises Mi355Error (EBADARG) whose `.column` / `.row` name the smallest such (input, row)."""
+    import torch
+    if not isinstance(inputs, (list, tuple)):
+        inputs = [inputs]
+    n = table.numel() * table.element_size() // 32
+    for t in inputs:
+        assert t.numel() * t.element_size() >= 32 * input_rows, "an input column is shorter than input_rows"
+    m = torch.empty_like(table)
+    arr = (C.c_void_p * max(1, len(inputs)))(*[t.data_ptr() for t in inputs])
+    missing = C.c_uint64(0)
+    rc = lib().mi355_fr_lookup_multiplicities_dev(ptr(m), n, ptr(table), table_rows, arr, len(inputs), input_rows, 1 if last else 0, C.byref(missing))
+    if rc != 0:
+        err = Mi355Error(rc, lib().mi355_last_error().decode())
+        err.column, err.row = (missing.value >> 40, missing.value & ((1 << 40) - 1)) if rc == 1 and missing.value != (1 << 64) - 1 else (None, None)
+        raise err
+    return m
 
 
 # halo2curves bn256 G2 generator (x.c0, x.c1, y.c0, y.c1) [EXT-recalled src/bn256/curve.rs]; the same four words are the first pairing

@@ -82,3 +82,30 @@ def run_process(layers, ks=None, out_dir: str | None = None, args=(), env=None, 
                 lay[name] = f.read()
         lay["protocol_path"] = protos[i]
     return rec
+
+
+def run_lookup_multiplicities(layer: int, k: int | None = None, out_dir: str | None = None, args=(), env=None, timeout: int = 1800, protocol_file: str | None = None, **shape) -> dict:
+    """tests/cpp/test_lookup_multiplicities.cpp: one layer proven by the default route (the builder's multiplicity columns handed in) and by the device route
+    (ProofOptions::device_multiplicities, the m columns emptied).  Returns the program's record with `proof` (device route), `proof_default`, `vk` and `instances`;
+    args: "--rule last", "--corrupt-lookup", "--devices D"."""
+    from . import build
+    out_dir = out_dir or tempfile.mkdtemp(prefix=f"mi355_lookup_m_l{layer}_")
+    os.makedirs(out_dir, exist_ok=True)
+    proto = write_protocol(layer, out_dir, k, protocol_file, **shape)
+    e = dict(os.environ)
+    e.update(env or {})
+    t0 = time.perf_counter()
+    out = subprocess.run([build.build_cpp("test_lookup_multiplicities"), "--protocol", proto, "--out", out_dir] + list(args), capture_output=True, text=True, timeout=timeout, env=e)
+    line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
+    rec = {"layer": layer, "ok": False, "returncode": out.returncode, "out_dir": out_dir, "protocol_path": proto, "process_wall_s": time.perf_counter() - t0}
+    if line is None:
+        rec["error"] = (out.stdout + out.stderr)[-1200:]
+        return rec
+    rec.update(json.loads(line))
+    rec["returncode"] = out.returncode
+    for name in ("proof", "proof_default", "vk", "instances"):
+        p = os.path.join(out_dir, name + ".bin")
+        if os.path.exists(p):
+            with open(p, "rb") as f:
+                rec[name] = f.read()
+    return rec
