@@ -122,7 +122,16 @@ int mi355_srs_register_dev(const void *bases_affine_dev, uint64_t n, int copy, u
  * (u32 LE k | g[2^k] x 64 B | g_lagrange[2^k] x 64 B | g2 128 B | s_g2 128 B; any other length is rejected, as load_params does)
  * streamed straight into device memory through two pinned staging buffers and registered as two library-owned bases.
  * flags bit 0: validate every point on the device (identity, or reduced coordinates on y^2 = x^3 + 3 -- the check SerdeFormat::RawBytes
- * makes on the CPU and RawBytesUnchecked skips).  g2_out / s_g2_out (optional, 128 B each) receive the two G2 points untouched.     */
+ * makes on the CPU and RawBytesUnchecked skips).  g2_out / s_g2_out (optional, 128 B each) receive the two G2 points untouched.
+ * flags bit 1: the file is SerdeFormat::Processed, the other format ParamsKZG::read_custom accepts [EXT-recalled poly/kzg/commitment.rs]:
+ * u32 LE k | g[2^k] x 32 B | g_lagrange[2^k] x 32 B | g2 64 B | s_g2 64 B, so the required length is 4 + 2 * 2^k * 32 + 128 (with bit 1 clear such a
+ * file is rejected for its length as before; with bit 1 set a RawBytes file is).  The 32-byte words (G1Affine::to_bytes, see mi355_g1_decompress_dev)
+ * stream through the same two pinned buffers into a pooled device block and every chunk is decompressed on the device straight into the SRS shard it
+ * belongs to, the copy of chunk i + 1 under the square roots of chunk i.  A word that is no point: MI355_EBADARG naming basis (g / g_lagrange) and index,
+ * nothing registered.  Bit 0 is implied (a decompressed point is on the curve by construction).  g2_out / s_g2_out still receive 128-byte G2Affine
+ * values, decoded on the host inside the library and checked to be on the twist.  Their 64-byte layout is recalled from halo2curves at the pinned commit
+ * and NOT pinned by any fixture of the reference: x.c0 then x.c1 as canonical little-endian words, bit 6 of byte 63 = parity of canonical y.c0,
+ * identity = 64 zero bytes.                                                                                                              */
 int mi355_srs_load_params_file(const char *path, uint32_t flags, uint32_t *k_out, uint64_t *g_handle_out, uint64_t *g_lagrange_handle_out, void *g2_out, void *s_g2_out);
 /* `&params.g[..n]` as a handle of its own (ParamsKZG::downsize keeps g[..2^k]; load_params_map clones + downsizes
  * [REF integration/tests/integration.rs:17-22]): the first n points of `parent_handle`, SHARING its device memory and window tables --
@@ -166,6 +175,19 @@ int mi355_g1_sum_host(const void *g1_points_host, uint64_t n, void *out_g1_host)
  * must not overlap; the _dev variant is asynchronous on the library stream.                                                          */
 int mi355_g1_batch_normalize_dev(const void *g1_points_dev, void *affine_out_dev, uint64_t n);
 int mi355_g1_batch_normalize_host(const void *g1_points_host, void *affine_out_host, uint64_t n);
+/* halo2curves G1Affine::from_bytes / to_bytes over whole arrays [EXT-recalled halo2curves derive/curve.rs; the 32-byte form is pinned by fixture KAT A4]:
+ * the compressed word of SerdeFormat::Processed params files, proofs and .vkey files = little-endian canonical x, bit 6 of byte 31 = parity of canonical y,
+ * bit 7 ignored, identity = 32 zero bytes.  decompress: n words (32 B) -> n affine points (64 B, Montgomery, reduced), one square root in Fq per point on the
+ * device.  A word that is no point (x >= q; x^3 + 3 a non-residue; x = 0 with the sign bit set) is written as the identity, the call returns MI355_EBADARG,
+ * mi355_last_error() names the smallest such index and *first_bad_out (optional) receives it; *first_bad_out = ~0 when every word decodes.  compress: n affine
+ * points (reduced coordinates, trusted as everywhere in this ABI) -> n words.  Input and output must not overlap; device pointers 16-byte aligned; n < 2^32.
+ * _dev: runs on the library stream of the device that owns the output; decompress returns when the error word has been read (the result decides the return
+ * code), compress is asynchronous.  _host: staged through device workspace in chunks of 2^22 points, synchronous.  No CPU fallback (MI355_ENODEVICE).
+ * Kernels report as "g1_decompress" / "g1_compress" in mi355_profile_get.  No subgroup check (G1 of BN254 has cofactor 1).                              */
+int mi355_g1_decompress_dev(const void *bytes_dev, void *affine_out_dev, uint64_t n, uint64_t *first_bad_out);
+int mi355_g1_decompress_host(const void *bytes_host, void *affine_out_host, uint64_t n, uint64_t *first_bad_out);
+int mi355_g1_compress_dev(const void *affine_dev, void *bytes_out_dev, uint64_t n);
+int mi355_g1_compress_host(const void *affine_host, void *bytes_out_host, uint64_t n);
 /* (per calling thread) normalise = 0: subsequent MSM results are SOME Jacobian representative of the sum (as best_multiexp's C::Curve is) instead of the
  * normalised one; saves the serial field inversion (~0.4 ms) where the result is folded again anyway (per-GPU partial sums).      */
 int mi355_msm_set_normalise(int on);
@@ -311,7 +333,7 @@ int mi355_srs_read_host(uint64_t handle, uint64_t offset, uint64_t n, void *out_
 
 /* ---- measurement hooks (bench.py): HIP-event timing of the kernels of the most recent MSM / NTT call.       */
 int mi355_profile_enable(int on);
-/* name in {"msm_total","msm_digits","msm_sort","msm_accumulate","msm_reduce","ntt_total","ntt_pass"}; returns the
+/* name in {"msm_total","msm_digits","msm_sort","msm_accumulate","msm_reduce","ntt_total","ntt_pass","g1_decompress","g1_compress"}; returns the
  * accumulated milliseconds and launch count since the last mi355_profile_reset().                             */
 int mi355_profile_get(const char *name, double *ms_out, uint64_t *launches_out);
 int mi355_profile_reset(void);

@@ -16,7 +16,9 @@
 // it reuses the product's own limb code (scroll-prover_amd/csrc/fp.hpp compiles for the host).
 #pragma once
 #include <array>
+#include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -124,6 +126,36 @@ inline bool g1_from_bytes(const G1Bytes &b, G1Affine &out) {
   std::memcpy(out.data(), &x, 32); std::memcpy(out.data() + 4, &y, 32);
   return true;
 }
+
+// The same two conversions for whole vectors, on the device (mi355_g1_compress_host / mi355_g1_decompress_host): what ParamsKZG::write_custom / read_custom
+// do per point for SerdeFormat::Processed, and the form in which a downsized g_lagrange or the commitments of a .vkey are dumped.  g1_from_bytes throws
+// Error(MI355_EBADARG) naming the smallest index that is no curve point (from_bytes' CtOption is none there).  The single-point helpers above stay host code.
+inline std::vector<G1Bytes> g1_to_bytes(const G1Affine *points, size_t n) {
+  std::vector<G1Bytes> out(n);
+  check(mi355_g1_compress_host(points, out.data(), n));
+  return out;
+}
+inline std::vector<G1Bytes> g1_to_bytes(const std::vector<G1Affine> &points) { return g1_to_bytes(points.data(), points.size()); }
+inline std::vector<G1Affine> g1_from_bytes(const G1Bytes *words, size_t n) {
+  std::vector<G1Affine> out(n);
+  check(mi355_g1_decompress_host(words, out.data(), n, nullptr));
+  return out;
+}
+inline std::vector<G1Affine> g1_from_bytes(const std::vector<G1Bytes> &words) { return g1_from_bytes(words.data(), words.size()); }
+// the 64-byte compressed form of a G2Affine in a Processed params file (x.c0, x.c1 canonical little-endian, bit 6 of byte 63 = parity of canonical y.c0,
+// identity = all zero) [EXT-recalled halo2curves; not pinned by a fixture of the reference].  The inverse runs inside mi355_srs_load_params_file.
+inline std::array<uint8_t, 64> g2_to_bytes(const std::array<uint8_t, 128> &p) {
+  std::array<uint8_t, 64> out{};
+  bool ident = true; for (auto b : p) ident = ident && b == 0;
+  if (ident) return out;
+  zk::fe_t c[3]; std::memcpy(c, p.data(), 96);
+  for (int i = 0; i < 3; i++) c[i] = zk::Fq::to_canonical(c[i]);
+  std::memcpy(out.data(), &c[0], 32); std::memcpy(out.data() + 32, &c[1], 32);
+  out[63] |= (uint8_t)((c[2].l[0] & 1u) << 6);
+  return out;
+}
+// halo2_proofs::SerdeFormat, the two members ParamsKZG files are passed around in (RawBytesUnchecked = RawBytes with validate = false)
+enum class SerdeFormat { RawBytes, Processed };
 
 // ------------------------------------------------------------------------------------------------ resident polynomials
 // One vector of Fr resident in HBM: a mi355_buf_alloc block (the C++ twin of the Rust shim's DevicePoly).  Move-only; the destructor hands the
@@ -239,6 +271,54 @@ class ParamsKZG {
     std::unique_ptr<ParamsKZG> p(new ParamsKZG(kk, hg, hl));
     p->g2 = g2; p->s_g2 = sg2;
     return p;
+  }
+  // ParamsKZG::read_custom(reader, format): Processed files (32-byte compressed points) take the same streaming route and are decompressed on the device
+  static std::unique_ptr<ParamsKZG> read_custom(const std::string &path, SerdeFormat format, bool validate = false) {
+    uint32_t kk = 0; uint64_t hg = 0, hl = 0; std::array<uint8_t, 128> g2{}, sg2{};
+    check(mi355_srs_load_params_file(path.c_str(), (validate ? 1u : 0u) | (format == SerdeFormat::Processed ? 2u : 0u), &kk, &hg, &hl, g2.data(), sg2.data()));
+    std::unique_ptr<ParamsKZG> p(new ParamsKZG(kk, hg, hl));
+    p->g2 = g2; p->s_g2 = sg2;
+    return p;
+  }
+  // ParamsKZG::write_custom(writer, format).  Processed: the bases are compressed on the device that holds them (mi355_srs_dev_ptr + mi355_g1_compress_dev) and
+  // only the words are downloaded; with the bases sharded over several devices the points come back through mi355_srs_read_host and the host-pointer form.
+  void write_custom(const std::string &path, SerdeFormat format) const {
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) throw Error(MI355_EBADARG, "write_custom: cannot open " + path);
+    struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{f};
+    auto put = [&](const void *p, size_t bytes) { if (std::fwrite(p, 1, bytes, f) != bytes) throw Error(MI355_EHIP, "write_custom: short write to " + path); };
+    const uint8_t hdr[4] = {(uint8_t)k, (uint8_t)(k >> 8), (uint8_t)(k >> 16), (uint8_t)(k >> 24)};
+    put(hdr, 4);
+    const uint64_t chunk = std::min<uint64_t>(n, uint64_t(1) << 22);
+    if (format == SerdeFormat::RawBytes) {
+      std::vector<G1Affine> pts(chunk);
+      for (uint64_t h : {g_, gl_}) for (uint64_t lo = 0; lo < n; lo += chunk) { const uint64_t m = std::min(chunk, n - lo); check(mi355_srs_read_host(h, lo, m, pts.data())); put(pts.data(), m * 64); }
+      put(g2.data(), 128); put(s_g2.data(), 128);
+      return;
+    }
+    std::vector<G1Bytes> words(chunk);
+    const bool one_device = mi355_mem_info(1, nullptr, nullptr, nullptr, nullptr, nullptr) != MI355_OK;   // no second device slot: every basis sits whole on the primary device
+    if (one_device) {
+      void *buf = nullptr; check(mi355_buf_alloc(chunk * 32, 0, &buf));
+      struct Free { void *p; ~Free() { (void)mi355_buf_free(p); } } free_buf{buf};
+      for (uint64_t h : {g_, gl_}) {
+        void *base = nullptr; check(mi355_srs_dev_ptr(h, &base));
+        for (uint64_t lo = 0; lo < n; lo += chunk) {
+          const uint64_t m = std::min(chunk, n - lo);
+          check(mi355_g1_compress_dev(static_cast<const char *>(base) + lo * 64, buf, m));
+          check(mi355_buf_download(words.data(), buf, m * 32));
+          put(words.data(), m * 32);
+        }
+      }
+    } else {
+      std::vector<G1Affine> pts(chunk);
+      for (uint64_t h : {g_, gl_}) for (uint64_t lo = 0; lo < n; lo += chunk) {
+        const uint64_t m = std::min(chunk, n - lo);
+        check(mi355_srs_read_host(h, lo, m, pts.data())); check(mi355_g1_compress_host(pts.data(), words.data(), m)); put(words.data(), m * 32);
+      }
+    }
+    const auto a = g2_to_bytes(g2), b = g2_to_bytes(s_g2);
+    put(a.data(), 64); put(b.data(), 64);
   }
   std::array<uint8_t, 128> g2{}, s_g2{};
   ParamsKZG(const ParamsKZG &) = delete;

@@ -51,6 +51,12 @@ extern "C" {
     pub fn mi355_msm_g1_batch_host(srs: u64, base_offset: u64, scalars_host: *const *const c_void, batch: u32, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g1_adhoc_host(bases: *const c_void, scalars: *const c_void, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_g1_batch_normalize_host(g1_points_host: *const c_void, affine_out_host: *mut c_void, n: u64) -> c_int;
+    pub fn mi355_g1_decompress_dev(bytes_dev: *const c_void, affine_out_dev: *mut c_void, n: u64, first_bad_out: *mut u64) -> c_int;
+    pub fn mi355_g1_decompress_host(bytes_host: *const c_void, affine_out_host: *mut c_void, n: u64, first_bad_out: *mut u64) -> c_int;
+    pub fn mi355_g1_compress_dev(affine_dev: *const c_void, bytes_out_dev: *mut c_void, n: u64) -> c_int;
+    pub fn mi355_g1_compress_host(affine_host: *const c_void, bytes_out_host: *mut c_void, n: u64) -> c_int;
+    pub fn mi355_srs_load_params_file(path: *const c_char, flags: u32, k_out: *mut u32, g_handle_out: *mut u64, g_lagrange_handle_out: *mut u64,
+                                      g2_out: *mut c_void, s_g2_out: *mut c_void) -> c_int;
     pub fn mi355_ntt_fr_host(data_host: *mut c_void, log_n: u32, omega: *const c_void) -> c_int;
     pub fn mi355_intt_fr_host(data_host: *mut c_void, log_n: u32, omega_inv: *const c_void, divisor: *const c_void) -> c_int;
     pub fn mi355_coeff_to_extended_host(dst: *mut c_void, coeffs: *const c_void, log_n: u32, log_ext: u32,
@@ -337,6 +343,23 @@ pub fn batch_normalize_g1(p: &[G1], q: &mut [G1Affine]) -> bool {
     assert_eq!(p.len(), q.len());                     // same panic as the reference
     if !available() || (p.len() as u64) < (1u64 << min_log("MI355_NORMALIZE_MIN_LOGN", 12)) { return false; }
     unsafe { mi355_g1_batch_normalize_host(p.as_ptr() as *const c_void, q.as_mut_ptr() as *mut c_void, p.len() as u64) == MI355_OK }
+}
+
+/// The `G1Affine::from_bytes` loop of `ParamsKZG::read_custom(.., SerdeFormat::Processed)` over a whole basis: `words` are the 32-byte compressed forms in file
+/// order.  Ok(false) -> the caller runs the original CPU loop; Err(i) -> word i is no curve point (the CPU loop would have failed there: io::Error InvalidData).
+pub fn g1_from_bytes_many(words: &[[u8; 32]], out: &mut [G1Affine]) -> Result<bool, u64> {
+    assert_eq!(words.len(), out.len());
+    if !available() || (words.len() as u64) < (1u64 << min_log("MI355_CODEC_MIN_LOGN", 12)) { return Ok(false); }
+    let mut bad: u64 = !0;
+    let rc = unsafe { mi355_g1_decompress_host(words.as_ptr() as *const c_void, out.as_mut_ptr() as *mut c_void, words.len() as u64, &mut bad) };
+    if rc == MI355_OK { Ok(true) } else if bad != !0 { Err(bad) } else { Ok(false) }
+}
+
+/// The `to_bytes` loop of `ParamsKZG::write_custom(.., SerdeFormat::Processed)`.  Returns false -> caller runs the original CPU code.
+pub fn g1_to_bytes_many(points: &[G1Affine], out: &mut [[u8; 32]]) -> bool {
+    assert_eq!(points.len(), out.len());
+    if !available() || (points.len() as u64) < (1u64 << min_log("MI355_CODEC_MIN_LOGN", 12)) { return false; }
+    unsafe { mi355_g1_compress_host(points.as_ptr() as *const c_void, out.as_mut_ptr() as *mut c_void, points.len() as u64) == MI355_OK }
 }
 
 /// Replacement body of `best_fft` for G = Scalar = Fr (the G = curve-point instantiation keeps the CPU code).

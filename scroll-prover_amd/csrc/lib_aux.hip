@@ -1,12 +1,13 @@
 // lib_aux.hip -- libmi355zk.so, the translation unit of the kernels either side of MSM / NTT: the DFT over G1 points
 // (g1fft.hpp: g_to_lagrange, ParamsKZG::downsize), the multiplicative scans of the permutation / lookup arguments and kate_division
-// (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), and the multiplicities of the mv-lookup argument
-// (lookup.hpp).  Host logic only.
+// (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), the multiplicities of the mv-lookup argument
+// (lookup.hpp), and the compressed-point codec of G1 (g1codec.hpp).  Host logic only.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #include "g1fft.hpp"
 #include "frscan.hpp"
 #include "g2.hpp"
 #include "lookup.hpp"
+#include "g1codec.hpp"
 #include "lib_common.hpp"
 #include <thread>
 
@@ -70,6 +71,44 @@ int linrec_impl(const fe_t *src, fe_t *dst, uint64_t n, const fe_t &m, bool reve
   return MI355_OK;
 }
 
+// ---- G1 point codec (g1codec.hpp).  Grid: grid-stride over at most 16 workgroups per CU; MI355_G1_CODEC_BLOCKS overrides the workgroup count (tests run the
+// error reporting at two grid sizes; the result must not depend on it)
+static uint32_t g1codec_grid(uint64_t n) {
+  uint64_t blocks = std::min<uint64_t>(ceil_div(n, G1CODEC_THREADS), (uint64_t)g.prop.multiProcessorCount * 16);
+  if (const char *e = getenv("MI355_G1_CODEC_BLOCKS")) { const long v = atol(e); if (v > 0) blocks = std::min<uint64_t>((uint64_t)v, 65535u * 4); }
+  return (uint32_t)std::max<uint64_t>(1, blocks);
+}
+int launch_g1_decompress(const void *bytes_dev, void *affine_out_dev, uint64_t n, uint64_t base, unsigned long long *err_dev) {
+  if (!n) return MI355_OK;
+  Scope sc("g1_decompress");
+  hipLaunchKernelGGL(k_g1_decompress, dim3(g1codec_grid(n)), dim3(G1CODEC_THREADS), 0, g.stream, (const uint4 *)bytes_dev, (uint4 *)affine_out_dev, n, base, err_dev);
+  sc.close();
+  HIPCHK(hipGetLastError());
+  return MI355_OK;
+}
+static int launch_g1_compress(const void *affine_dev, void *bytes_out_dev, uint64_t n) {
+  if (!n) return MI355_OK;
+  Scope sc("g1_compress");
+  hipLaunchKernelGGL(k_g1_compress, dim3(g1codec_grid(n)), dim3(G1CODEC_THREADS), 0, g.stream, (const uint4 *)affine_dev, (uint4 *)bytes_out_dev, n);
+  sc.close();
+  HIPCHK(hipGetLastError());
+  return MI355_OK;
+}
+bool g2_decode_host(const uint8_t in[64], void *g2affine_out) {
+  g2_affine_t p; const bool ok = g2_decompress_point(in, p);
+  memcpy(g2affine_out, &p, sizeof p);
+  return ok;
+}
+static bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
+  const char *x = (const char *)a, *y = (const char *)b;
+  return x < y + b_bytes && y < x + a_bytes;
+}
+static int g1codec_bad_index(uint64_t bad, uint64_t *first_bad_out) {
+  if (first_bad_out) *first_bad_out = bad;
+  return fail(MI355_EBADARG, "g1_decompress: word " + std::to_string(bad) + " is not the compressed form of a G1 point (x >= q, x^3 + 3 a non-residue, or the identity with the sign bit set)");
+}
+constexpr uint64_t G1CODEC_HOST_CHUNK = 1ull << 22;   // points per staged chunk of the host-pointer forms (128 + 256 MiB of workspace at most)
+
 }  // namespace mi355
 
 using namespace mi355;
@@ -129,6 +168,89 @@ int mi355_g1_batch_normalize_host(const void *jac_host, void *affine_host, uint6
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(affine_host, out, n * sizeof(g1_affine_t), hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
+  return MI355_OK;
+  });
+}
+// ---- G1Affine::from_bytes / to_bytes over arrays (g1codec.hpp)
+int mi355_g1_decompress_dev(const void *bytes_dev, void *affine_out_dev, uint64_t n, uint64_t *first_bad_out) {
+  return guarded([&]() -> int {
+  int slot; CHK(common_slot({affine_out_dev, bytes_dev}, &slot, "g1_decompress")); DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (first_bad_out) *first_bad_out = ~0ull;
+  if (n == 0) return MI355_OK;
+  if (!bytes_dev || !affine_out_dev) return fail(MI355_EBADARG, "g1_decompress: null pointer");
+  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_decompress: n must be < 2^32");
+  if (ranges_overlap(bytes_dev, n * 32, affine_out_dev, n * sizeof(g1_affine_t))) return fail(MI355_EBADARG, "g1_decompress: input and output must not overlap");
+  if (((uintptr_t)bytes_dev | (uintptr_t)affine_out_dev) & 15) return fail(MI355_EBADARG, "g1_decompress: device pointers must be 16-byte aligned");
+  unsigned long long *err; CHK(ws_get("g1codec.err", 8, (void **)&err));
+  HIPCHK(hipMemsetAsync(err, 0xff, 8, g.stream));
+  CHK(launch_g1_decompress(bytes_dev, affine_out_dev, n, 0, err));
+  unsigned long long bad = ~0ull;
+  HIPCHK(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (bad != ~0ull) return g1codec_bad_index(bad, first_bad_out);
+  return finish_async();
+  });
+}
+int mi355_g1_decompress_host(const void *bytes_host, void *affine_out_host, uint64_t n, uint64_t *first_bad_out) {
+  return guarded([&]() -> int {
+  const int slot = pick_replica_slot(); DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (first_bad_out) *first_bad_out = ~0ull;
+  if (n == 0) return MI355_OK;
+  if (!bytes_host || !affine_out_host) return fail(MI355_EBADARG, "g1_decompress: null pointer");
+  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_decompress: n must be < 2^32");
+  if (ranges_overlap(bytes_host, n * 32, affine_out_host, n * sizeof(g1_affine_t))) return fail(MI355_EBADARG, "g1_decompress: input and output must not overlap");
+  const uint64_t chunk = std::min(n, G1CODEC_HOST_CHUNK);
+  char *dev; CHK(ws_get("io.g1codec", chunk * (32 + sizeof(g1_affine_t)) + 256, (void **)&dev));
+  unsigned long long *err = (unsigned long long *)dev; char *in = dev + 256, *out = in + chunk * 32;
+  HIPCHK(hipMemsetAsync(err, 0xff, 8, g.stream));
+  for (uint64_t lo = 0; lo < n; lo += chunk) {
+    const uint64_t len = std::min(chunk, n - lo);
+    HIPCHK(hipMemcpyAsync(in, (const char *)bytes_host + lo * 32, len * 32, hipMemcpyHostToDevice, g.stream));
+    CHK(launch_g1_decompress(in, out, len, lo, err));
+    HIPCHK(hipMemcpyAsync((char *)affine_out_host + lo * sizeof(g1_affine_t), out, len * sizeof(g1_affine_t), hipMemcpyDeviceToHost, g.stream));
+  }
+  unsigned long long bad = ~0ull;
+  HIPCHK(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  resolve_spans();
+  if (bad != ~0ull) return g1codec_bad_index(bad, first_bad_out);
+  return MI355_OK;
+  });
+}
+int mi355_g1_compress_dev(const void *affine_dev, void *bytes_out_dev, uint64_t n) {
+  return guarded([&]() -> int {
+  int slot; CHK(common_slot({bytes_out_dev, affine_dev}, &slot, "g1_compress")); DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (n == 0) return MI355_OK;
+  if (!affine_dev || !bytes_out_dev) return fail(MI355_EBADARG, "g1_compress: null pointer");
+  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_compress: n must be < 2^32");
+  if (ranges_overlap(affine_dev, n * sizeof(g1_affine_t), bytes_out_dev, n * 32)) return fail(MI355_EBADARG, "g1_compress: input and output must not overlap");
+  if (((uintptr_t)affine_dev | (uintptr_t)bytes_out_dev) & 15) return fail(MI355_EBADARG, "g1_compress: device pointers must be 16-byte aligned");
+  CHK(launch_g1_compress(affine_dev, bytes_out_dev, n));
+  return finish_async();
+  });
+}
+int mi355_g1_compress_host(const void *affine_host, void *bytes_out_host, uint64_t n) {
+  return guarded([&]() -> int {
+  const int slot = pick_replica_slot(); DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (n == 0) return MI355_OK;
+  if (!affine_host || !bytes_out_host) return fail(MI355_EBADARG, "g1_compress: null pointer");
+  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_compress: n must be < 2^32");
+  if (ranges_overlap(affine_host, n * sizeof(g1_affine_t), bytes_out_host, n * 32)) return fail(MI355_EBADARG, "g1_compress: input and output must not overlap");
+  const uint64_t chunk = std::min(n, G1CODEC_HOST_CHUNK);
+  char *dev; CHK(ws_get("io.g1codec", chunk * (32 + sizeof(g1_affine_t)) + 256, (void **)&dev));
+  char *out = dev + 256, *in = out + chunk * 32;
+  for (uint64_t lo = 0; lo < n; lo += chunk) {
+    const uint64_t len = std::min(chunk, n - lo);
+    HIPCHK(hipMemcpyAsync(in, (const char *)affine_host + lo * sizeof(g1_affine_t), len * sizeof(g1_affine_t), hipMemcpyHostToDevice, g.stream));
+    CHK(launch_g1_compress(in, out, len));
+    HIPCHK(hipMemcpyAsync((char *)bytes_out_host + lo * 32, out, len * 32, hipMemcpyDeviceToHost, g.stream));
+  }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  resolve_spans();
   return MI355_OK;
   });
 }

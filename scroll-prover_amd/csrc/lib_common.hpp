@@ -262,6 +262,11 @@ int ntt_tu_init_device();
 int aux_tu_init_device();
 // twiddle table out[i] = (base^step)^i on the current context's stream (kernel in ntt.hpp; used by the G1 DFT as well)
 int launch_pow_table(fe_t *out, const fe_t &base, uint64_t step, uint32_t count);
+// the G1 point codec (kernels in g1codec.hpp, launched by lib_aux.hip; the Processed params loader of lib_msm.hip uses it chunk by chunk): queue the decompression of
+// n 32-byte words into n affine points on the current context's stream; a rejected word leaves base + its index in *err_dev by atomicMin (the caller presets ~0)
+int launch_g1_decompress(const void *bytes_dev, void *affine_out_dev, uint64_t n, uint64_t base, unsigned long long *err_dev);
+// the two G2 points of a Processed params file, decoded on the host (64 bytes -> 128-byte G2Affine); false for a word that is no point of the twist
+bool g2_decode_host(const uint8_t in[64], void *g2affine_out);
 // window-cost model shared by the MSM launch code and mi355_srs_precompute
 constexpr int MSM_SCALAR_BITS = 255, MSM_MAX_C = 24;   // hard limit of the sorter (23 key bits); the automatic choices stop at g_auto_max_c
 double msm_cost(uint64_t n, int c, bool shared);

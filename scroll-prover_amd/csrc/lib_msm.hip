@@ -581,6 +581,7 @@ extern "C" {
 
 // Prover::load_params for one degree: stream a RawBytes params file into device memory (two pinned staging buffers: the read of chunk
 // i + 1 overlaps the DMA of chunk i), optionally validate every point on the device, register both bases as library-owned handles.
+// flags bit 1: the file is SerdeFormat::Processed -- the compressed words take the same route and are decompressed chunk by chunk on the device.
 static int stream_file_to_device(FILE *f, void *dev, size_t bytes, void *pinned[2], size_t chunk) {
   hipEvent_t ev[2] = {nullptr, nullptr};
   for (int i = 0; i < 2; i++) { HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); HIPCHK(hipEventRecord(ev[i], g.stream)); }
@@ -596,6 +597,44 @@ static int stream_file_to_device(FILE *f, void *dev, size_t bytes, void *pinned[
   for (int i = 0; i < 2; i++) (void)hipEventDestroy(ev[i]);
   return rc;
 }
+// SerdeFormat::Processed: the 32-byte words of one shard.  Chunk i + 1 is read and copied (a stream of its own) while chunk i is decompressed on the library
+// stream straight into the shard: two pinned host buffers, the two halves of one pooled device block.  *bad_out: the smallest rejected index of the basis, or ~0.
+static int stream_processed_to_shard(FILE *f, const Shard &sh, void *pinned[2], size_t chunk_pts, unsigned long long *bad_out) {
+  void *stage = nullptr; CHK(mi355_buf_alloc(2 * chunk_pts * 32, sh.slot, &stage));
+  hipStream_t cs = nullptr; hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
+  const int rc = [&]() -> int {
+    unsigned long long *err; CHK(ws_get("g1codec.err", 8, (void **)&err));
+    HIPCHK(hipMemsetAsync(err, 0xff, 8, g.stream));
+    HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) {
+      HIPCHK(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&used[i], hipEventDisableTiming));
+      HIPCHK(hipEventRecord(copied[i], cs)); HIPCHK(hipEventRecord(used[i], g.stream));
+    }
+    uint64_t done = 0; int which = 0;
+    while (done < sh.n) {
+      const uint64_t len = std::min<uint64_t>(chunk_pts, sh.n - done);
+      char *half = (char *)stage + (size_t)which * chunk_pts * 32;
+      HIPCHK(hipEventSynchronize(copied[which]));                       // the previous copy out of this pinned buffer has finished
+      if (fread(pinned[which], 1, len * 32, f) != len * 32) return fail(MI355_EBADARG, "srs_load_params_file: short read");
+      HIPCHK(hipStreamWaitEvent(cs, used[which], 0));                   // the kernel that read this half of the device block has finished
+      HIPCHK(hipMemcpyAsync(half, pinned[which], len * 32, hipMemcpyHostToDevice, cs));
+      HIPCHK(hipEventRecord(copied[which], cs));
+      HIPCHK(hipStreamWaitEvent(g.stream, copied[which], 0));
+      CHK(launch_g1_decompress(half, sh.dev + done, len, sh.lo + done, err));
+      HIPCHK(hipEventRecord(used[which], g.stream));
+      done += len; which ^= 1;
+    }
+    HIPCHK(hipMemcpyAsync(bad_out, err, 8, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return MI355_OK;
+  }();
+  if (cs) { (void)hipStreamSynchronize(cs); }
+  (void)hipStreamSynchronize(g.stream);
+  for (int i = 0; i < 2; i++) { if (copied[i]) (void)hipEventDestroy(copied[i]); if (used[i]) (void)hipEventDestroy(used[i]); }
+  if (cs) (void)hipStreamDestroy(cs);
+  (void)mi355_buf_free(stage);
+  return rc;
+}
 int mi355_srs_load_params_file(const char *path, uint32_t flags, uint32_t *k_out, uint64_t *g_handle_out, uint64_t *g_lagrange_handle_out, void *g2_out, void *s_g2_out) {
   return guarded([&]() -> int {
   AllGuard lk;
@@ -609,10 +648,15 @@ int mi355_srs_load_params_file(const char *path, uint32_t flags, uint32_t *k_out
     if (fread(hdr, 1, 4, f) != 4) { rc = fail(MI355_EBADARG, "srs_load_params_file: empty file"); break; }
     const uint32_t k = (uint32_t)hdr[0] | ((uint32_t)hdr[1] << 8) | ((uint32_t)hdr[2] << 16) | ((uint32_t)hdr[3] << 24);
     if (k == 0 || k > 28) { rc = fail(MI355_EBADARG, "srs_load_params_file: k out of range (not a RawBytes params file)"); break; }
-    const uint64_t n = 1ull << k, want = 4 + 2 * n * sizeof(g1_affine_t) + 256;
-    if (fseek(f, 0, SEEK_END) != 0 || (uint64_t)ftell(f) != want) { rc = fail(MI355_EBADARG, "srs_load_params_file: file length does not match 4 + 2 * 2^k * 64 + 256 (load_params rejects it too)"); break; }
+    const bool processed = (flags & 2u) != 0;   // SerdeFormat::Processed: 32-byte compressed G1 words, 64-byte compressed G2 points
+    const uint64_t n = 1ull << k, want = processed ? 4 + 2 * n * 32 + 128 : 4 + 2 * n * sizeof(g1_affine_t) + 256;
+    if (fseek(f, 0, SEEK_END) != 0 || (uint64_t)ftell(f) != want) {
+      rc = fail(MI355_EBADARG, processed ? "srs_load_params_file: file length does not match 4 + 2 * 2^k * 32 + 128 (not a Processed params file of this k)"
+                                         : "srs_load_params_file: file length does not match 4 + 2 * 2^k * 64 + 256 (load_params rejects it too)");
+      break;
+    }
     fseek(f, 4, SEEK_SET);
-    const size_t chunk = std::min<uint64_t>(64ull << 20, n * sizeof(g1_affine_t));
+    const size_t chunk = std::min<uint64_t>(64ull << 20, n * (processed ? 32 : sizeof(g1_affine_t)));
     sg.n = sl.n = n; sg.mem = std::make_shared<SrsMem>(); sl.mem = std::make_shared<SrsMem>();
     if (srs_alloc(*sg.mem, n) != MI355_OK || srs_alloc(*sl.mem, n) != MI355_OK) { (void)hipGetLastError(); rc = fail(MI355_EOOM, "srs_load_params_file: device allocation failed"); break; }
     bool okp = true;
@@ -621,9 +665,25 @@ int mi355_srs_load_params_file(const char *path, uint32_t flags, uint32_t *k_out
     for (Srs *b : {&sg, &sl}) for (auto &sh : b->mem->sh) {   // the file holds g then g_lagrange, each in point order = shard order
       if (rc != MI355_OK) break;
       if ((rc = bind_ctx(sh.slot)) != MI355_OK) break;
-      rc = stream_file_to_device(f, sh.dev, sh.n * sizeof(g1_affine_t), pinned, chunk);
+      if (!processed) { rc = stream_file_to_device(f, sh.dev, sh.n * sizeof(g1_affine_t), pinned, chunk); continue; }
+      unsigned long long bad = ~0ull;
+      rc = stream_processed_to_shard(f, sh, pinned, chunk / 32, &bad);
+      if (rc == MI355_OK && bad != ~0ull)
+        rc = fail(MI355_EBADARG, std::string("srs_load_params_file: ") + (b == &sg ? "g" : "g_lagrange") + "[" + std::to_string(bad) + "] is not the compressed form of a G1 point");
     }
     if (rc != MI355_OK) break;
+    if (processed) {   // a decompressed point is on the curve by construction: bit 0 has nothing left to check
+      uint8_t tail[128]; uint8_t g2v[128], sg2v[128];
+      if (fread(tail, 1, 128, f) != 128) { rc = fail(MI355_EBADARG, "srs_load_params_file: short read (g2 / s_g2)"); break; }
+      if (!g2_decode_host(tail, g2v)) { rc = fail(MI355_EBADARG, "srs_load_params_file: g2 is not the compressed form of a point of the twist"); break; }
+      if (!g2_decode_host(tail + 64, sg2v)) { rc = fail(MI355_EBADARG, "srs_load_params_file: s_g2 is not the compressed form of a point of the twist"); break; }
+      if (g2_out) memcpy(g2_out, g2v, 128);
+      if (s_g2_out) memcpy(s_g2_out, sg2v, 128);
+      *k_out = k;
+      *g_handle_out = srs_insert(sg);
+      *g_lagrange_handle_out = srs_insert(sl);
+      break;
+    }
     uint8_t tail[256];
     if (fread(tail, 1, 256, f) != 256) { rc = fail(MI355_EBADARG, "srs_load_params_file: short read (g2 / s_g2)"); break; }
     if (g2_out) memcpy(g2_out, tail, 128);

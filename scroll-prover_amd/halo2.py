@@ -591,9 +591,19 @@ class ParamsKZG:
     def g_lagrange_slice(self, offset: int, n: int) -> SrsSlice:
         return SrsSlice(self._gl, offset, n)
 
-    def write(self, path: str) -> None:
-        """ParamsKZG::write (SerdeFormat::RawBytes): a file prover::load_params / params_from_file accepts."""
-        write_params(path, self.k, self.read_g(), self.read_g(lagrange=True), self.g2, self.s_g2)
+    def write(self, path: str, format: str = "raw") -> None:
+        """ParamsKZG::write (SerdeFormat::RawBytes): a file prover::load_params / params_from_file accepts.  format="processed" is
+        ParamsKZG::write_custom(.., SerdeFormat::Processed): both bases are compressed on the device (mi355_srs_dev_ptr + mi355_g1_compress_dev, shard by
+        shard when the basis is spread over several devices) and only the 32-byte words cross to the host; g2 / s_g2 are compressed on the host."""
+        if format == "raw":
+            write_params(path, self.k, self.read_g(), self.read_g(lagrange=True), self.g2, self.s_g2)
+            return
+        assert format == "processed", "format must be 'raw' or 'processed'"
+        with open(path, "wb") as f:
+            f.write(int(self.k).to_bytes(4, "little"))
+            for h in (self._g, self._gl):
+                f.write(_srs_compressed(h, self.n).tobytes())
+            f.write(g2_to_bytes(self.g2)); f.write(g2_to_bytes(self.s_g2))
 
     def release(self) -> None:
         for h in (self._g, self._gl):
@@ -637,11 +647,93 @@ def g1_from_bytes(b: bytes) -> np.ndarray:
     return np.array(m(x) + m(y), dtype=np.uint64)
 
 
-# ------------------------------------------------------------------------------------------ params files (SerdeFormat::RawBytes)
-def params_file_size(k: int) -> int:
+def g1_decompress(words) -> np.ndarray:
+    """G1Affine::from_bytes over an array, on the device (mi355_g1_decompress_host / _dev): words = [n, 32] uint8 (or n * 32 bytes) on the host -> [n, 8] uint64
+    points; a device tensor of n * 32 bytes -> a device tensor of n * 64 bytes.  Raises Mi355Error (EBADARG, `.index` = the smallest rejected index) for a word
+    that is no curve point."""
+    bad = C.c_uint64()
+    if _is_device(words):
+        import torch
+        n = words.numel() * words.element_size() // 32
+        out = torch.empty(n * 64, dtype=torch.uint8, device=words.device)
+        rc = lib().mi355_g1_decompress_dev(ptr(words), ptr(out), n, C.byref(bad))
+    else:
+        w = np.ascontiguousarray(np.frombuffer(words, dtype=np.uint8) if isinstance(words, (bytes, bytearray)) else words, dtype=np.uint8).reshape(-1, 32)
+        n = w.shape[0]
+        out = np.zeros((n, 8), dtype=np.uint64)
+        rc = lib().mi355_g1_decompress_host(ptr(w), ptr(out), n, C.byref(bad))
+    if rc != _capi.OK:
+        e = Mi355Error(rc, lib().mi355_last_error().decode())
+        e.index = bad.value if bad.value != (1 << 64) - 1 else None
+        raise e
+    return out
+
+
+def g1_compress(points):
+    """G1Affine::to_bytes over an array, on the device: [n, 8] uint64 host points -> [n, 32] uint8 words; a device tensor of n * 64 bytes -> a device tensor of
+    n * 32 bytes (queued on the library stream)."""
+    if _is_device(points):
+        import torch
+        n = points.numel() * points.element_size() // 64
+        out = torch.empty(n * 32, dtype=torch.uint8, device=points.device)
+        check(lib().mi355_g1_compress_dev(ptr(points), ptr(out), n))
+        return out
+    p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+    out = np.zeros((p.shape[0], 32), dtype=np.uint8)
+    check(lib().mi355_g1_compress_host(ptr(p), ptr(out), p.shape[0]))
+    return out
+
+
+def _srs_compressed(handle: int, n: int) -> np.ndarray:
+    """the first n points of a registered basis as [n, 32] compressed words: compressed on the device that holds them; only the words are downloaded.  A basis
+    sharded over several devices exposes its primary shard through mi355_srs_dev_ptr only: the other shards go through mi355_srs_read_host + the host form."""
+    dp = C.c_void_p()
+    check(lib().mi355_srs_dev_ptr(handle, C.byref(dp)))
+    out = np.zeros((n, 32), dtype=np.uint8)
+    if _single_device():
+        chunk = min(n, 1 << 24)
+        buf = DeviceBuffer(chunk * 32)
+        try:
+            for lo in range(0, n, chunk):
+                m = min(chunk, n - lo)
+                check(lib().mi355_g1_compress_dev(C.c_void_p(dp.value + lo * 64), C.c_void_p(buf.data_ptr()), m))
+                check(lib().mi355_buf_download(ptr(out[lo:lo + m]), C.c_void_p(buf.data_ptr()), m * 32))
+        finally:
+            buf.free()
+        return out
+    chunk = min(n, 1 << 22)
+    pts = np.zeros((chunk, 8), dtype=np.uint64)
+    for lo in range(0, n, chunk):
+        m = min(chunk, n - lo)
+        check(lib().mi355_srs_read_host(handle, lo, m, ptr(pts)))
+        check(lib().mi355_g1_compress_host(ptr(pts), ptr(out[lo:lo + m]), m))
+    return out
+
+
+def _single_device() -> bool:
+    """whether a registered basis sits whole on the primary device (one bound device): slot 1 does not exist then"""
+    return lib().mi355_mem_info(1, None, None, None, None, None) != _capi.OK
+
+
+def g2_to_bytes(g2affine: bytes) -> bytes:
+    """the 64-byte compressed form of a G2Affine (128 B, Montgomery) in a SerdeFormat::Processed params file: x.c0 then x.c1 as canonical little-endian words,
+    bit 6 of byte 63 = parity of canonical y.c0, identity = 64 zero bytes [EXT-recalled halo2curves; no fixture of the reference pins this layout]."""
+    assert len(g2affine) == 128
+    if not any(g2affine):
+        return bytes(64)
+    rinv = pow(1 << 256, -1, P_MOD)
+    c = [int.from_bytes(g2affine[32 * i:32 * i + 32], "little") * rinv % P_MOD for i in range(3)]
+    out = bytearray(c[0].to_bytes(32, "little") + c[1].to_bytes(32, "little"))
+    out[63] |= (c[2] & 1) << 6
+    return bytes(out)
+
+
+# ------------------------------------------------------------------------------------------ params files (SerdeFormat::RawBytes / Processed)
+def params_file_size(k: int, format: str = "raw") -> int:
     """`u32 LE k | g[2^k] x 64 B | g_lagrange[2^k] x 64 B | g2 128 B | s_g2 128 B` [EXT-recalled ParamsKZG::write_custom, RawBytes];
-    params26 = 8 589 934 852 bytes (SURVEY 6).  `prover::load_params` rejects any other length."""
-    return 4 + 2 * (1 << k) * 64 + 256
+    params26 = 8 589 934 852 bytes (SURVEY 6).  `prover::load_params` rejects any other length.  format="processed": 32-byte G1 words and 64-byte G2 words."""
+    assert format in ("raw", "processed")
+    return 4 + 2 * (1 << k) * 64 + 256 if format == "raw" else 4 + 2 * (1 << k) * 32 + 128
 
 
 def write_params(path: str, k: int, g: np.ndarray, g_lagrange: np.ndarray, g2: bytes = bytes(128), s_g2: bytes = bytes(128)) -> None:
@@ -667,13 +759,16 @@ def read_params(path: str):
     return k, g, gl, tail[:128], tail[128:]
 
 
-def params_from_file(path: str, validate: bool = False, downsize_to: int = 0) -> "ParamsKZG":
+def params_from_file(path: str, validate: bool = False, downsize_to: int = 0, format: str = "raw") -> "ParamsKZG":
     """Prover::load_params(dir, degree) [REF bin/src/trace_prover.rs:35-36] for one degree: the file is streamed into HBM by the library
     (mi355_srs_load_params_file: pinned double-buffered reads, exact-length rule, optional on-device point validation) and both bases
-    are registered; downsize_to < k reproduces load_params on a larger file (g truncated, g_lagrange rebuilt on the device)."""
+    are registered; downsize_to < k reproduces load_params on a larger file (g truncated, g_lagrange rebuilt on the device).
+    format="processed": the file is SerdeFormat::Processed (32-byte compressed points, decompressed on the device while the next chunk is copied)."""
+    assert format in ("raw", "processed"), "format must be 'raw' or 'processed'"
     k, hg, hl = C.c_uint32(), C.c_uint64(), C.c_uint64()
     g2 = (C.c_uint8 * 128)(); s_g2 = (C.c_uint8 * 128)()
-    check(lib().mi355_srs_load_params_file(path.encode(), 1 if validate else 0, C.byref(k), C.byref(hg), C.byref(hl), g2, s_g2))
+    flags = (1 if validate else 0) | (2 if format == "processed" else 0)
+    check(lib().mi355_srs_load_params_file(path.encode(), flags, C.byref(k), C.byref(hg), C.byref(hl), g2, s_g2))
     p = ParamsKZG(k.value, hg.value, hl.value)
     p.g2, p.s_g2 = bytes(g2), bytes(s_g2)
     if downsize_to and downsize_to < p.k:
