@@ -34,7 +34,7 @@ int g1fft_impl(const void *in, int in_jac, void *out, int out_jac, uint32_t log_
   hipStream_t s = g.stream;
   fe_t w; memcpy(&w, omega, 32);
   Scope total("g1_fft");
-  CHK(launch_pow_table(tw, w, 1, half));   // kernel of ntt.hpp, launched by lib_ntt.hip on this context's stream
+  CHK(launch_pow_table(tw, w, 1, half));   // kernel of ntt29.hpp, launched by lib_ntt.hip on this context's stream
   if (in_jac) hipLaunchKernelGGL(k_g1fft_load<1>, dim3(ceil_div(n, 256)), dim3(256), 0, s, in, work, log_n);
   else hipLaunchKernelGGL(k_g1fft_load<0>, dim3(ceil_div(n, 256)), dim3(256), 0, s, in, work, log_n);
   for (uint32_t st = 0; st < log_n; st++) hipLaunchKernelGGL(k_g1fft_stage, dim3(ceil_div(n / 2, 256)), dim3(256), 0, s, work, tw, log_n, st);

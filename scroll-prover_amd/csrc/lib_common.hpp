@@ -260,7 +260,7 @@ int pick_replica_slot();
 int msm_tu_init_device();
 int ntt_tu_init_device();
 int aux_tu_init_device();
-// twiddle table out[i] = (base^step)^i on the current context's stream (kernel in ntt.hpp; used by the G1 DFT as well)
+// twiddle table out[i] = (base^step)^i on the current context's stream (kernel in ntt29.hpp; used by the G1 DFT as well)
 int launch_pow_table(fe_t *out, const fe_t &base, uint64_t step, uint32_t count);
 // the G1 point codec (kernels in g1codec.hpp, launched by lib_aux.hip; the Processed params loader of lib_msm.hip uses it chunk by chunk): queue the decompression of
 // n 32-byte words into n affine points on the current context's stream; a rejected word leaves base + its index in *err_dev by atomicMin (the caller presets ~0)

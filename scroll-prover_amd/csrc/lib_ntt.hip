@@ -1,10 +1,10 @@
-// lib_ntt.hip -- libmi355zk.so, the Fr translation unit: launch orchestration of ntt29.hpp (plan cache, <= 3 global passes), the
-// EvaluationDomain wrappers (ifft, coset extension and its inverse), distribute_powers, the element-wise vector operations, the gate-shaped
-// fused evaluation (mi355_fr_gate_eval_dev), eval_polynomial, and the batched / replicated entry points that spread independent transforms
-// over the bound devices.  Host logic only; all arithmetic runs in the kernels.
+// lib_ntt.hip -- libmi355zk.so, the Fr translation unit: launch orchestration of ntt29.hpp (plan cache and its twiddle tables, one driver for the <= 3
+// global passes), the EvaluationDomain wrappers (ifft, coset extension and its inverse), and the kernels of frpoly.hpp: distribute_powers, the element-wise
+// vector operations, the gate-shaped fused evaluation (mi355_fr_gate_eval_dev), eval_polynomial; the batched / replicated entry points spread independent
+// transforms over the bound devices.  Host logic only; all arithmetic runs in the kernels.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
-#include "ntt.hpp"
 #include "ntt29.hpp"
+#include "frpoly.hpp"
 #include "lib_common.hpp"
 
 namespace mi355 {
@@ -15,30 +15,31 @@ int ntt_tu_init_device() {
   return MI355_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ NTT
+// ------------------------------------------------------------------------------------------------ plans and their twiddle tables
 constexpr uint32_t NTT_DIRECT_TW_MAX_LOG = 20;   // 2^20 x 36 B = 38 MB per table at most
 std::string plan_key(uint32_t log_n, const void *omega) { std::string k((const char *)omega, 32); k.push_back((char)log_n); return k; }
 
-int pow_table29(NttPlan &p, Tw29 *out, const fe_t &base, uint64_t step, uint32_t count) {
-  uint4 *lo, *hi; uint32_t *top;
-  CHK(dev_malloc((void **)&lo, (size_t)count * 16, "ntt twiddles")); p.owned.push_back(lo);
-  CHK(dev_malloc((void **)&hi, (size_t)count * 16, "ntt twiddles")); p.owned.push_back(hi);
-  CHK(dev_malloc((void **)&top, (size_t)count * 4, "ntt twiddles")); p.owned.push_back(top);
-  hipLaunchKernelGGL(k_pow_table29, dim3(ceil_div(count, 256)), dim3(256), 0, g.stream, lo, hi, top, base, step, count);
-  HIPCHK(hipGetLastError());
-  out->lo = lo; out->hi = hi; out->top = top;
+// The one owner of a plan's tables: the three device arrays (SoA) of a `count`-entry table, registered in p.owned only when all three exist.
+// TableMem::pooled: dev_malloc -- the device's pooled blocks are given back and the allocation retried before MI355_EOOM is reported (the small power tables:
+// failure is an error); TableMem::spare: plain hipMalloc and a quiet MI355_EOOM (the big optional tables: the caller then takes the table-free form of the pass).
+enum class TableMem { pooled, spare };
+static int alloc_plan_table(NttPlan &p, uint64_t count, TableMem mem, Soa29 *out) {
+  void *a[3] = {nullptr, nullptr, nullptr}; const size_t bytes[3] = {count * 16, count * 16, count * 4};
+  int rc = MI355_OK;
+  for (int i = 0; i < 3 && rc == MI355_OK; i++) {
+    if (mem == TableMem::pooled) rc = dev_malloc(&a[i], bytes[i], "ntt twiddles");
+    else if (hipMalloc(&a[i], bytes[i]) != hipSuccess) { (void)hipGetLastError(); a[i] = nullptr; rc = MI355_EOOM; }
+  }
+  if (rc != MI355_OK) { for (void *q : a) if (q) (void)hipFree(q); return rc; }
+  p.owned.insert(p.owned.end(), a, a + 3);
+  *out = Soa29{(uint4 *)a[0], (uint4 *)a[1], (uint32_t *)a[2]};
   return MI355_OK;
 }
-
-int launch_pow_table(fe_t *out, const fe_t &base, uint64_t step, uint32_t count) {
-  hipLaunchKernelGGL(k_pow_table, dim3(ceil_div(count, 256)), dim3(256), 0, g.stream, out, base, step, count);
-  HIPCHK(hipGetLastError());
-  return MI355_OK;
-}
-
-static void free_plan_tables(NttPlan &p) {
-  for (void *q : p.owned) (void)hipFree(q);
-  p.owned.clear();
+// gives back the tables registered from index `from` of p.owned on (0: all of them), once the stream that may still be building them has drained
+static void free_plan_tables(NttPlan &p, size_t from = 0) {
+  (void)hipStreamSynchronize(g.stream);
+  for (size_t i = from; i < p.owned.size(); i++) (void)hipFree(p.owned[i]);
+  p.owned.resize(from);
 }
 // big twiddle tables (256 MB and more) are only built into HBM that is really spare: the table plus max(16 GiB, 1/12 of the device) must be free -- a multi-layer prover process
 // that peaks at 274 GiB of 288 builds none of them and takes the table-free form of the same pass (the lo x hi product, or the separate coset shift)
@@ -48,14 +49,21 @@ static bool hbm_spare_for_table(uint64_t entries) {
   if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return false; }
   return fr >= entries * 36 + std::max<size_t>((size_t)16 << 30, tot / 12);
 }
-// three device arrays of one 29-bit table (SoA), all or nothing
-static bool alloc_tw29(uint64_t cnt, uint4 **lo, uint4 **hi, uint32_t **top) {
-  *lo = *hi = nullptr; *top = nullptr;
-  if (hipMalloc((void **)lo, cnt * 16) == hipSuccess && hipMalloc((void **)hi, cnt * 16) == hipSuccess && hipMalloc((void **)top, cnt * 4) == hipSuccess) return true;
-  (void)hipGetLastError();
-  if (*lo) (void)hipFree(*lo); if (*hi) (void)hipFree(*hi); if (*top) (void)hipFree(*top);
-  return false;
+
+int pow_table29(NttPlan &p, Tw29 *out, const fe_t &base, uint64_t step, uint32_t count) {
+  Soa29 t; CHK(alloc_plan_table(p, count, TableMem::pooled, &t));
+  hipLaunchKernelGGL(k_pow_table29, dim3(ceil_div(count, 256)), dim3(256), 0, g.stream, t.lo, t.hi, t.top, base, step, count);
+  HIPCHK(hipGetLastError());
+  *out = t;
+  return MI355_OK;
 }
+
+int launch_pow_table(fe_t *out, const fe_t &base, uint64_t step, uint32_t count) {
+  hipLaunchKernelGGL(k_pow_table, dim3(ceil_div(count, 256)), dim3(256), 0, g.stream, out, base, step, count);
+  HIPCHK(hipGetLastError());
+  return MI355_OK;
+}
+
 static int build_plan(NttPlan &p, uint32_t log_n, const void *omega) {
   if (log_n <= 8) { p.levels = 1; p.log_m[0] = log_n; }
   else if (log_n <= g.ntt_two_level_max_log) { p.levels = 2; p.log_m[0] = (log_n + 1) / 2; p.log_m[1] = log_n / 2; }   // two passes up to 2^18 (2^20 as an A/B knob: 1024-point columns, two adjacent columns per tile)
@@ -70,21 +78,15 @@ static int build_plan(NttPlan &p, uint32_t log_n, const void *omega) {
       // inter-level twiddles w_S^e, e < 2^log_s: ONE table when it is small enough to live in L2 (no lo x hi product per element),
       // otherwise the usual two half-size tables
       p.split[l] = log_s <= NTT_DIRECT_TW_MAX_LOG ? log_s : (log_s + 1) / 2;
-      bool direct = false;
-      if (log_s >= g.ntt_direct2_min_log && log_s <= g.ntt_direct2_max_log) {
-        // big level: every twiddle w_S^(column k) once, in the order the pass reads them (36 B x 2^log_s: 2.4 GB at 2^26, read coalesced
-        // next to the data by a pass that is ALU-bound); saves the lo x hi product per element.  HBM may be full of window tables: when the
-        // allocation fails the level falls back to the lo x hi pair, which is functionally equivalent.
-        const uint64_t cnt = 1ull << log_s; uint4 *lo, *hi; uint32_t *top;
-        if (hbm_spare_for_table(cnt) && alloc_tw29(cnt, &lo, &hi, &top)) {
-          p.owned.push_back(lo); p.owned.push_back(hi); p.owned.push_back(top);
-          hipLaunchKernelGGL(k_pow_table29_2d, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, g.stream, lo, hi, top, Fr::pow_u64(w, N >> log_s), log_s - lm, cnt);
-          HIPCHK(hipGetLastError());
-          p.tw29_s_lo[l].lo = lo; p.tw29_s_lo[l].hi = hi; p.tw29_s_lo[l].top = top; p.tw29_s_hi[l] = p.tw29_s_lo[l]; p.direct2[l] = 1;
-          direct = true;
-        }
-      }
-      if (!direct) {
+      // big level: every twiddle w_S^(column k) once, in the order the pass reads them (36 B x 2^log_s: 2.4 GB at 2^26, read coalesced
+      // next to the data by a pass that is ALU-bound); saves the lo x hi product per element.  HBM may be full of window tables: when the
+      // allocation fails the level falls back to the lo x hi pair, which is functionally equivalent.
+      const uint64_t cnt = 1ull << log_s; Soa29 t;
+      if (log_s >= g.ntt_direct2_min_log && log_s <= g.ntt_direct2_max_log && hbm_spare_for_table(cnt) && alloc_plan_table(p, cnt, TableMem::spare, &t) == MI355_OK) {
+        hipLaunchKernelGGL(k_pow_table29_2d, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, g.stream, t.lo, t.hi, t.top, Fr::pow_u64(w, N >> log_s), log_s - lm, cnt);
+        HIPCHK(hipGetLastError());
+        p.tw29_s_lo[l] = p.tw29_s_hi[l] = t; p.direct2[l] = 1;
+      } else {
         CHK(pow_table29(p, &p.tw29_s_lo[l], w, N >> log_s, 1u << p.split[l]));
         CHK(pow_table29(p, &p.tw29_s_hi[l], w, (N >> log_s) << p.split[l], 1u << (log_s - p.split[l])));
       }
@@ -99,22 +101,15 @@ int get_plan(uint32_t log_n, const void *omega, NttPlan **out) {
   if (it != g.ntt_plans.end()) { *out = &it->second; return MI355_OK; }
   NttPlan p; p.log_n = log_n;
   const int rc = build_plan(p, log_n, omega);
-  if (rc != MI355_OK) { (void)hipStreamSynchronize(g.stream); free_plan_tables(p); return rc; }   // nothing of a half-built plan is kept
+  if (rc != MI355_OK) { free_plan_tables(p); return rc; }   // nothing of a half-built plan is kept
   g.ntt_plans[key] = p; *out = &g.ntt_plans[key];
   return MI355_OK;
 }
-
-// radix-4 register rounds (two DIF stages per LDS round trip): one work item per 4 elements.  (The radix-2 and radix-8 instantiations and the raw-scratch modes were A/B paths
-// of rounds 3-4 -- results in HISTORY.md section 5 -- and left the library in round 6.)
-#define NTT29_LAUNCH(KERN, BLOCKS, TILE, LDS, ...) hipLaunchKernelGGL(KERN<2>, dim3(BLOCKS), dim3(std::max(64u, std::min(512u, (TILE) / 4))), LDS, s, __VA_ARGS__)
-
-uint32_t cols_for(uint32_t log_m) { uint32_t lc = 3; while (lc > 0 && log_m + lc > g.ntt_tile_log) lc--; return lc; }
 
 // an inverse transform's divisor (the three post-scaling constants equal) is folded into the inter-level twiddles of the last strided
 // pass: one table of 2^log_s entries per (plan, divisor), and the closing pass ends with reduce_small instead of a multiplication.
 // On success *fold_tw names the scaled table and *post3_dev is cleared; otherwise both stay as they were (the divisor remains a multiplication).
 static int fold_divisor(NttPlan *p, uint32_t log_n, const fe_t *pre3_host, const fe_t *post3_host, const Tw29 **fold_tw, fe_t **post3_dev) {
-  hipStream_t s = g.stream;
   if (post3_host && !pre3_host && g.ntt_fold_scale && p->levels >= 2 && memcmp(&post3_host[0], &post3_host[1], 32) == 0 && memcmp(&post3_host[0], &post3_host[2], 32) == 0) {
     const uint32_t l = p->levels - 2;
     uint32_t log_sl = log_n; for (uint32_t q = 0; q < l; q++) log_sl -= p->log_m[q];
@@ -122,13 +117,11 @@ static int fold_divisor(NttPlan *p, uint32_t log_n, const fe_t *pre3_host, const
       const std::string key((const char *)&post3_host[0], 32);
       auto it = p->scaled.find(key);
       if (it == p->scaled.end()) {
-        const uint32_t cnt = 1u << log_sl; uint4 *lo, *hi; uint32_t *top;
-        if (alloc_tw29(cnt, &lo, &hi, &top)) {
-          p->owned.push_back(lo); p->owned.push_back(hi); p->owned.push_back(top);
-          hipLaunchKernelGGL(k_scale_table29, dim3(ceil_div(cnt, 256)), dim3(256), 0, s, p->tw29_s_lo[l].lo, p->tw29_s_lo[l].hi, p->tw29_s_lo[l].top, lo, hi, top, post3_host[0], cnt);
+        const uint32_t cnt = 1u << log_sl; Soa29 t;
+        if (alloc_plan_table(*p, cnt, TableMem::spare, &t) == MI355_OK) {
+          hipLaunchKernelGGL(k_scale_table29, dim3(ceil_div(cnt, 256)), dim3(256), 0, g.stream, p->tw29_s_lo[l].lo, p->tw29_s_lo[l].hi, p->tw29_s_lo[l].top, t.lo, t.hi, t.top, post3_host[0], cnt);
           HIPCHK(hipGetLastError());
-          Tw29 t; t.lo = lo; t.hi = hi; t.top = top;
-          it = p->scaled.emplace(key, t).first;
+          it = p->scaled.emplace(key, Tw29(t)).first;
         }
       }
       if (it != p->scaled.end()) { *fold_tw = &it->second; *post3_dev = nullptr; }   // allocation failed: the divisor stays a multiplication in the closing pass
@@ -150,19 +143,76 @@ static const NttPlan::CosetTw *coset_fold_tables(NttPlan *p, uint32_t log_n, con
   if (p->coset.size() >= 16) return nullptr;
   const uint32_t lm = p->log_m[0], log_t = log_n - lm; const uint64_t cnt = 1ull << log_n;
   fe_t f, w; memcpy(&f, factor, 32); memcpy(&w, omega, 32);
-  NttPlan::CosetTw T;
-  uint4 *lo, *hi; uint32_t *top;
   // big tables (0.6 GB per factor at 2^24, 2.4 GB at 2^26) are built only into HBM that is really spare (hbm_spare_for_table): the first coset transform of a proof runs when most
   // of the proof's working set is already allocated, so what is free here is close to what stays free; below the margin the shift stays the separate pass
-  if (!hbm_spare_for_table(cnt)) return nullptr;
-  if (!alloc_tw29(cnt, &lo, &hi, &top)) return nullptr;
-  p->owned.push_back(lo); p->owned.push_back(hi); p->owned.push_back(top);
-  hipLaunchKernelGGL(k_pow_table29_2d, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, g.stream, lo, hi, top, w, log_t, cnt, f, 1);   // level 0: w_S = omega (S = N)
-  if (hipGetLastError() != hipSuccess) return nullptr;
-  T.s2d.lo = lo; T.s2d.hi = hi; T.s2d.top = top;
-  if (pow_table29(*p, &T.in, Fr::pow_u64(f, 1ull << log_t), 1, 1u << lm) != MI355_OK) return nullptr;
+  const size_t mark = p->owned.size();
+  NttPlan::CosetTw T; Soa29 s2d;
+  if (!hbm_spare_for_table(cnt) || alloc_plan_table(*p, cnt, TableMem::spare, &s2d) != MI355_OK) return nullptr;
+  hipLaunchKernelGGL(k_pow_table29_2d, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, g.stream, s2d.lo, s2d.hi, s2d.top, w, log_t, cnt, f, 1);   // level 0: w_S = omega (S = N)
+  // a failed build keeps nothing: tables left in p->owned without an entry in p->coset would be allocated again by every later call with this factor
+  if (hipGetLastError() != hipSuccess || pow_table29(*p, &T.in, Fr::pow_u64(f, 1ull << log_t), 1, 1u << lm) != MI355_OK) { free_plan_tables(*p, mark); return nullptr; }
+  T.s2d = s2d;
   return &p->coset.emplace(key, T).first->second;
 }
+
+// ------------------------------------------------------------------------------------------------ the passes of one plan
+uint32_t cols_for(uint32_t log_m) { uint32_t lc = 3; while (lc > 0 && log_m + lc > g.ntt_tile_log) lc--; return lc; }
+
+// descriptor of strided level l (its sub-problems have 2^log_s elements).  fold_tw: the divisor-scaled table of fold_divisor replaces the inter-level twiddles of the last
+// strided level; coset: the tables of coset_fold_tables replace those of the first and add the factor applied on load
+static Ntt29Level strided_level(const NttPlan &p, uint32_t l, uint32_t log_s, const Tw29 *fold_tw, const NttPlan::CosetTw *coset) {
+  Ntt29Level L; L.log_m = p.log_m[l]; L.log_t = log_s - L.log_m; L.split = p.split[l]; L.tw_m = p.tw29_m[l]; L.tw_s_lo = p.tw29_s_lo[l]; L.tw_s_hi = p.tw29_s_hi[l];
+  L.direct = p.direct2[l] ? 2u : (p.split[l] == log_s) ? 1u : 0u;
+  if (fold_tw && l + 2 == p.levels) L.tw_s_lo = *fold_tw;
+  if (coset && l == 0) { L.tw_in = coset->in; L.has_in = 1; L.tw_s_lo = coset->s2d; L.tw_s_hi = coset->s2d; L.direct = 2; }
+  return L;
+}
+// launch geometry of a pass: 2^lc adjacent columns (strided pass) or segments (closing pass) per tile, as many as fit MI355_NTT_TILE_LOG.  The kernels run radix-4 register
+// rounds (two DIF stages per LDS round trip), one work item per 4 elements.  (The radix-2 and radix-8 instantiations and the raw-scratch modes were A/B paths of rounds 3-4 --
+// results in HISTORY.md section 5 -- and left the library in round 6.)
+struct PassGeom { uint32_t lc, blocks, threads; size_t lds; };
+static uint32_t pass_threads(uint32_t log_tile) { return std::max(64u, std::min(512u, (1u << log_tile) / 4)); }
+static PassGeom strided_geom(const Ntt29Level &L, uint32_t log_n, uint32_t log_s) {
+  PassGeom G; G.lc = std::min(cols_for(L.log_m), L.log_t);
+  G.blocks = (uint32_t)(((1ull << log_n) >> log_s) << (L.log_t - G.lc)); G.threads = pass_threads(L.log_m + G.lc); G.lds = (size_t)36 << (L.log_m + G.lc);
+  return G;
+}
+static PassGeom final_geom(uint32_t log_m, uint32_t log_a, uint32_t log_b) {
+  PassGeom G; G.lc = std::min(cols_for(log_m), log_a);
+  G.blocks = (uint32_t)(((uint64_t)1 << log_b) << (log_a - G.lc)); G.threads = pass_threads(log_m + G.lc); G.lds = (size_t)36 * (((size_t)1 << log_m) + 1) * ((size_t)1 << G.lc);   // segments are padded by one element
+  return G;
+}
+// What one enqueue_passes call transforms: one vector, or `count` full-length vectors named by device pointer tables (blockIdx.y = vector)
+struct PassVectors {
+  const fe_t *src; uint64_t src_len; const fe_t *pre3; fe_t *scratch, *dst;
+  const fe_t *const *srcs; fe_t *const *scratches, *const *dsts; uint32_t count;
+  // src (zero-padded from src_len elements on, pre3-scaled; may equal dst) -> dst through scratch
+  static PassVectors single(const fe_t *src, uint64_t src_len, const fe_t *pre3, fe_t *scratch, fe_t *dst) { return PassVectors{src, src_len, pre3, scratch, dst, nullptr, nullptr, nullptr, 1}; }
+  // srcs[i] -> dsts[i] through scratches[i]; srcs[i] is only read by the first pass, so it may equal dsts[i]
+  static PassVectors batch(const fe_t *const *srcs, fe_t *const *scratches, fe_t *const *dsts, uint32_t count) { return PassVectors{nullptr, 0, nullptr, nullptr, nullptr, srcs, scratches, dsts, count}; }
+};
+// enqueues the passes of plan p on the stream: levels - 1 strided passes (source -> scratch, then scratch in place) and the closing pass (-> destination, times post3)
+static int enqueue_passes(const NttPlan &p, const PassVectors &V, const fe_t *post3, const Tw29 *fold_tw, const NttPlan::CosetTw *coset) {
+  const uint32_t last = p.levels - 1, vectors = V.srcs ? V.count : 1u;
+  const uint64_t N = 1ull << p.log_n;
+  const fe_t *cur = V.src; const fe_t *const *curs = V.srcs; uint64_t cur_len = V.srcs ? N : V.src_len; const fe_t *cur_pre = V.pre3;
+  uint32_t log_s = p.log_n;
+  for (uint32_t l = 0; l < last; l++) {
+    const Ntt29Level L = strided_level(p, l, log_s, fold_tw, coset);
+    const PassGeom G = strided_geom(L, p.log_n, log_s);
+    Scope sc("ntt_pass");
+    hipLaunchKernelGGL(k_ntt29_strided<2>, dim3(G.blocks, vectors), dim3(G.threads), G.lds, g.stream, cur, V.scratch, L, G.lc, cur_len, cur_pre, NttBatch{curs, V.scratches});
+    cur = V.scratch; curs = V.scratches; cur_len = N; cur_pre = nullptr; log_s -= L.log_m;
+  }
+  const uint32_t log_a = last ? p.log_m[0] : 0, log_b = p.levels == 3 ? p.log_m[1] : 0;   // a single-pass plan is one workgroup of the closing pass
+  const PassGeom G = final_geom(p.log_m[last], log_a, log_b);
+  Scope sc("ntt_pass");
+  hipLaunchKernelGGL(k_ntt29_final<2>, dim3(G.blocks, vectors), dim3(G.threads), G.lds, g.stream, cur, V.dst, p.log_m[last], log_a, log_b, G.lc, p.tw29_m[last], cur_len, cur_pre, post3, NttBatch{curs, V.dsts});
+  HIPCHK(hipGetLastError());
+  return MI355_OK;
+}
+
+static void post3_from_divisor(fe_t post[3], const void *divisor) { for (int i = 0; i < 3; i++) memcpy(&post[i], divisor, 32); }
 
 // dst[2^log_n] = NTT_omega( pre3-scaled, zero-padded src[src_len] ), then optional post3 scaling.  src may equal dst.
 // coset: the tables of coset_fold_tables -- the transform is then of src[i] f^i (first pass; multi-pass plans only)
@@ -177,48 +227,25 @@ int ntt_dev_impl(const fe_t *src, uint64_t src_len, fe_t *dst, uint32_t log_n, c
     if (post3_host) { HIPCHK(hipMemcpyAsync(c + 3, post3_host, 3 * sizeof(fe_t), hipMemcpyHostToDevice, s)); post3 = c + 3; }
     HIPCHK(hipStreamSynchronize(s));  // the host copies may be stack temporaries of the caller
   }
-  if (log_n == 0) {
-    if (src != dst || pre3 || post3 || src_len < 1) {
-      // size-1 transform = identity (apart from scalings); handle through the generic final kernel
-    }
-  }
   NttPlan *p; CHK(get_plan(log_n, omega, &p));
   const Tw29 *fold_tw = nullptr;
   CHK(fold_divisor(p, log_n, pre3_host, post3_host, &fold_tw, &post3));
   if (coset && (p->levels < 2 || fold_tw || pre3)) return fail(MI355_EBADARG, "ntt: a folded coset shift needs a multi-pass plan and no other scaling");
   CallTrace tr("ntt_fr", N, 64.0);
   Scope total("ntt_total");
-  if (p->levels == 1) {
-    const uint32_t lm = p->log_m[0], tile = 1u << lm;
-    Scope sc("ntt_pass");
-    NTT29_LAUNCH(k_ntt29_final, 1u, tile, (size_t)36 * (tile + 1), src, dst, lm, 0u, 0u, 0u, p->tw29_m[0], src_len, pre3, post3);
-  } else {
-    fe_t *scratch; CHK(ws_get("ntt.scratch", N * sizeof(fe_t), (void **)&scratch));
-    uint32_t log_s = log_n;
-    const fe_t *cur = src; uint64_t cur_len = src_len; const fe_t *cur_pre = pre3;
-    for (uint32_t l = 0; l + 1 < p->levels; l++) {
-      Ntt29Level L9; L9.log_m = p->log_m[l]; L9.log_t = log_s - L9.log_m; L9.split = p->split[l]; L9.tw_m = p->tw29_m[l]; L9.tw_s_lo = p->tw29_s_lo[l]; L9.tw_s_hi = p->tw29_s_hi[l];
-      L9.direct = p->direct2[l] ? 2u : (p->split[l] == log_s) ? 1u : 0u;
-      if (fold_tw && l + 2 == p->levels) L9.tw_s_lo = *fold_tw;
-      if (coset && l == 0) { L9.tw_in = coset->in; L9.has_in = 1; L9.tw_s_lo = coset->s2d; L9.tw_s_hi = coset->s2d; L9.direct = 2; }
-      const uint32_t lc = std::min(cols_for(L9.log_m), L9.log_t), tile = 1u << (L9.log_m + lc);
-      const uint64_t blocks = (N >> log_s) << (L9.log_t - lc);
-      Scope sc("ntt_pass");
-      NTT29_LAUNCH(k_ntt29_strided, (uint32_t)blocks, tile, (size_t)36 * tile, cur, scratch, L9, lc, cur_len, cur_pre);
-      cur = scratch; cur_len = N; cur_pre = nullptr; log_s -= L9.log_m;
-    }
-    const uint32_t lm = p->log_m[p->levels - 1], log_a = p->log_m[0], log_b = p->levels == 3 ? p->log_m[1] : 0;
-    const uint32_t lc = std::min(cols_for(lm), log_a), tile = 1u << (lm + lc);
-    const uint64_t blocks = ((uint64_t)1 << log_b) << (log_a - lc);
-    Scope sc("ntt_pass");
-    NTT29_LAUNCH(k_ntt29_final, (uint32_t)blocks, tile, (size_t)36 * (((size_t)1 << lm) + 1) * ((size_t)1 << lc), cur, dst, lm, log_a, log_b, lc, p->tw29_m[p->levels - 1], N, (const fe_t *)nullptr, post3);
-  }
-  HIPCHK(hipGetLastError());
+  fe_t *scratch = nullptr;
+  if (p->levels > 1) CHK(ws_get("ntt.scratch", N * sizeof(fe_t), (void **)&scratch));
+  CHK(enqueue_passes(*p, PassVectors::single(src, src_len, pre3, scratch, dst), post3, fold_tw, coset));
   total.close();
   tr.done();
   return MI355_OK;
 }
-
+// in place; divisor == NULL: best_fft, otherwise EvaluationDomain::ifft (every element times the divisor)
+int transform_in_place(fe_t *data, uint32_t log_n, const void *omega, const void *divisor) {
+  if (!divisor) return ntt_dev_impl(data, 1ull << log_n, data, log_n, omega, nullptr, nullptr);
+  fe_t post[3]; post3_from_divisor(post, divisor);
+  return ntt_dev_impl(data, 1ull << log_n, data, log_n, omega, nullptr, post);
+}
 
 // `data.size()` in-place transforms of 2^log_n elements (optionally times a divisor) as batched launches: blockIdx.y = vector.  Used by the batch entry
 // points for small transforms; falls back to the loop of single transforms where the batched kernels do not apply.  Same results.
@@ -226,10 +253,9 @@ int ntt_dev_impl(const fe_t *src, uint64_t src_len, fe_t *dst, uint32_t log_n, c
 int ntt_batch_inplace(const std::vector<fe_t *> &data, uint32_t log_n, const void *omega, const void *divisor, const std::vector<const fe_t *> *srcs = nullptr, const NttPlan::CosetTw *coset = nullptr) {
   const size_t cnt = data.size();
   auto single_loop = [&]() -> int {
-    if (coset) { for (size_t i = 0; i < cnt; i++) CHK(ntt_dev_impl((*srcs)[i], 1ull << log_n, data[i], log_n, omega, nullptr, nullptr, coset)); return MI355_OK; }
-    for (fe_t *d : data) {
-      if (!divisor) CHK(ntt_dev_impl(d, 1ull << log_n, d, log_n, omega, nullptr, nullptr));
-      else { fe_t post[3]; for (int i = 0; i < 3; i++) memcpy(&post[i], divisor, 32); CHK(ntt_dev_impl(d, 1ull << log_n, d, log_n, omega, nullptr, post)); }
+    for (size_t i = 0; i < cnt; i++) {
+      if (coset) CHK(ntt_dev_impl((*srcs)[i], 1ull << log_n, data[i], log_n, omega, nullptr, nullptr, coset));
+      else CHK(transform_in_place(data[i], log_n, omega, divisor));
     }
     return MI355_OK;
   };
@@ -240,7 +266,7 @@ int ntt_batch_inplace(const std::vector<fe_t *> &data, uint32_t log_n, const voi
   hipStream_t s = g.stream;
   fe_t post_host[3]; fe_t *post3 = nullptr; const Tw29 *fold_tw = nullptr;
   if (divisor) {
-    for (int i = 0; i < 3; i++) memcpy(&post_host[i], divisor, 32);
+    post3_from_divisor(post_host, divisor);
     fe_t *c; CHK(ws_get("ntt.consts", 6 * sizeof(fe_t), (void **)&c));
     HIPCHK(hipMemcpyAsync(c + 3, post_host, 3 * sizeof(fe_t), hipMemcpyHostToDevice, s)); HIPCHK(hipStreamSynchronize(s));
     post3 = c + 3;
@@ -259,28 +285,8 @@ int ntt_batch_inplace(const std::vector<fe_t *> &data, uint32_t log_n, const voi
   CallTrace tr("ntt_fr_batch", N * cnt, 64.0);
   for (size_t base = 0; base < cnt; base += chunk) {
     const uint32_t c = (uint32_t)std::min(chunk, cnt - base);
-    const fe_t *const *d_data = dtab + base; fe_t *const *d_scr = (fe_t *const *)(dtab + cnt + base);
-    uint32_t log_s = log_n;
-    for (uint32_t l = 0; l + 1 < p->levels; l++) {
-      Ntt29Level L9; L9.log_m = p->log_m[l]; L9.log_t = log_s - L9.log_m; L9.split = p->split[l]; L9.tw_m = p->tw29_m[l]; L9.tw_s_lo = p->tw29_s_lo[l]; L9.tw_s_hi = p->tw29_s_hi[l];
-      L9.direct = p->direct2[l] ? 2u : (p->split[l] == log_s) ? 1u : 0u;
-      if (fold_tw && l + 2 == p->levels) L9.tw_s_lo = *fold_tw;
-      if (coset && l == 0) { L9.tw_in = coset->in; L9.has_in = 1; L9.tw_s_lo = coset->s2d; L9.tw_s_hi = coset->s2d; L9.direct = 2; }
-      const uint32_t lc = std::min(cols_for(L9.log_m), L9.log_t), tile = 1u << (L9.log_m + lc);
-      const uint64_t blocks = (N >> log_s) << (L9.log_t - lc);
-      Scope sc("ntt_pass");
-      const NttBatch B{l == 0 ? (const fe_t *const *)(dtab + 2 * cnt + base) : (const fe_t *const *)d_scr, d_scr};
-      hipLaunchKernelGGL((k_ntt29_strided<2, 0>), dim3((uint32_t)blocks, c), dim3(std::max(64u, std::min(512u, tile / 4))), (size_t)36 * tile, s, (const fe_t *)nullptr, (fe_t *)nullptr, L9, lc, N, (const fe_t *)nullptr, Raw29{nullptr, nullptr, nullptr}, B);
-      log_s -= L9.log_m;
-    }
-    const uint32_t lm = p->log_m[p->levels - 1], log_a = p->log_m[0], log_b = p->levels == 3 ? p->log_m[1] : 0;
-    const uint32_t lc = std::min(cols_for(lm), log_a), tile = 1u << (lm + lc);
-    const uint64_t blocks = ((uint64_t)1 << log_b) << (log_a - lc);
-    Scope sc("ntt_pass");
-    const NttBatch B{(const fe_t *const *)d_scr, (fe_t *const *)d_data};
-    hipLaunchKernelGGL((k_ntt29_final<2, 0>), dim3((uint32_t)blocks, c), dim3(std::max(64u, std::min(512u, tile / 4))), (size_t)36 * (((size_t)1 << lm) + 1) * ((size_t)1 << lc), s, (const fe_t *)nullptr, (fe_t *)nullptr, lm, log_a, log_b, lc,
-                       p->tw29_m[p->levels - 1], N, (const fe_t *)nullptr, (const fe_t *)post3, Raw29{nullptr, nullptr, nullptr}, B);
-    HIPCHK(hipGetLastError());
+    const fe_t *const *d_src = dtab + 2 * cnt + base; fe_t *const *d_scr = (fe_t *const *)(dtab + cnt + base), *const *d_dst = (fe_t *const *)(dtab + base);
+    CHK(enqueue_passes(*p, PassVectors::batch(d_src, d_scr, d_dst, c), post3, fold_tw, coset));
   }
   tr.done();
   return MI355_OK;
@@ -320,11 +326,6 @@ template <class F> int run_per_device_lists(const std::vector<BatchItem> &items,
 }
 template <class F> int run_per_device(const std::vector<BatchItem> &items, F run) {
   return run_per_device_lists(items, [&](int slot, const std::vector<uint32_t> &idx) -> int { for (uint32_t i : idx) CHK(run(slot, i)); return MI355_OK; });
-}
-int transform_in_place(fe_t *data, uint32_t log_n, const void *omega, const void *divisor) {
-  if (!divisor) return ntt_dev_impl(data, 1ull << log_n, data, log_n, omega, nullptr, nullptr);
-  fe_t post[3]; for (int i = 0; i < 3; i++) memcpy(&post[i], divisor, 32);
-  return ntt_dev_impl(data, 1ull << log_n, data, log_n, omega, nullptr, post);
 }
 // Host-pointer batch on ONE device (called with the device's lock held): upload of item i + 1 | transform of item i | download of item i - 1.
 // PCIe is full duplex, but a copy from / to pageable memory blocks its calling thread for the whole transfer, so the downloads run on a helper
@@ -384,6 +385,19 @@ int ntt_host_pipeline(const std::vector<uint32_t> &idx, void *const *data_host, 
   if (sh.err != hipSuccess) return fail(MI355_EHIP, std::string("ntt_batch download: ") + hipGetErrorString(sh.err));
   return rc;
 }
+// The host-pointer transforms, with the device lock held: upload in_bytes to a staging buffer, body(source, destination) on the staged data, download out_bytes; synchronous.
+// In place in "io.ntt" unless src_role names a second staging buffer for the source.
+template <class F> int host_transform(const void *in_host, size_t in_bytes, const char *src_role, void *out_host, size_t out_bytes, F body) {
+  void *src = nullptr, *dst;
+  if (src_role) CHK(ws_get(src_role, in_bytes, &src));
+  CHK(ws_get("io.ntt", out_bytes, &dst));
+  if (!src_role) src = dst;
+  HIPCHK(hipMemcpyAsync(src, in_host, in_bytes, hipMemcpyHostToDevice, g.stream));
+  CHK(body((const fe_t *)src, (fe_t *)dst));
+  HIPCHK(hipMemcpyAsync(out_host, dst, out_bytes, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream)); resolve_spans();
+  return MI355_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -393,7 +407,7 @@ int mi355_ntt_fr_dev(void *data_dev, uint32_t log_n, const void *omega) {
   return guarded([&]() -> int {
   int slot; CHK(common_slot({data_dev}, &slot, "ntt")); DevGuard lk(slot);
   CHK(need_init(slot)); CHK(check_ntt_args(data_dev, log_n, omega));
-  CHK(ntt_dev_impl((const fe_t *)data_dev, 1ull << log_n, (fe_t *)data_dev, log_n, omega, nullptr, nullptr));
+  CHK(transform_in_place((fe_t *)data_dev, log_n, omega, nullptr));
   return finish_async();
   });
 }
@@ -402,8 +416,7 @@ int mi355_intt_fr_dev(void *data_dev, uint32_t log_n, const void *omega_inv, con
   int slot; CHK(common_slot({data_dev}, &slot, "intt")); DevGuard lk(slot);
   CHK(need_init(slot)); CHK(check_ntt_args(data_dev, log_n, omega_inv));
   if (!divisor) return fail(MI355_EBADARG, "intt: null divisor");
-  fe_t post[3]; for (int i = 0; i < 3; i++) memcpy(&post[i], divisor, 32);
-  CHK(ntt_dev_impl((const fe_t *)data_dev, 1ull << log_n, (fe_t *)data_dev, log_n, omega_inv, nullptr, post));
+  CHK(transform_in_place((fe_t *)data_dev, log_n, omega_inv, divisor));
   return finish_async();
   });
 }
@@ -417,7 +430,15 @@ int mi355_coeff_to_extended_dev(void *dst_dev, const void *coeffs_dev, uint32_t 
   return finish_async();
   });
 }
-static int extended_to_coeff_locked(void *data_dev, uint32_t log_ext, const void *g_coset, const void *g_coset_inv, const void *extended_omega_inv, const void *extended_ifft_divisor);
+// body of mi355_extended_to_coeff_dev, to be called with the device lock held
+static int extended_to_coeff_locked(void *data_dev, uint32_t log_ext, const void *g_coset, const void *g_coset_inv, const void *extended_omega_inv, const void *extended_ifft_divisor) {
+  CHK(check_ntt_args(data_dev, log_ext, extended_omega_inv));
+  if (!g_coset || !g_coset_inv || !extended_ifft_divisor) return fail(MI355_EBADARG, "extended_to_coeff: null pointer");
+  // post-scale table {d, d * g_coset_inv, d * g_coset}: three constant products formed on the host (setup, not data path)
+  fe_t d, gc, gci, post[3]; memcpy(&d, extended_ifft_divisor, 32); memcpy(&gc, g_coset, 32); memcpy(&gci, g_coset_inv, 32);
+  post[0] = d; post[1] = Fr::mul(d, gci); post[2] = Fr::mul(d, gc);
+  return ntt_dev_impl((const fe_t *)data_dev, 1ull << log_ext, (fe_t *)data_dev, log_ext, extended_omega_inv, nullptr, post);
+}
 int mi355_extended_to_coeff_dev(void *data_dev, uint32_t log_ext, const void *g_coset, const void *g_coset_inv, const void *extended_omega_inv, const void *extended_ifft_divisor) {
   return guarded([&]() -> int {
   int slot; CHK(common_slot({data_dev}, &slot, "extended_to_coeff")); DevGuard lk(slot);
@@ -431,9 +452,8 @@ int mi355_ntt_fr_host(void *data_host, uint32_t log_n, const void *omega) {
   return guarded([&]() -> int {
   const int slot = pick_replica_slot(); DevGuard lk(slot);   // host-pointer calls may run on any bound device (replicas): callers on different threads land on different devices
   CHK(need_init(slot)); CHK(check_ntt_args(data_host, log_n, omega));
-  NttHostArgs a{log_n, omega, nullptr};
   const size_t bytes = sizeof(fe_t) << log_n;
-  return with_host_io(data_host, bytes, bytes, bytes, "io.ntt", [](void *dev, void *ud) { auto *a = (NttHostArgs *)ud; return ntt_dev_impl((const fe_t *)dev, 1ull << a->log_n, (fe_t *)dev, a->log_n, a->omega, nullptr, nullptr); }, &a);
+  return host_transform(data_host, bytes, nullptr, data_host, bytes, [&](const fe_t *, fe_t *dev) { return transform_in_place(dev, log_n, omega, nullptr); });
   });
 }
 int mi355_intt_fr_host(void *data_host, uint32_t log_n, const void *omega_inv, const void *divisor) {
@@ -441,48 +461,27 @@ int mi355_intt_fr_host(void *data_host, uint32_t log_n, const void *omega_inv, c
   const int slot = pick_replica_slot(); DevGuard lk(slot);   // host-pointer calls may run on any bound device (replicas): callers on different threads land on different devices
   CHK(need_init(slot)); CHK(check_ntt_args(data_host, log_n, omega_inv));
   if (!divisor) return fail(MI355_EBADARG, "intt: null divisor");
-  NttHostArgs a{log_n, omega_inv, divisor};
   const size_t bytes = sizeof(fe_t) << log_n;
-  return with_host_io(data_host, bytes, bytes, bytes, "io.ntt", [](void *dev, void *ud) {
-    auto *a = (NttHostArgs *)ud; fe_t post[3]; for (int i = 0; i < 3; i++) memcpy(&post[i], a->divisor, 32);
-    return ntt_dev_impl((const fe_t *)dev, 1ull << a->log_n, (fe_t *)dev, a->log_n, a->omega, nullptr, post); }, &a);
+  return host_transform(data_host, bytes, nullptr, data_host, bytes, [&](const fe_t *, fe_t *dev) { return transform_in_place(dev, log_n, omega_inv, divisor); });
   });
 }
 int mi355_coeff_to_extended_host(void *dst_host, const void *coeffs_host, uint32_t log_n, uint32_t log_ext, const void *g_coset, const void *g_coset_inv, const void *extended_omega) {
   return guarded([&]() -> int {
-  {
-    const int slot = pick_replica_slot(); DevGuard lk(slot);   // host-pointer calls may run on any bound device (replicas): callers on different threads land on different devices
-    CHK(need_init(slot)); CHK(check_ntt_args(dst_host, log_ext, extended_omega));
-    if (!coeffs_host || !g_coset || !g_coset_inv || log_n > log_ext) return fail(MI355_EBADARG, "coeff_to_extended: bad argument");
-    void *src, *dst; CHK(ws_get("io.ntt_src", sizeof(fe_t) << log_n, &src)); CHK(ws_get("io.ntt", sizeof(fe_t) << log_ext, &dst));
-    HIPCHK(hipMemcpyAsync(src, coeffs_host, sizeof(fe_t) << log_n, hipMemcpyHostToDevice, g.stream));
+  const int slot = pick_replica_slot(); DevGuard lk(slot);   // host-pointer calls may run on any bound device (replicas): callers on different threads land on different devices
+  CHK(need_init(slot)); CHK(check_ntt_args(dst_host, log_ext, extended_omega));
+  if (!coeffs_host || !g_coset || !g_coset_inv || log_n > log_ext) return fail(MI355_EBADARG, "coeff_to_extended: bad argument");
+  return host_transform(coeffs_host, sizeof(fe_t) << log_n, "io.ntt_src", dst_host, sizeof(fe_t) << log_ext, [&](const fe_t *src, fe_t *dst) {
     fe_t pre[3]; pre[0] = Fr::one(); memcpy(&pre[1], g_coset, 32); memcpy(&pre[2], g_coset_inv, 32);
-    CHK(ntt_dev_impl((const fe_t *)src, 1ull << log_n, (fe_t *)dst, log_ext, extended_omega, pre, nullptr));
-    HIPCHK(hipMemcpyAsync(dst_host, dst, sizeof(fe_t) << log_ext, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream)); resolve_spans();
-  }
-  return MI355_OK;
+    return ntt_dev_impl(src, 1ull << log_n, dst, log_ext, extended_omega, pre, nullptr);
   });
-}
-// body of mi355_extended_to_coeff_dev, to be called with the device lock held
-static int extended_to_coeff_locked(void *data_dev, uint32_t log_ext, const void *g_coset, const void *g_coset_inv, const void *extended_omega_inv, const void *extended_ifft_divisor) {
-  CHK(check_ntt_args(data_dev, log_ext, extended_omega_inv));
-  if (!g_coset || !g_coset_inv || !extended_ifft_divisor) return fail(MI355_EBADARG, "extended_to_coeff: null pointer");
-  // post-scale table {d, d * g_coset_inv, d * g_coset}: three constant products formed on the host (setup, not data path)
-  fe_t d, gc, gci, post[3]; memcpy(&d, extended_ifft_divisor, 32); memcpy(&gc, g_coset, 32); memcpy(&gci, g_coset_inv, 32);
-  post[0] = d; post[1] = Fr::mul(d, gci); post[2] = Fr::mul(d, gc);
-  return ntt_dev_impl((const fe_t *)data_dev, 1ull << log_ext, (fe_t *)data_dev, log_ext, extended_omega_inv, nullptr, post);
+  });
 }
 int mi355_extended_to_coeff_host(void *data_host, uint32_t log_ext, const void *g_coset, const void *g_coset_inv, const void *extended_omega_inv, const void *extended_ifft_divisor) {
   return guarded([&]() -> int {
   const int slot = pick_replica_slot(); DevGuard lk(slot);   // host-pointer calls may run on any bound device (replicas): callers on different threads land on different devices
   CHK(need_init(slot)); CHK(check_ntt_args(data_host, log_ext, extended_omega_inv));
-  void *dev; CHK(ws_get("io.ntt", sizeof(fe_t) << log_ext, &dev));
-  HIPCHK(hipMemcpyAsync(dev, data_host, sizeof(fe_t) << log_ext, hipMemcpyHostToDevice, g.stream));
-  CHK(extended_to_coeff_locked(dev, log_ext, g_coset, g_coset_inv, extended_omega_inv, extended_ifft_divisor));
-  HIPCHK(hipMemcpyAsync(data_host, dev, sizeof(fe_t) << log_ext, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream)); resolve_spans();
-  return MI355_OK;
+  const size_t bytes = sizeof(fe_t) << log_ext;
+  return host_transform(data_host, bytes, nullptr, data_host, bytes, [&](const fe_t *, fe_t *dev) { return extended_to_coeff_locked(dev, log_ext, g_coset, g_coset_inv, extended_omega_inv, extended_ifft_divisor); });
   });
 }
 

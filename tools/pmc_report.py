@@ -127,7 +127,7 @@ def ntt_table(frows, wrows, title):
     return rows
 
 
-md += ntt_table(fetch, write, "## NTT 2^26, single transforms (`mi355_ntt_fr_dev` / `mi355_intt_fr_dev`: k_ntt29_strided<2,0> x 2 + k_ntt29_final<2,0>; N x 32 B = 2.147e9 B per vector)")
+md += ntt_table(fetch, write, "## NTT 2^26, single transforms (`mi355_ntt_fr_dev` / `mi355_intt_fr_dev`: k_ntt29_strided<2> x 2 + k_ntt29_final<2>; N x 32 B = 2.147e9 B per vector)")
 l4f, l4w, l4s = parse("L4_pmc_FETCH_SIZE.txt"), parse("L4_pmc_WRITE_SIZE.txt"), parse("L4_pmc_sq.txt")
 md += ntt_table(l4f, l4w, "## NTT 2^26 THROUGH THE BATCHED ENTRY POINTS (`mi355_ntt_fr_batch_dev`, `mi355_coset_ntt_fr_batch_dev`): every transform of one layer-4 create_proof + its keygen")
 if sq:
