@@ -132,6 +132,8 @@ void orc_f_from_canonical(int w, fe *o, const fe *a) { fe_from_canonical(o, a, s
 void orc_f_to_canonical(int w, fe *o, const fe *a) { fe_to_canonical(o, a, sel(w)); }
 /* vector helpers */
 void orc_f_mul_vec(int w, fe *o, const fe *a, const fe *b, uint64_t n) { for (uint64_t i = 0; i < n; i++) fe_mul(&o[i], &a[i], &b[i], sel(w)); }
+void orc_f_add_vec(int w, fe *o, const fe *a, const fe *b, uint64_t n) { for (uint64_t i = 0; i < n; i++) fe_add(&o[i], &a[i], &b[i], sel(w)); }
+void orc_f_sub_vec(int w, fe *o, const fe *a, const fe *b, uint64_t n) { for (uint64_t i = 0; i < n; i++) fe_sub(&o[i], &a[i], &b[i], sel(w)); }
 void orc_f_from_canonical_vec(int w, fe *o, const fe *a, uint64_t n) { for (uint64_t i = 0; i < n; i++) fe_from_canonical(&o[i], &a[i], sel(w)); }
 void orc_f_to_canonical_vec(int w, fe *o, const fe *a, uint64_t n) { for (uint64_t i = 0; i < n; i++) fe_to_canonical(&o[i], &a[i], sel(w)); }
 

@@ -110,6 +110,16 @@ def f_mul_vec(w, a, b):
     lib().orc_f_mul_vec(w, _p(o), _p(a), _p(b), C.c_uint64(a.shape[0])); return o
 
 
+def f_add_vec(w, a, b):
+    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b); o = np.empty_like(a)
+    lib().orc_f_add_vec(w, _p(o), _p(a), _p(b), C.c_uint64(a.shape[0])); return o
+
+
+def f_sub_vec(w, a, b):
+    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b); o = np.empty_like(a)
+    lib().orc_f_sub_vec(w, _p(o), _p(a), _p(b), C.c_uint64(a.shape[0])); return o
+
+
 def int_to_limbs(x: int):
     return np.array([(x >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
 

@@ -269,3 +269,42 @@ def test_glv_decomposition_and_joint_scalar_multiple(hs):
             jac = np.zeros(12, dtype=np.uint64); hs.hs_xyzz_to_jac(p_(jac), p_(out))
             got = pyref.g1_jacobian_from_limbs(jac[:4], jac[4:8], jac[8:])
             assert got == (pyref.g1_mul(Pt, k) if k % R else None), (k, Pt)
+
+
+def test_every_pair_of_adversarial_words(hs):
+    """fp.hpp and fp29.hpp on every ordered pair of the adversarial word pool (tests/gpu_common.py), the words taken as they are: expected values from
+    Python integers.  The same pairs pin the C oracle's add / sub / mul, which the GPU tests use where Python is too slow."""
+    from tests import gpu_common as gc
+    ints = gc.adversarial_fr_ints()
+    a, b = gc.pool_pairs(gc.adversarial_fr_words())
+    xs, ys = gc.words_to_ints(a), gc.words_to_ints(b)
+    rinv = pow(1 << 256, -1, R)
+    assert len(xs) == len(ints) ** 2
+    want = {
+        "add": gc.ints_to_words((x + y) % R for x, y in zip(xs, ys)),
+        "sub": gc.ints_to_words((x - y) % R for x, y in zip(xs, ys)),
+        "mul": gc.ints_to_words(x * y * rinv % R for x, y in zip(xs, ys)),
+        "sqr": gc.ints_to_words(x * x * rinv % R for x in xs),
+    }
+    assert (cref.f_add_vec(cref.FR, a, b) == want["add"]).all() and (cref.f_sub_vec(cref.FR, a, b) == want["sub"]).all() and (cref.f_mul_vec(cref.FR, a, b) == want["mul"]).all()
+    for i in range(0, len(xs), 37):                                     # the scalar entry points are the same C functions
+        assert (cref.f_add(cref.FR, a[i], b[i]) == want["add"][i]).all() and (cref.f_sub(cref.FR, a[i], b[i]) == want["sub"][i]).all() and (cref.f_mul(cref.FR, a[i], b[i]) == want["mul"][i]).all()
+
+    def o29(which, x, y):
+        out = np.zeros(4, dtype=np.uint64); hs.hs_f29_op(cref.FR, which, p_(out), p_(x), p_(y)); return pyref.from_limbs(out)
+
+    for i, (x, y) in enumerate(zip(xs, ys)):
+        A, B = a[i], b[i]
+        for which, key in ((0, "add"), (1, "sub"), (2, "mul"), (7, "mul"), (8, "sqr")):
+            assert (op(hs, cref.FR, which, A, B) == want[key][i]).all(), (which, hex(x), hex(y))
+        assert pyref.from_limbs(op(hs, cref.FR, 4, A)) == -x % R          # Fr::neg keeps zero as zero (the -1 path of k_fr_gate_eval relies on it)
+        assert o29(0, A, B) == x * y * rinv % R, (hex(x), hex(y))
+        assert o29(1, A, B) == x * x * rinv % R
+        assert o29(2, A, B) == (x + y) * y * rinv % R
+        assert o29(3, A, B) == (x - y) % R
+        assert o29(4, A, B) == (x - 2 * y) % R
+        assert o29(5, A, B) == (3 * x - y) % R
+        assert o29(6, A, B) == (2 * x - y) ** 2 * rinv % R
+        assert o29(7, A, B) == x
+        assert o29(8, A, B) == ((x - y) * (y - 2 * x) - (y - x) * x) * rinv % R
+        assert bool(hs.hs_f29_is_zero(cref.FR, p_(A), p_(B))) is (x == y)

@@ -186,3 +186,53 @@ def test_host_compact_nonzero_needs_no_device():
         for threads in (1, 3, 16):
             idx, vals = h2.compact_nonzero(col, threads)
             assert (idx == want).all() and (vals == col[want]).all()
+
+
+def test_full_range_operand_generators():
+    """tests/gpu_common.py: the adversarial word pool is a duplicate-free set of legal words, and every rand_fr_full draw of the full-range GPU tests
+    has at least 60 % of its words at or above 2^252 (expected 1 - 2^252 / r = 66.9 %, standard deviation 1.5 % at n = 1000), where rand_fr has none."""
+    from tests import gpu_common as gc
+    R = pyref.R_MOD
+    ints = gc.adversarial_fr_ints()
+    words = gc.adversarial_fr_words()
+    assert all(0 <= v < R for v in ints) and len(set(ints)) == len(ints) >= 50
+    assert words.shape == (len(ints), 4) and words.dtype == np.uint64 and gc.words_to_ints(words) == ints and gc.below_r(words).all()
+    mont = (1 << 256) % R
+    for v in [0, 1, 2, R - 1, R - 2, (R - 1) // 2, (R + 1) // 2, mont, R - mont, 2 * mont % R, gc.ALL_ONES_LIMBS, (1 << 252) - 1, 1 << 252, 1 << 253,
+              int("55" * 32, 16) % R, int("AA" * 32, 16) % R] + [(1 << (29 * i)) + d for i in range(1, 9) for d in (-1, 0, 1)] + [(1 << (32 * i)) - d for i in range(1, 8) for d in (1, 0)]:
+        assert v in ints, hex(v)
+    assert gc.ALL_ONES_LIMBS < R and all((gc.ALL_ONES_LIMBS >> (29 * i)) & 0x1FFFFFFF == 0x1FFFFFFF for i in range(8)) and gc.ALL_ONES_LIMBS + (1 << 232) >= R
+    a, b = gc.pool_pairs(words)
+    m = len(ints)
+    assert a.shape == b.shape == (m * m, 4) and set(zip(gc.words_to_ints(a), gc.words_to_ints(b))) == {(x, y) for x in ints for y in ints}
+    assert (gc.tile_words(words, 2 * m + 3)[m:2 * m] == words).all()
+    r0 = gc.rand_fr(np.random.default_rng(1), 1000, full=False)
+    assert (r0[:, 3] < np.uint64(1 << 60)).all()                       # what the older generator covers
+    for name, (seed, sizes) in gc.FULL_RANGE_DRAWS.items():
+        big = gc.full_range(name, max(sizes))
+        assert big.shape == (max(sizes), 4) and big.dtype == r0.dtype and gc.below_r(big).all()
+        for n in sizes:
+            if n >= 1000:
+                share = float((big[:n, 3] >= np.uint64(1 << 60)).mean())
+                assert share >= 0.60, (name, seed, n, share)
+        assert (gc.full_range(name, 1000) == big[:1000]).all()        # a shorter draw is a prefix
+
+
+def test_scan_oracle_agrees_with_integers_on_the_pool():
+    """the C oracle's batch_invert / prefix_sum / prefix_product on the adversarial word pool against Python integers: what the full-range GPU scan
+    tests lean on"""
+    from tests import gpu_common as gc
+    R = pyref.R_MOD
+    rinv, mont = pow(1 << 256, -1, R), (1 << 256) % R
+    ints, pool = gc.adversarial_fr_ints(), gc.adversarial_fr_words()
+    assert gc.words_to_ints(cref.batch_invert(pool)) == [pow(v * rinv, -1, R) * (1 << 256) % R if v else 0 for v in ints]
+    z, t = cref.prefix_sum(pool)
+    acc, want = 0, []
+    for v in ints:
+        want.append(acc); acc = (acc + v) % R
+    assert gc.words_to_ints(z) == want and gc.words_to_ints(t)[0] == acc
+    z, t = cref.prefix_product(pool[1:])
+    acc, want = mont, []
+    for v in ints[1:]:
+        want.append(acc); acc = acc * v * rinv % R
+    assert gc.words_to_ints(z) == want and gc.words_to_ints(t)[0] == acc
