@@ -188,7 +188,7 @@ template <class P> struct Fp {
   // signed limbs and a 2x2 transition matrix per 30 steps).  Montgomery form in and out; 0 -> 0.  The instruction stream does not depend on
   // the data -- 20 batches of 30 steps cover every 256-bit input (bound 590) -- so a whole wavefront can invert 64 different values
   // without divergence, and the dependent chains are 32-bit shifts / adds instead of multiword borrow chains: about a quarter of the
-  // binary Euclid's latency in the one-lane normalisations (k_msm_final29, the tile inversions of the scans).
+  // binary Euclid's latency in the one-lane normalisations (k_msm_final, the tile inversions of the scans).
   // State: f = m, g = a, d = 0, e = 1 with d * a = f, e * a = g (mod m) up to the running power of two, which update_de divides out.
   static constexpr int32_t SG_M30 = 0x3fffffff;
   ZK_HD static constexpr uint32_t sg_mod(int i) {   // bits [30 i, 30 i + 30) of the modulus

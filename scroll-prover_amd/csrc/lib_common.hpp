@@ -99,7 +99,6 @@ struct Ctx {
   std::map<std::string, NttPlan> ntt_plans;  // key = log_n | omega bytes
   g1_affine_t *fixed_base_table = nullptr;
   uint32_t sort_t2 = 0;         // MI355_SORT_T2 = 8192 | 16384 (0: by size)
-  uint32_t debug_gather_mask = 0x7fffffffu;   // MI355_DEBUG_GATHER_MASK (timing experiments only: results become wrong)
   uint32_t seg_factor = 16;
   uint32_t sort_fb = 11;        // MI355_SORT_FB: fine (level-2) key bits of the sorter, 9..12
   uint32_t sort_split = 1;      // MI355_SORT_SPLIT: the level-1 output is two streams (payload u32 + fine key u16); 1 = 24 576-entry tiles where the bin bookkeeping leaves room, 2 = 16 384-entry tiles (the single-stream u64 records were an A/B path of round 3 and left the library in round 6)

@@ -282,9 +282,6 @@ static int init_ctx(int slot, int device_id) {
   CHK(ntt_tu_init_device());
   CHK(aux_tu_init_device());
   { const char *e = getenv("MI355_TRACE"); g.trace = e && e[0] == '1'; }
-#ifdef MI355_DEBUG_KNOBS
-  { const char *e = getenv("MI355_DEBUG_GATHER_MASK"); if (e) g.debug_gather_mask = (uint32_t)strtoul(e, nullptr, 0); }
-#endif
   { const char *e = getenv("MI355_REDUCE_CHAINS"); if (e) { int v = atoi(e); if (v >= 1024) g.reduce_chains = (uint32_t)v; } }
   { const char *e = getenv("MI355_SEG_FILL"); if (e) { int v = atoi(e); if (v >= 2 && v <= 100) g.seg_fill = (uint32_t)v; } }
   { const char *e = getenv("MI355_SEG_FILL_SEGFIX"); if (e) { int v = atoi(e); if (v >= 2 && v <= 100) g.seg_fill_segfix = (uint32_t)v; } }

@@ -2,6 +2,8 @@
 // segmented accumulation -> fix-up -> reduction tail), the host-pointer and sharded (multi-device) schedules, the C-ABI entry points
 // mi355_msm_* / mi355_g1_sum_*, and the SRS entry points that launch kernels of msm.hpp (params-file loader with on-device validation,
 // window-table build, synthetic SRS).  Host logic only; all arithmetic runs in the kernels.
+// The bucket pipeline exists once: msm_shape, msm_acc_plan, msm_stage_polys, msm_sort_stage, msm_segfix_levels<G> and msm_reduce_tail<G>
+// serve the G1 schedules (msm_enqueue and its callers) and the G2 MSM (msm_g2_impl); G is the point-operations policy of msm.hpp / msm_g2.hpp.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #define ZK_FRSCAN_DEVICE_ONLY 1   // msm.hpp needs the block scans of frscan.hpp, not its kernels (those belong to lib_aux.hip)
 #include "msm.hpp"
@@ -43,11 +45,11 @@ int choose_c(uint64_t n) {
 }
 
 struct PreTable { const g1_affine_t *table = nullptr; uint64_t row_stride = 0; int c = 0, w = 0; };   // table already offset to the slice start
-
-int msm_batch_impl(const g1_affine_t *bases, const fe_t *const *polys_host, uint32_t M, uint64_t n, void *out_host, const PreTable *pre, void *out_dev_user = nullptr, bool accumulate_plan = false);
-
-int msm_dev_impl(const g1_affine_t *bases, const fe_t *scalars, uint64_t n, void *out_host, const PreTable *pre = nullptr) {
-  return msm_batch_impl(bases, &scalars, 1, n, out_host, pre);
+// the same tables for a point range that starts `lo` points further on (slices of a chunked MSM); null stays null
+const PreTable *pre_advance(const PreTable *pre, uint64_t lo, PreTable &store) {
+  if (!pre) return nullptr;
+  store = *pre; if (store.table) store.table += lo;
+  return &store;
 }
 
 // The shape of one MSM pass -- window bits, table use, sorter key split, entry / bucket counts -- derived in ONE place for the launch code
@@ -75,45 +77,106 @@ int msm_shape(uint64_t n, uint32_t M, const PreTable *pre, MsmShape &o, const Ms
   return MI355_OK;
 }
 
+// a batch that would overflow the 32-bit entry index, the coarse histogram's LDS or 8 GiB of bucket records runs as two half batches
+template <class G> bool msm_batch_must_split(uint64_t n, uint32_t M, const PreTable *pre) {
+  MsmShape sh;
+  return msm_shape(n, M, pre, sh) != MI355_OK || sh.emax > (1ull << 29) || sh.nbuckets * sizeof(typename G::rec_t) > (8ull << 30);
+}
+
+// workspace roles of one pass: the policy's prefix ("msm." / "msm2."), the buffer's name, "#slot" for the second slot of a pipelined MSM
+struct Roles {
+  const char *prefix; std::string sfx;
+  template <class T> int get(const char *name, size_t bytes, T *&ptr) const { return ws_get((std::string(prefix) + name + sfx).c_str(), bytes, (void **)&ptr); }
+};
+
+// up to 8 polynomial pointers travel in the kernel argument; a longer array is staged through a buffer the library owns (the caller's
+// array may be a temporary)
+int msm_stage_polys(const fe_t *const *polys_host, uint32_t M, const Roles &ws, hipStream_t s, PolyPtrs &inl, const fe_t **&polys_dev) {
+  if (M <= 8) { for (uint32_t m = 0; m < M; m++) inl.p[m] = polys_host[m]; return MI355_OK; }
+  CHK(ws.get("polys", (size_t)M * sizeof(void *), polys_dev));
+  g.polys_stage.assign(polys_host, polys_host + M);
+  HIPCHK(hipMemcpyAsync(polys_dev, g.polys_stage.data(), (size_t)M * sizeof(void *), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return MI355_OK;
+}
+
+// The accumulate launch: worst-case entries per thread (16 .. 4096, MI355_SEG_FACTOR segments per lane slot), workgroups, threads.  The
+// kernels derive the actual segment from the entry count on the device (msm_seg_eff) out of the packed argument msm_seg_arg builds:
+// worst-case segment | minimum << 13 | (fill percentage / 2) << 26.
+struct AccPlan { uint32_t seg, blocks, tn; };
+AccPlan msm_acc_plan(uint64_t emax) {
+  const uint64_t want_threads = (uint64_t)g.prop.multiProcessorCount * 256 * g.seg_factor;
+  uint64_t seg = (emax + want_threads - 1) / want_threads; if (seg < 16) seg = 16; if (seg > 4096) seg = 4096;
+  const uint32_t blocks = ceil_div(ceil_div(emax, seg), 256);
+  return {(uint32_t)seg, blocks, blocks * 256};
+}
+uint32_t msm_seg_arg(uint32_t seg, uint32_t fill_pct) { return seg | (std::min(g.seg_min, seg) << 13) | ((fill_pct / 2) << 26); }
+MsmPlan msm_plan(const MsmShape &sh, uint64_t n, uint32_t M, uint32_t seg) {
+  MsmPlan P; P.n = (uint32_t)n; P.c = sh.c; P.windows = sh.W; P.nb = 1u << (sh.c - 1); P.seg = seg; P.batch = M;
+  return P;
+}
+
+// launch(std::integral_constant<int, Q>): Q = 4 (a quad per logical thread, the latency form) where the caller asks for it and the policy
+// has it, else Q = 1 (one lane per logical thread, the throughput form)
+template <class G, class F> void with_lanes(bool quad, F &&launch) {
+  if constexpr (G::QUAD) { if (quad) { launch(std::integral_constant<int, 4>{}); return; } }
+  launch(std::integral_constant<int, 1>{});
+}
+
+// The fix-up of straddling buckets as ONE segmented reduction over the 2 * tn partial slots of the accumulate threads, level by level
+// (64 slots -> 2 per level) until one wavefront holds the rest.
+template <class G> int msm_segfix_levels(const int32_t *part_id, const typename G::rec_t *part, uint32_t tn, typename G::rec_t *buckets, hipStream_t s, const Roles &ws) {
+  using rec_t = typename G::rec_t;
+  uint32_t N = 2 * tn; const uint32_t waves1 = ceil_div(N, 64);
+  const size_t cap = (size_t)2 * waves1 + (size_t)waves1 / 8 + 512;
+  int32_t *lv_ids; rec_t *lv_recs;
+  CHK(ws.get("segfix_ids", cap * 4, lv_ids)); CHK(ws.get("segfix_recs", cap * sizeof(rec_t), lv_recs));
+  const int32_t *cur_ids = part_id; const rec_t *cur_recs = part; size_t used = 0;
+  while (N > 64) {
+    const uint32_t waves = ceil_div(N, 64);
+    hipLaunchKernelGGL(k_msm_segfix<G>, dim3(ceil_div(N, 256)), dim3(256), 0, s, cur_ids, cur_recs, N, buckets, lv_ids + used, lv_recs + used, 0);
+    cur_ids = lv_ids + used; cur_recs = lv_recs + used; used += (size_t)2 * waves; N = 2 * waves;
+  }
+  hipLaunchKernelGGL(k_msm_segfix<G>, dim3(1), dim3(64), 0, s, cur_ids, cur_recs, N, buckets, (int32_t *)nullptr, (rec_t *)nullptr, 1);
+  return MI355_OK;
+}
+
 // The reduction tail of one MSM pass: sum_b (b + 1) B[b] per bucket set by short chunked running sums, a multi-block tree per set, the
-// Horner over windows (none with window tables) and the normalisation.  Runs entirely on the 29-bit field.
-int msm_reduce_tail(const MsmShape &sh, uint32_t M, const g1_xyzz29_t *buckets, g1_jac_t *out_dev, bool normalise, hipStream_t s, const std::string &sfx) {
-  auto role = [&](const char *r) { return std::string(r) + sfx; };
-  const uint32_t nb = 1u << (sh.c - 1), red_wpp = sh.shared ? 1 : sh.W, red_windows = M * red_wpp;
+// Horner over windows (none with window tables) and the result in the caller's form (G1: Jacobian, normalised on request; G2: affine).
+template <class G> int msm_reduce_tail(const MsmShape &sh, uint32_t M, const typename G::rec_t *buckets, typename G::out_t *out_dev, bool normalise, hipStream_t s, const Roles &ws) {
+  using rec_t = typename G::rec_t;
+  const uint32_t nb = 1u << (sh.c - 1), wpp = sh.shared ? 1 : sh.W, sets = M * wpp;   // bucket sets per polynomial, bucket sets to reduce
   // running-sum chunk per reduce thread: every thread is one serial chain of 2*chunk additions plus a ~(c-1)-bit scalar multiple, so the
   // chain is kept short (the kernel is latency-bound) as long as there are enough buckets to give the GPU ~128k chains (measured at 2^21 buckets: 2.58 ms with 256k chains of 8 buckets, 2.11 ms with 128k of 16, 2.63 ms with 64k of 32)
   uint32_t chunk = 64; while (chunk > nb) chunk >>= 1;
   // (bucket sets of small MSMs: chains down to g.reduce_min_chunk buckets -- the chain is then mostly the (c - 2)-bit multiple of the
   // chunk sum, ~26 instead of ~37 addition times at 2^16 buckets)
-  while (chunk > g.reduce_min_chunk && (uint64_t)(nb / chunk) * red_windows < g.reduce_chains) chunk >>= 1;
-  const uint32_t chunks_per_window = nb / chunk, nchunks = chunks_per_window * red_windows;
-  g1_xyzz29_t *chunk_out, *tree_a, *tree_b, *window_sums;
-  CHK(ws_get(role("msm.chunk_out").c_str(), (size_t)nchunks * sizeof(g1_xyzz29_t), (void **)&chunk_out));
-  { const size_t lvl = (size_t)ceil_div(chunks_per_window, 64 * TREE_PER_THREAD) * red_windows + 1;   // 64: the quad form's logical threads per block
-    CHK(ws_get(role("msm.tree_a").c_str(), lvl * sizeof(g1_xyzz29_t), (void **)&tree_a)); CHK(ws_get(role("msm.tree_b").c_str(), lvl * sizeof(g1_xyzz29_t), (void **)&tree_b)); }
-  CHK(ws_get(role("msm.window_sums").c_str(), (size_t)red_windows * sizeof(g1_xyzz29_t), (void **)&window_sums));
-  MsmPlan PR; PR.n = 0; PR.c = sh.c; PR.windows = red_windows; PR.nb = nb; PR.seg = 0; PR.batch = M;
+  while (chunk > g.reduce_min_chunk && (uint64_t)(nb / chunk) * sets < g.reduce_chains) chunk >>= 1;
+  const uint32_t chunks_per_set = nb / chunk, nchunks = chunks_per_set * sets;
+  rec_t *chunk_out, *tree_a, *tree_b, *window_sums;
+  CHK(ws.get("chunk_out", (size_t)nchunks * sizeof(rec_t), chunk_out));
+  { const size_t lvl = (size_t)ceil_div(chunks_per_set, 64 * TREE_PER_THREAD) * sets + 1;   // 64: the quad form's logical threads per block (an upper bound for the one-lane form)
+    CHK(ws.get("tree_a", lvl * sizeof(rec_t), tree_a)); CHK(ws.get("tree_b", lvl * sizeof(rec_t), tree_b)); }
+  CHK(ws.get("window_sums", (size_t)sets * sizeof(rec_t), window_sums));
   // latency form (a quad per logical thread, g1_xyzz29_add_q4: ~2.6x shorter dependent chain per addition) where the kernel cannot fill the
   // GPU anyway; throughput form (one lane per thread) for big bucket sets.  MI355_TAIL_COOP_MAX = largest logical thread count that takes the quads.
-  const bool coop_reduce = nchunks <= g.tail_coop_max && (g.tail_coop_mask & 2u);
-  if (coop_reduce) hipLaunchKernelGGL(k_msm_bucket_reduce<4>, dim3(ceil_div((uint64_t)nchunks * 4, 128)), dim3(128), 0, s, buckets, chunk_out, PR, chunk);
-  else hipLaunchKernelGGL(k_msm_bucket_reduce<1>, dim3(ceil_div(nchunks, 128)), dim3(128), 0, s, buckets, chunk_out, PR, chunk);
-  {
-    // tree-sum the chunk results per window, ping-ponging between two small buffers
-    const g1_xyzz29_t *cur = chunk_out; uint32_t cnt = chunks_per_window; g1_xyzz29_t *bufs[2] = {tree_a, tree_b}; int which = 0;
-    while (true) {
-      const bool coop = (uint64_t)cnt * red_windows <= g.tail_coop_max && (g.tail_coop_mask & 4u);
-      const uint32_t per_block = (coop ? 64u : 256u) * TREE_PER_THREAD;
-      const uint32_t outn = ceil_div(cnt, per_block);
-      g1_xyzz29_t *dst = outn == 1 ? window_sums : bufs[which];
-      if (coop) hipLaunchKernelGGL(k_msm_tree_sum29<4>, dim3(outn, red_windows), dim3(256), 0, s, cur, cnt, dst, outn);
-      else hipLaunchKernelGGL(k_msm_tree_sum29<1>, dim3(outn, red_windows), dim3(256), 0, s, cur, cnt, dst, outn);
-      if (outn == 1) break;
-      cur = dst; cnt = outn; which ^= 1;
-    }
+  with_lanes<G>(nchunks <= g.tail_coop_max && (g.tail_coop_mask & 2u), [&](auto q) {
+    constexpr int Q = decltype(q)::value;
+    hipLaunchKernelGGL((k_msm_bucket_reduce<G, Q>), dim3(ceil_div((uint64_t)nchunks * Q, 128)), dim3(128), 0, s, buckets, chunk_out, nb, sets, chunk);
+  });
+  // tree-sum the chunk results per set, ping-ponging between two small buffers
+  const rec_t *cur = chunk_out; uint32_t cnt = chunks_per_set; rec_t *bufs[2] = {tree_a, tree_b}; int which = 0;
+  while (true) {
+    const bool coop = G::QUAD && (uint64_t)cnt * sets <= g.tail_coop_max && (g.tail_coop_mask & 4u);
+    const uint32_t outn = ceil_div(cnt, (coop ? 64u : 256u) * TREE_PER_THREAD);
+    rec_t *dst = outn == 1 ? window_sums : bufs[which];
+    with_lanes<G>(coop, [&](auto q) { hipLaunchKernelGGL((k_msm_tree_sum<G, decltype(q)::value>), dim3(outn, sets), dim3(256), 0, s, cur, cnt, dst, outn); });
+    if (outn == 1) break;
+    cur = dst; cnt = outn; which ^= 1;
   }
-  if (g.tail_coop_max && (g.tail_coop_mask & 8u)) hipLaunchKernelGGL(k_msm_final29<4>, dim3(M), dim3(64), 0, s, (const g1_xyzz29_t *)window_sums, red_wpp, sh.shared ? 0u : sh.c, out_dev, normalise ? 1 : 0);
-  else hipLaunchKernelGGL(k_msm_final29<1>, dim3(M), dim3(64), 0, s, (const g1_xyzz29_t *)window_sums, red_wpp, sh.shared ? 0u : sh.c, out_dev, normalise ? 1 : 0);
+  with_lanes<G>(g.tail_coop_max && (g.tail_coop_mask & 8u), [&](auto q) {
+    hipLaunchKernelGGL((k_msm_final<G, decltype(q)::value>), dim3(M), dim3(64), 0, s, (const rec_t *)window_sums, wpp, sh.shared ? 0u : sh.c, out_dev, normalise ? 1 : 0);
+  });
   HIPCHK(hipGetLastError());
   return MI355_OK;
 }
@@ -203,44 +266,35 @@ struct MsmStreams { hipStream_t a, b, c; };
 int msm_enqueue(const g1_affine_t *bases, const PolyPtrs &inl, const fe_t *const *polys_dev, uint32_t M, uint64_t n, g1_jac_t *out_dev, const PreTable *pre, MsmSlot &slot,
                 const MsmStreams &st, bool normalise, const MsmShape *forced = nullptr, uint32_t set_index = 0, uint32_t set_count = 1, bool skip_tail = false) {
   const bool piped = st.a != st.b;
-  const std::string sfx = slot.id ? "#" + std::to_string(slot.id) : std::string();
-  auto role = [&](const char *r) { return std::string(r) + sfx; };
-#define WS(name, bytes, ptr) CHK(ws_get(role(name).c_str(), bytes, (void **)&ptr))
+  const Roles ws{G1Ops::ROLE, slot.id ? "#" + std::to_string(slot.id) : std::string()};
   MsmShape sh; CHK(msm_shape(n, M, pre, sh, forced));
   const bool shared = sh.shared;
   if (shared) bases = pre->table;
-  MsmPlan P; P.n = (uint32_t)n; P.batch = M; P.c = sh.c; P.windows = sh.W; P.nb = 1u << (P.c - 1);
   const uint64_t emax = sh.emax;
-  const uint64_t want_threads = (uint64_t)g.prop.multiProcessorCount * 256 * g.seg_factor;   // segments per lane slot (MI355_SEG_FACTOR)
-  uint64_t seg = (emax + want_threads - 1) / want_threads; if (seg < 16) seg = 16; if (seg > 4096) seg = 4096;
-  P.seg = (uint32_t)seg;
-  // worst-case segment (<= 4096) | minimum << 13 | (fill percentage / 2) << 26: the kernels derive the segment from the actual entry count.  With the
-  // segmented fix-up (two-partial buckets are cheap) the entries may spread over more threads than with the per-bucket kernels
+  const AccPlan ap = msm_acc_plan(emax);
+  const MsmPlan P = msm_plan(sh, n, M, ap.seg);
+  // with the segmented fix-up (two-partial buckets are cheap) the entries may spread over more threads than with the per-bucket kernels
   const bool segfix = g.fixup_mode == 1 || (g.fixup_mode == 2 && (uint32_t)sh.nbuckets >= (1u << 19) && (uint64_t)P.seg * sh.nbuckets >= emax);
-  const uint32_t seg_arg = P.seg | (std::min(g.seg_min, P.seg) << 13) | (((segfix ? g.seg_fill_segfix : g.seg_fill) / 2) << 26);
-  const uint32_t red_wpp = shared ? 1 : P.windows;        // bucket sets per polynomial
-  const uint32_t red_windows = M * red_wpp;               // bucket sets to reduce
+  const uint32_t seg_arg = msm_seg_arg(P.seg, segfix ? g.seg_fill_segfix : g.seg_fill);
   const uint32_t nbuckets = (uint32_t)sh.nbuckets;
-  const uint32_t acc_threads = ceil_div(emax, seg), acc_blocks = ceil_div(acc_threads, 256);
-  const uint32_t tn = acc_blocks * 256;
+  const uint32_t acc_blocks = ap.blocks, tn = ap.tn;
   uint32_t *offsets, *sorted;
   g1_xyzz29_t *buckets, *part; int32_t *part_id;
   // per-slot: what the accumulation and the reduction of this chunk read while the next chunk is being sorted
-  WS("msm.offsets", ((size_t)nbuckets + 1) * 4, offsets);
-  WS("msm.sorted", emax * 4, sorted);
-  WS("msm.buckets", (size_t)nbuckets * set_count * sizeof(g1_xyzz29_t), buckets);
+  CHK(ws.get("offsets", ((size_t)nbuckets + 1) * 4, offsets));
+  CHK(ws.get("sorted", emax * 4, sorted));
+  CHK(ws.get("buckets", (size_t)nbuckets * set_count * sizeof(g1_xyzz29_t), buckets));
   buckets += (size_t)nbuckets * set_index;
-  WS("msm.part", (size_t)tn * 2 * sizeof(g1_xyzz29_t), part);
-  WS("msm.part_id", (size_t)tn * 2 * 4, part_id);
+  CHK(ws.get("part", (size_t)tn * 2 * sizeof(g1_xyzz29_t), part));
+  CHK(ws.get("part_id", (size_t)tn * 2 * 4, part_id));
   const uint32_t big_cap = tn / g.fixup_serial_max + 2;
-  uint32_t *big_list; WS("msm.big_list", ((size_t)big_cap * 3 + 1) * 4, big_list);
+  uint32_t *big_list; CHK(ws.get("big_list", ((size_t)big_cap * 3 + 1) * 4, big_list));
   uint32_t *big_count = big_list + (size_t)big_cap * 3;
   // buckets that span >= FIXUP_HUGE_MIN accumulate threads (at most tn / FIXUP_HUGE_MIN of them) get FIXUP_SLICES workgroups each
   const uint32_t huge_cap = tn / FIXUP_HUGE_MIN + 2;
   uint32_t *huge_list, *huge_count; g1_xyzz29_t *huge_part;
-  WS("msm.huge_list", ((size_t)huge_cap * 3 + 1) * 4, huge_list); huge_count = huge_list + (size_t)huge_cap * 3;
-  WS("msm.huge_part", (size_t)huge_cap * FIXUP_SLICES * sizeof(g1_xyzz29_t), huge_part);
-#undef WS
+  CHK(ws.get("huge_list", ((size_t)huge_cap * 3 + 1) * 4, huge_list)); huge_count = huge_list + (size_t)huge_cap * 3;
+  CHK(ws.get("huge_part", (size_t)huge_cap * FIXUP_SLICES * sizeof(g1_xyzz29_t), huge_part));
 
   {
     hipStream_t s = st.a;
@@ -256,9 +310,7 @@ int msm_enqueue(const g1_affine_t *bases, const PolyPtrs &inl, const fe_t *const
     {
       Scope sc("msm_accumulate", s);
       HIPCHK(hipMemsetAsync(buckets, 0, (size_t)nbuckets * sizeof(g1_xyzz29_t), s));
-#define ACC_LAUNCH(V) hipLaunchKernelGGL(k_msm_accumulate<V>, dim3(acc_blocks), dim3(256), 0, s, bases, sorted, offsets, nbuckets, buckets, part, part_id, seg_arg, log2_ceil(n), shared ? pre->row_stride : (uint64_t)0, g.debug_gather_mask)
-      ACC_LAUNCH(4);   // <4>: limb products as explicitly chained v_mad (fp29.hpp mac_*).  The C++-multiplier variant <0> (59.5 vs 57.1 ms at 2^26, round 3) and the older A/B variants are no longer instantiated (round 6)
-#undef ACC_LAUNCH
+      hipLaunchKernelGGL(k_msm_accumulate, dim3(acc_blocks), dim3(256), 0, s, bases, sorted, offsets, nbuckets, buckets, part, part_id, seg_arg, log2_ceil(n), shared ? pre->row_stride : (uint64_t)0);
     }
     if (piped) { HIPCHK(hipEventRecord(slot.acc_done, s)); HIPCHK(hipStreamWaitEvent(st.c, slot.acc_done, 0)); }
   }
@@ -272,28 +324,20 @@ int msm_enqueue(const g1_affine_t *bases, const PolyPtrs &inl, const fe_t *const
     // threads cost more than the shorter chains save (measured: +0.15 ms at 2^18, +0.5 ms at 2^21 buckets)
     // auto (2): big bucket sets whose buckets are no longer than a segment straddle two accumulate threads as a rule -- the case the
     // segmented reduction is measured faster in (2^24 .. 2^26 with c = 22); everything else takes the per-bucket kernels
-    if (segfix) {
-      // one segmented reduction over the 2 * tn partial slots, level by level (64 slots -> 2 per level) until one wavefront holds the rest
-      uint32_t N = 2 * tn; const uint32_t waves1 = ceil_div(N, 64);
-      int32_t *lv_ids; g1_xyzz29_t *lv_recs;
-      { const std::string r1 = role("msm.segfix_ids"), r2 = role("msm.segfix_recs"); const size_t cap = (size_t)2 * waves1 + (size_t)waves1 / 8 + 512;
-        CHK(ws_get(r1.c_str(), cap * 4, (void **)&lv_ids)); CHK(ws_get(r2.c_str(), cap * sizeof(g1_xyzz29_t), (void **)&lv_recs)); }
-      const int32_t *cur_ids = part_id; const g1_xyzz29_t *cur_recs = part; size_t used = 0;
-      while (N > 64) {
-        const uint32_t waves = ceil_div(N, 64);
-        hipLaunchKernelGGL(k_msm_segfix, dim3(ceil_div(N, 256)), dim3(256), 0, s, cur_ids, cur_recs, N, buckets, lv_ids + used, lv_recs + used, 0);
-        cur_ids = lv_ids + used; cur_recs = lv_recs + used; used += (size_t)2 * waves; N = 2 * waves;
-      }
-      hipLaunchKernelGGL(k_msm_segfix, dim3(1), dim3(64), 0, s, cur_ids, cur_recs, N, buckets, (int32_t *)nullptr, (g1_xyzz29_t *)nullptr, 1);
-    } else {
-    if ((uint64_t)nbuckets * 4 <= g.tail_coop_max && (g.tail_coop_mask & 1u)) hipLaunchKernelGGL((k_msm_fixup<4, 4>), dim3(ceil_div((uint64_t)nbuckets * 16, 256)), dim3(256), 0, s, offsets, nbuckets, buckets, part, part_id, seg_arg, tn, big_list, big_count, big_cap, huge_list, huge_count, huge_cap, g.fixup_serial_max, g.fixup_huge_min);
-    else if (nbuckets <= (1u << g.fixup_lanes_max_log)) hipLaunchKernelGGL((k_msm_fixup<4, 1>), dim3(ceil_div((uint64_t)nbuckets * 4, 256)), dim3(256), 0, s, offsets, nbuckets, buckets, part, part_id, seg_arg, tn, big_list, big_count, big_cap, huge_list, huge_count, huge_cap, g.fixup_serial_max, g.fixup_huge_min);
-    else hipLaunchKernelGGL((k_msm_fixup<1, 1>), dim3(ceil_div(nbuckets, 256)), dim3(256), 0, s, offsets, nbuckets, buckets, part, part_id, seg_arg, tn, big_list, big_count, big_cap, huge_list, huge_count, huge_cap, g.fixup_serial_max, g.fixup_huge_min);
-    hipLaunchKernelGGL(k_msm_fixup_big, dim3(big_cap), dim3(256), 0, s, buckets, part, part_id, big_list, big_count);
-    hipLaunchKernelGGL(k_msm_fixup_huge, dim3(huge_cap * FIXUP_SLICES), dim3(256), 0, s, part, part_id, huge_list, huge_count, huge_part, huge_cap);
-    hipLaunchKernelGGL(k_msm_fixup_huge_fold, dim3(huge_cap), dim3(64), 0, s, buckets, huge_list, huge_count, (const g1_xyzz29_t *)huge_part);
+    if (segfix) CHK(msm_segfix_levels<G1Ops>(part_id, part, tn, buckets, s, ws));
+    else {
+      // launch = threads / 256 workgroups of the per-bucket fix-up in one of its three forms
+      auto fixup = [&](auto kernel, uint64_t threads) {
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(threads, 256)), dim3(256), 0, s, offsets, nbuckets, buckets, part, part_id, seg_arg, tn, big_list, big_count, big_cap, huge_list, huge_count, huge_cap, g.fixup_serial_max, g.fixup_huge_min);
+      };
+      if ((uint64_t)nbuckets * 4 <= g.tail_coop_max && (g.tail_coop_mask & 1u)) fixup(k_msm_fixup<4, 4>, (uint64_t)nbuckets * 16);
+      else if (nbuckets <= (1u << g.fixup_lanes_max_log)) fixup(k_msm_fixup<4, 1>, (uint64_t)nbuckets * 4);
+      else fixup(k_msm_fixup<1, 1>, nbuckets);
+      hipLaunchKernelGGL(k_msm_fixup_big, dim3(big_cap), dim3(256), 0, s, buckets, part, part_id, big_list, big_count);
+      hipLaunchKernelGGL(k_msm_fixup_huge, dim3(huge_cap * FIXUP_SLICES), dim3(256), 0, s, part, part_id, huge_list, huge_count, huge_part, huge_cap);
+      hipLaunchKernelGGL(k_msm_fixup_huge_fold, dim3(huge_cap), dim3(64), 0, s, buckets, huge_list, huge_count, (const g1_xyzz29_t *)huge_part);
     }
-    if (!skip_tail) CHK(msm_reduce_tail(sh, M, buckets, out_dev, normalise, s, sfx));
+    if (!skip_tail) CHK(msm_reduce_tail<G1Ops>(sh, M, buckets, out_dev, normalise, s, ws));
   }
   if (piped) HIPCHK(hipEventRecord(slot.red_done, st.c));
   slot.used = true;
@@ -313,26 +357,36 @@ uint32_t msm_chunks_for(uint32_t M, uint64_t n) {
   return k;
 }
 
+// The M results of a finished schedule go to the caller: into device memory in stream order (the call returns without waiting), or into
+// host memory once the stream has drained.  what / count: the trace line's "<what>=<count>".
+int msm_deliver(CallTrace &tr, const g1_jac_t *out_dev, uint32_t M, void *out_host, void *out_dev_user, hipStream_t s, const char *what, uint32_t count) {
+  if (out_dev_user) {   // asynchronous: the caller's stream order protects the result
+    HIPCHK(hipMemcpyAsync(out_dev_user, out_dev, (size_t)M * sizeof(g1_jac_t), hipMemcpyDeviceToDevice, s));
+    if (g.profiling) resolve_spans();
+    tr.done(" (device result)");
+    return MI355_OK;
+  }
+  HIPCHK(hipMemcpyAsync(out_host, out_dev, (size_t)M * sizeof(g1_jac_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  resolve_spans();
+  { char buf[64]; snprintf(buf, sizeof buf, " %s=%u c=%d W=%d", what, count, g.last_c, g.last_w); tr.done(buf); }
+  return MI355_OK;
+}
+
 // out_dev_user: the M results stay in device memory and the call returns without waiting for the stream.  accumulate_plan: second half of
 // a split batch (mi355_msm_last_plan reports the entries of the whole batch).
-int msm_batch_impl(const g1_affine_t *bases, const fe_t *const *polys_host, uint32_t M, uint64_t n, void *out_host, const PreTable *pre, void *out_dev_user, bool accumulate_plan) {
+int msm_batch_impl(const g1_affine_t *bases, const fe_t *const *polys_host, uint32_t M, uint64_t n, void *out_host, const PreTable *pre, void *out_dev_user = nullptr, bool accumulate_plan = false) {
   if (M == 0) return MI355_OK;
   if (n == 0) {
     if (out_dev_user) { HIPCHK(hipMemsetAsync(out_dev_user, 0, (size_t)M * sizeof(g1_jac_t), g.stream)); return MI355_OK; }
     memset(out_host, 0, (size_t)M * sizeof(g1_jac_t)); return MI355_OK;
   }
   if (n >= (1ull << 31)) return fail(MI355_EBADARG, "msm: n must be < 2^31");
-  if (M > 1) {
-    // a batch that would overflow the 32-bit entry index, the coarse histogram's LDS or 8 GiB of bucket records is processed as two
-    // half batches (the same shape computation as the launch code: msm_shape)
-    MsmShape sh; const int rc0 = msm_shape(n, M, pre, sh);
-    if (rc0 != MI355_OK || sh.emax > (1ull << 29) || sh.nbuckets * sizeof(g1_xyzz29_t) > (8ull << 30)) {
-      const uint32_t h = M / 2;
-      int rc = msm_batch_impl(bases, polys_host, h, n, out_host, pre, out_dev_user, accumulate_plan);
-      if (rc != MI355_OK) return rc;
-      return msm_batch_impl(bases, polys_host + h, M - h, n, out_host ? (char *)out_host + (size_t)h * sizeof(g1_jac_t) : nullptr, pre,
-                            out_dev_user ? (char *)out_dev_user + (size_t)h * sizeof(g1_jac_t) : nullptr, true);
-    }
+  if (M > 1 && msm_batch_must_split<G1Ops>(n, M, pre)) {   // the same shape computation as the launch code: msm_shape
+    const uint32_t h = M / 2;
+    CHK(msm_batch_impl(bases, polys_host, h, n, out_host, pre, out_dev_user, accumulate_plan));
+    return msm_batch_impl(bases, polys_host + h, M - h, n, out_host ? (char *)out_host + (size_t)h * sizeof(g1_jac_t) : nullptr, pre,
+                          out_dev_user ? (char *)out_dev_user + (size_t)h * sizeof(g1_jac_t) : nullptr, true);
   }
   const uint32_t K = msm_chunks_for(M, n);
   if (!accumulate_plan) { g.last_entries = 0; g.last_host_slices = 1; }
@@ -341,16 +395,9 @@ int msm_batch_impl(const g1_affine_t *bases, const fe_t *const *polys_host, uint
   CHK(ws_get("msm.out", (size_t)(K + 1) * M * sizeof(g1_jac_t), (void **)&out_dev));
   hipStream_t s = g.stream;
   Scope total("msm_total", s);
-  PolyPtrs inl; for (int i = 0; i < 8; i++) inl.p[i] = nullptr;
+  PolyPtrs inl{};
   if (K == 1) {
-    if (M <= 8) for (uint32_t m = 0; m < M; m++) inl.p[m] = polys_host[m];
-    else {
-      // the pointer array is staged through a buffer the library owns (the caller's array may be a temporary)
-      CHK(ws_get("msm.polys", (size_t)M * sizeof(void *), (void **)&polys_dev));
-      g.polys_stage.assign(polys_host, polys_host + M);
-      HIPCHK(hipMemcpyAsync(polys_dev, g.polys_stage.data(), (size_t)M * sizeof(void *), hipMemcpyHostToDevice, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
+    CHK(msm_stage_polys(polys_host, M, Roles{G1Ops::ROLE, ""}, s, inl, polys_dev));
     MsmStreams st{s, s, s};
     CHK(msm_enqueue(bases, inl, polys_dev, M, n, out_dev, pre, g.msm_slot[0], st, t_opts.normalise));
   } else {
@@ -361,8 +408,7 @@ int msm_batch_impl(const g1_affine_t *bases, const fe_t *const *polys_host, uint
     HIPCHK(hipStreamWaitEvent(g.aux_stream[0], g.ev_fork, 0)); HIPCHK(hipStreamWaitEvent(g.aux_stream[1], g.ev_fork, 0));
     MsmStreams st{g.aux_stream[0], s, g.aux_stream[1]};
     for (uint32_t k = 0; k < K; k++) {
-      PreTable pk; const PreTable *pp = nullptr;
-      if (pre) { pk = *pre; if (pk.table) pk.table += lo[k]; pp = &pk; }
+      PreTable pk; const PreTable *pp = pre_advance(pre, lo[k], pk);
       inl.p[0] = polys_host[0] + lo[k];   // pipelined MSMs are single-polynomial (msm_chunks_for)
       CHK(msm_enqueue(bases + lo[k], inl, nullptr, M, lo[k + 1] - lo[k], out_dev + (size_t)(k + 1) * M, pp, g.msm_slot[k & 1], st, false));
     }
@@ -374,17 +420,7 @@ int msm_batch_impl(const g1_affine_t *bases, const fe_t *const *polys_host, uint
   total.close();
   g.msm_slot[0].used = g.msm_slot[1].used = false;
   g.last_chunks = (int)K;
-  if (out_dev_user) {   // asynchronous: the caller's stream order protects the result
-    HIPCHK(hipMemcpyAsync(out_dev_user, out_dev, (size_t)M * sizeof(g1_jac_t), hipMemcpyDeviceToDevice, s));
-    if (g.profiling) resolve_spans();
-    tr.done(" (device result)");
-    return MI355_OK;
-  }
-  HIPCHK(hipMemcpyAsync(out_host, out_dev, (size_t)M * sizeof(g1_jac_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  resolve_spans();
-  { char buf[64]; snprintf(buf, sizeof buf, " batch=%u c=%d W=%d", M, g.last_c, g.last_w); tr.done(buf); }
-  return MI355_OK;
+  return msm_deliver(tr, out_dev, M, out_host, out_dev_user, s, "batch", M);
 }
 
 // mi355_msm_g1_host on one device.  Big single MSMs are cut into K point-range slices: slice k + 1 crosses PCIe on the copy stream while
@@ -425,7 +461,7 @@ int msm_host_single(const g1_affine_t *bases, const fe_t *const *polys_host, uin
   Scope total("msm_total", s);
   // the staging buffer may still be read by work queued earlier on the compute stream
   HIPCHK(hipEventRecord(g.ev_fork, s)); HIPCHK(hipStreamWaitEvent(g.copy_stream, g.ev_fork, 0));
-  PolyPtrs inl; for (int i = 0; i < 8; i++) inl.p[i] = nullptr;
+  PolyPtrs inl{};
   MsmStreams st{s, s, s};
   for (uint32_t k = 0; k < K; k++) {
     const uint64_t lo = cut[k], hi = cut[k + 1];
@@ -433,8 +469,7 @@ int msm_host_single(const g1_affine_t *bases, const fe_t *const *polys_host, uin
     HIPCHK(hipMemcpyAsync(sc + lo, polys_host[0] + lo, (hi - lo) * sizeof(fe_t), hipMemcpyHostToDevice, g.copy_stream));
     HIPCHK(hipEventRecord(g.ev_copy[k & 3], g.copy_stream));
     HIPCHK(hipStreamWaitEvent(s, g.ev_copy[k & 3], 0));
-    PreTable pk; const PreTable *pp = nullptr;
-    if (pre) { pk = *pre; if (pk.table) pk.table += lo; pp = &pk; }
+    PreTable pk; const PreTable *pp = pre_advance(pre, lo, pk);
     inl.p[0] = sc + lo;
     CHK(msm_enqueue(bases + lo, inl, nullptr, 1, hi - lo, out_dev, pp, g.msm_slot[0], st, t_opts.normalise, &shape, k, K, true));
   }
@@ -443,114 +478,64 @@ int msm_host_single(const g1_affine_t *bases, const fe_t *const *polys_host, uin
   {
     Scope sc2("msm_reduce", s);
     hipLaunchKernelGGL(k_msm_bucket_fold, dim3(ceil_div(shape.nbuckets, 256)), dim3(256), 0, s, buckets, (uint32_t)shape.nbuckets, K);
-    CHK(msm_reduce_tail(shape, 1, buckets, out_dev, t_opts.normalise, s, std::string()));
+    CHK(msm_reduce_tail<G1Ops>(shape, 1, buckets, out_dev, t_opts.normalise, s, Roles{G1Ops::ROLE, ""}));
   }
   total.close();
   g.last_chunks = (int)K; g.last_host_slices = (int)K;
-  if (out_dev_user) {   // sharded MSM: the partial stays on the device, in stream order
-    HIPCHK(hipMemcpyAsync(out_dev_user, out_dev, sizeof(g1_jac_t), hipMemcpyDeviceToDevice, s));
-    if (g.profiling) resolve_spans();
-    return MI355_OK;
-  }
-  HIPCHK(hipMemcpyAsync(out_host, out_dev, sizeof(g1_jac_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  resolve_spans();
-  { char buf[64]; snprintf(buf, sizeof buf, " host slices=%u c=%d W=%d", K, g.last_c, g.last_w); tr.done(buf); }
-  return MI355_OK;
+  return msm_deliver(tr, out_dev, 1, out_host, out_dev_user, s, "host slices", K);   // sharded MSM: the partial stays on the device, in stream order
 }
 
 // ------------------------------------------------------------------------------------------------ G2 MSM
 // M MSMs over one G2 basis in device memory (already validated), scalars in device memory; out_host: M x 128 B (normalised G2Affine).
-// One device, one stream: digits + sort (msm_sort_stage, shared = 0: no window tables for G2), segmented accumulation, segmented fix-up,
-// running sums + trees, Horner.  The window size comes from the G1 cost model (msm_shape); workspace roles msm2.* hold 256-byte records.
+// One device, one stream, the pieces of the G1 pass with the G2 policy: digits + sort (msm_sort_stage, shared = 0: no window tables for
+// G2), segmented accumulation at 100 % fill, the segmented fix-up (always), the reduction tail.  The window size comes from the G1 cost
+// model (msm_shape); workspace roles msm2.* hold 256-byte records.
 static int msm_g2_impl(const g2_affine_t *bases, const fe_t *const *polys, uint32_t M, uint64_t n, void *out_host, bool accumulate_plan = false) {
   if (M == 0) return MI355_OK;
   if (n == 0) { memset(out_host, 0, (size_t)M * sizeof(g2_affine_t)); return MI355_OK; }
   if (n >= (1ull << 31)) return fail(MI355_EBADARG, "msm_g2: n must be < 2^31");
-  MsmShape sh;
-  if (M > 1) {   // a batch that overflows the entry index, the coarse histogram or 8 GiB of bucket records runs as two half batches
-    const int rc0 = msm_shape(n, M, nullptr, sh);
-    if (rc0 != MI355_OK || sh.emax > (1ull << 29) || sh.nbuckets * sizeof(g2_xyzz_t) > (8ull << 30)) {
-      const uint32_t h = M / 2;
-      CHK(msm_g2_impl(bases, polys, h, n, out_host, accumulate_plan));
-      return msm_g2_impl(bases, polys + h, M - h, n, (char *)out_host + (size_t)h * sizeof(g2_affine_t), true);
-    }
+  if (M > 1 && msm_batch_must_split<G2Ops>(n, M, nullptr)) {
+    const uint32_t h = M / 2;
+    CHK(msm_g2_impl(bases, polys, h, n, out_host, accumulate_plan));
+    return msm_g2_impl(bases, polys + h, M - h, n, (char *)out_host + (size_t)h * sizeof(g2_affine_t), true);
   }
-  CHK(msm_shape(n, M, nullptr, sh));
+  MsmShape sh; CHK(msm_shape(n, M, nullptr, sh));
   if (!accumulate_plan) { g.last_entries = 0; g.last_host_slices = 1; }
   CallTrace tr("msm_g2", (uint64_t)M * n, 160.0);
   hipStream_t s = g.stream;
   Scope total("msm_g2_total", s);
-  MsmPlan P; P.n = (uint32_t)n; P.batch = M; P.c = sh.c; P.windows = sh.W; P.nb = 1u << (P.c - 1);
-  const uint64_t emax = sh.emax;
-  const uint64_t want_threads = (uint64_t)g.prop.multiProcessorCount * 256 * g.seg_factor;
-  uint64_t seg = (emax + want_threads - 1) / want_threads; if (seg < 16) seg = 16; if (seg > 4096) seg = 4096;
-  P.seg = (uint32_t)seg;
-  const uint32_t nbuckets = (uint32_t)sh.nbuckets, acc_blocks = ceil_div(ceil_div(emax, seg), 256), tn = acc_blocks * 256;
-  PolyPtrs inl; for (int i = 0; i < 8; i++) inl.p[i] = nullptr;
-  const fe_t **polys_dev = nullptr;
-  if (M <= 8) for (uint32_t m = 0; m < M; m++) inl.p[m] = polys[m];
-  else {   // the pointer array is staged through a buffer the library owns (the caller's array may be a temporary)
-    CHK(ws_get("msm2.polys", (size_t)M * sizeof(void *), (void **)&polys_dev));
-    g.polys_stage.assign(polys, polys + M);
-    HIPCHK(hipMemcpyAsync(polys_dev, g.polys_stage.data(), (size_t)M * sizeof(void *), hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-  }
+  const Roles ws{G2Ops::ROLE, ""};
+  const AccPlan ap = msm_acc_plan(sh.emax);
+  const MsmPlan P = msm_plan(sh, n, M, ap.seg);
+  const uint32_t nbuckets = (uint32_t)sh.nbuckets;
+  PolyPtrs inl{}; const fe_t **polys_dev = nullptr;
+  CHK(msm_stage_polys(polys, M, ws, s, inl, polys_dev));
   uint32_t *offsets, *sorted; g2_xyzz_t *buckets, *part; int32_t *part_id;
-  CHK(ws_get("msm2.offsets", ((size_t)nbuckets + 1) * 4, (void **)&offsets));
-  CHK(ws_get("msm2.sorted", emax * 4, (void **)&sorted));
-  CHK(ws_get("msm2.buckets", (size_t)nbuckets * sizeof(g2_xyzz_t), (void **)&buckets));
-  CHK(ws_get("msm2.part", (size_t)tn * 2 * sizeof(g2_xyzz_t), (void **)&part));
-  CHK(ws_get("msm2.part_id", (size_t)tn * 2 * 4, (void **)&part_id));
+  CHK(ws.get("offsets", ((size_t)nbuckets + 1) * 4, offsets));
+  CHK(ws.get("sorted", sh.emax * 4, sorted));
+  CHK(ws.get("buckets", (size_t)nbuckets * sizeof(g2_xyzz_t), buckets));
+  CHK(ws.get("part", (size_t)ap.tn * 2 * sizeof(g2_xyzz_t), part));
+  CHK(ws.get("part_id", (size_t)ap.tn * 2 * 4, part_id));
   CHK(msm_sort_stage(inl, polys_dev, M, n, sh, P, offsets, sorted, s, true));
   {
     Scope sc("msm_g2_accumulate", s);
     HIPCHK(hipMemsetAsync(buckets, 0, (size_t)nbuckets * sizeof(g2_xyzz_t), s));   // all zero = the XYZZ identity: empty buckets
-    hipLaunchKernelGGL(k_msm_g2_accumulate, dim3(acc_blocks), dim3(256), 0, s, bases, sorted, offsets, nbuckets, buckets, part, part_id, P.seg, std::min(g.seg_min, P.seg));
+    hipLaunchKernelGGL(k_msm_g2_accumulate, dim3(ap.blocks), dim3(256), 0, s, bases, sorted, offsets, nbuckets, buckets, part, part_id, msm_seg_arg(P.seg, 100));
   }
   {
     Scope sc("msm_g2_fixup", s);
-    uint32_t N = 2 * tn; const uint32_t waves1 = ceil_div(N, 64);
-    const size_t cap = (size_t)2 * waves1 + (size_t)waves1 / 8 + 512;
-    int32_t *lv_ids; g2_xyzz_t *lv_recs;
-    CHK(ws_get("msm2.segfix_ids", cap * 4, (void **)&lv_ids)); CHK(ws_get("msm2.segfix_recs", cap * sizeof(g2_xyzz_t), (void **)&lv_recs));
-    const int32_t *cur_ids = part_id; const g2_xyzz_t *cur_recs = part; size_t used = 0;
-    while (N > 64) {
-      const uint32_t waves = ceil_div(N, 64);
-      hipLaunchKernelGGL(k_msm_g2_segfix, dim3(ceil_div(N, 256)), dim3(256), 0, s, cur_ids, cur_recs, N, buckets, lv_ids + used, lv_recs + used, 0);
-      cur_ids = lv_ids + used; cur_recs = lv_recs + used; used += (size_t)2 * waves; N = 2 * waves;
-    }
-    hipLaunchKernelGGL(k_msm_g2_segfix, dim3(1), dim3(64), 0, s, cur_ids, cur_recs, N, buckets, (int32_t *)nullptr, (g2_xyzz_t *)nullptr, 1);
+    CHK(msm_segfix_levels<G2Ops>(part_id, part, ap.tn, buckets, s, ws));
   }
-  g2_affine_t *out_dev; CHK(ws_get("msm2.out", (size_t)M * sizeof(g2_affine_t), (void **)&out_dev));
+  g2_affine_t *out_dev; CHK(ws.get("out", (size_t)M * sizeof(g2_affine_t), out_dev));
   {
     Scope sc("msm_g2_reduce", s);
-    const uint32_t nb = P.nb, sets = M * P.windows;
-    uint32_t chunk = 64; while (chunk > nb) chunk >>= 1;   // running-sum chains as msm_reduce_tail cuts them
-    while (chunk > g.reduce_min_chunk && (uint64_t)(nb / chunk) * sets < g.reduce_chains) chunk >>= 1;
-    const uint32_t chunks_per_set = nb / chunk, nchunks = chunks_per_set * sets;
-    g2_xyzz_t *chunk_out, *tree_a, *tree_b, *window_sums;
-    CHK(ws_get("msm2.chunk_out", (size_t)nchunks * sizeof(g2_xyzz_t), (void **)&chunk_out));
-    { const size_t lvl = (size_t)ceil_div(chunks_per_set, 256 * TREE_PER_THREAD) * sets + 1;
-      CHK(ws_get("msm2.tree_a", lvl * sizeof(g2_xyzz_t), (void **)&tree_a)); CHK(ws_get("msm2.tree_b", lvl * sizeof(g2_xyzz_t), (void **)&tree_b)); }
-    CHK(ws_get("msm2.window_sums", (size_t)sets * sizeof(g2_xyzz_t), (void **)&window_sums));
-    hipLaunchKernelGGL(k_msm_g2_bucket_reduce, dim3(ceil_div(nchunks, 128)), dim3(128), 0, s, (const g2_xyzz_t *)buckets, chunk_out, nb, sets, chunk);
-    const g2_xyzz_t *cur = chunk_out; uint32_t cnt = chunks_per_set; g2_xyzz_t *bufs[2] = {tree_a, tree_b}; int which = 0;
-    while (true) {
-      const uint32_t outn = ceil_div(cnt, 256 * TREE_PER_THREAD);
-      g2_xyzz_t *dst = outn == 1 ? window_sums : bufs[which];
-      hipLaunchKernelGGL(k_msm_g2_tree_sum, dim3(outn, sets), dim3(256), 0, s, cur, cnt, dst, outn);
-      if (outn == 1) break;
-      cur = dst; cnt = outn; which ^= 1;
-    }
-    hipLaunchKernelGGL(k_msm_g2_final, dim3(M), dim3(64), 0, s, (const g2_xyzz_t *)window_sums, P.windows, P.c, out_dev);
+    CHK(msm_reduce_tail<G2Ops>(sh, M, buckets, out_dev, true, s, ws));
   }
-  HIPCHK(hipGetLastError());
   total.close();
   HIPCHK(hipMemcpyAsync(out_host, out_dev, (size_t)M * sizeof(g2_affine_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   resolve_spans();
-  g.last_c = (int)P.c; g.last_w = (int)P.windows; g.last_entries += emax; g.last_shared = false; g.last_chunks = 1;
+  g.last_c = (int)P.c; g.last_w = (int)P.windows; g.last_entries += sh.emax; g.last_shared = false; g.last_chunks = 1;
   { char buf[64]; snprintf(buf, sizeof buf, " batch=%u c=%d W=%d", M, g.last_c, g.last_w); tr.done(buf); }
   return MI355_OK;
 }
@@ -780,8 +765,7 @@ enum ScalarLoc { SCALARS_HOST = 0, SCALARS_DEV = 1 };
 // its own host thread (copies from pageable memory block the issuing thread, so one thread per device keeps the PCIe links busy in parallel);
 // the M x 96-byte partials are exchanged with ONE ncclAllGather per device (grouped) and folded + normalised on the primary device.
 // polys: M pointers to n scalars each, host memory or device memory of any bound device.
-static int msm_multi(const std::vector<Piece> &pieces, const fe_t *const *polys, ScalarLoc loc, uint32_t M, uint64_t n, void *out_host) {
-  (void)n;
+static int msm_multi(const std::vector<Piece> &pieces, const fe_t *const *polys, ScalarLoc loc, uint32_t M, void *out_host) {
   const int D = g_ndev;
   const MsmOpts opts = t_opts;
   std::vector<int> rcs(D, MI355_OK); std::vector<std::string> errs(D);
@@ -870,7 +854,7 @@ static bool single_device_call(const std::vector<Piece> &pieces) { return pieces
 static int msm_host_dispatch(uint64_t srs_handle, uint64_t base_offset, const void *const *scalars_host, uint32_t M, uint64_t n, void *out_g1_host) {
   std::vector<Piece> pieces; CHK(srs_pieces(srs_handle, base_offset, n, pieces));
   if (M == 0 || n == 0) { if (M) memset(out_g1_host, 0, (size_t)M * sizeof(g1_jac_t)); return MI355_OK; }
-  if (!single_device_call(pieces)) return msm_multi(pieces, (const fe_t *const *)scalars_host, SCALARS_HOST, M, n, out_g1_host);
+  if (!single_device_call(pieces)) return msm_multi(pieces, (const fe_t *const *)scalars_host, SCALARS_HOST, M, out_g1_host);
   const Piece &p = pieces[0];
   g_last_devices = 1; g_last_exchange = "none";
   // staged in groups of at most 4 GiB of scalars
@@ -884,7 +868,7 @@ static int msm_host_dispatch(uint64_t srs_handle, uint64_t base_offset, const vo
 static int msm_dev_dispatch(uint64_t srs_handle, uint64_t base_offset, const void *const *scalars_dev, uint32_t M, uint64_t n, void *out_g1_host) {
   std::vector<Piece> pieces; CHK(srs_pieces(srs_handle, base_offset, n, pieces));
   if (M == 0 || n == 0) { if (M) memset(out_g1_host, 0, (size_t)M * sizeof(g1_jac_t)); return MI355_OK; }
-  if (!single_device_call(pieces)) return msm_multi(pieces, (const fe_t *const *)scalars_dev, SCALARS_DEV, M, n, out_g1_host);
+  if (!single_device_call(pieces)) return msm_multi(pieces, (const fe_t *const *)scalars_dev, SCALARS_DEV, M, out_g1_host);
   g_last_devices = 1; g_last_exchange = "none";
   // Every scalar block is marked as used by queued work (slot_of's `touch`), with one device as with several: an upload into a block whose only
   // use since mi355_buf_alloc was as an MSM input must wait for the compute stream, not take the "fresh block" path.
@@ -989,7 +973,8 @@ int mi355_msm_g1_adhoc_host(const void *bases_host, const void *scalars_host, ui
     HIPCHK(hipMemcpyAsync(bs, bases_host, n * sizeof(g1_affine_t), hipMemcpyHostToDevice, g.stream));
   }
   g_last_devices = 1; g_last_exchange = "none";
-  return msm_dev_impl(bs, sc, n, out_g1_host);
+  const fe_t *poly = sc;
+  return msm_batch_impl(bs, &poly, 1, n, out_g1_host, nullptr);
   });
 }
 int mi355_g1_sum_host(const void *pts_host, uint64_t n, void *out_g1_host) {

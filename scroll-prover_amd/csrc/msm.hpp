@@ -7,17 +7,23 @@
 //   1 k_msm_digits      scalars (Montgomery) -> canonical -> signed c-bit digits d in [-2^(c-1), 2^(c-1)], digit plane [w][i]
 //   2 k_sort_l1_* / k_sort_l2_*   two-level counting sort of (window, bucket) keys: LDS histograms + LDS-staged coalesced
 //                       stores, one global atomic per (tile, non-empty bin); exclusive scans give the bucket offsets
-//   3 k_msm_accumulate  SEGMENTED bucket accumulation: thread t owns entries [t*L, (t+1)*L) of the sorted list whatever
+//   3 k_msm_accumulate  SEGMENTED bucket accumulation (msm_segment_walk): thread t owns entries [t*L, (t+1)*L) of the sorted list whatever
 //                       bucket boundaries fall inside, keeps a 9x29-bit XYZZ accumulator in registers, gathers affine
 //                       bases (64 B each) and does mixed additions.  Perfectly load-balanced for any scalar
 //                       distribution (witness columns are mostly 0/1/small values).
-//   4 k_msm_fixup(_big) buckets that straddle thread boundaries: sum their partials (one lane, or a workgroup for giant ones)
-//   5 k_msm_bucket_reduce / k_msm_tree_sum29   sum_b (b+1) * B[b] by short chunked running sums, then multi-block
+//   4 k_msm_fixup(_big) buckets that straddle thread boundaries: sum their partials (one lane, or a workgroup for giant ones);
+//     k_msm_segfix      the same as one segmented reduction by key over the partial records
+//   5 k_msm_bucket_reduce / k_msm_tree_sum   sum_b (b+1) * B[b] by short chunked running sums, then multi-block
 //                       wavefront-shuffle + LDS trees
-//   6 k_msm_final29     Horner over windows (none with window tables), normalise to (x, y, 1) with a one-lane Euclidean inverse
+//   6 k_msm_final       Horner over windows (none with window tables), normalise to (x, y, 1) with a one-lane Euclidean inverse
+//
+// Steps 3-6 are group-agnostic: the walk, k_msm_segfix and the tail kernels are templates over a point-operations policy (record type,
+// load / store / shuffle, addition and doubling, identity, result emission).  G1Ops below is G1 on the 29-bit field (g1_xyzz29_add / _dbl,
+// with the quad-cooperative form Q = 4 for the latency-bound tail); G2Ops (msm_g2.hpp) is the twist.  The per-bucket fix-up kernels and
+// k_msm_bucket_fold are G1 only.
 //
 // A batch of M polynomials over one basis (mi355_msm_g1_batch_*) runs the same kernels once with (polynomial m, window w) as
-// window m * W + w: grid.y = m in the digits kernel, a bucket set per polynomial, M workgroups in k_msm_final29.  Steps 4-6 run on the 29-bit field as well (g1_xyzz29_add / _dbl).
+// window m * W + w: grid.y = m in the digits kernel, a bucket set per polynomial, M workgroups in k_msm_final.
 //
 // Algorithmic HBM bytes: 96 B per (scalar, point) pair.  The accumulation is VALU-integer bound
 // (10 field multiplications = ~1650 v_mad_u64_u32 + ~700 other instructions per mixed addition), see DESIGN.md section 4.
@@ -68,6 +74,19 @@ __device__ __forceinline__ g1_xyzz29_t load_xyzz29(const g1_xyzz29_t *p) {
 #pragma unroll
   for (int i = 0; i < 9; i++) { const uint4 a = q[i]; w[4 * i] = a.x; w[4 * i + 1] = a.y; w[4 * i + 2] = a.z; w[4 * i + 3] = a.w; }
   return v;
+}
+
+__device__ __forceinline__ g1_xyzz29_t shfl_down_xyzz29(const g1_xyzz29_t &v, uint32_t o) {
+  g1_xyzz29_t r; const uint32_t *s = reinterpret_cast<const uint32_t *>(&v); uint32_t *d = reinterpret_cast<uint32_t *>(&r);
+#pragma unroll
+  for (int i = 0; i < 36; i++) d[i] = __shfl_down(s[i], o);
+  return r;
+}
+__device__ __forceinline__ g1_xyzz29_t shfl_xor_xyzz29(const g1_xyzz29_t &v, uint32_t o) {
+  g1_xyzz29_t r; const uint32_t *s = reinterpret_cast<const uint32_t *>(&v); uint32_t *d = reinterpret_cast<uint32_t *>(&r);
+#pragma unroll
+  for (int i = 0; i < 36; i++) d[i] = __shfl_xor(s[i], o);
+  return r;
 }
 
 // ---- quad-cooperative point addition / doubling for the latency-bound reduction tail (fix-up of small bucket sets, running sums, trees,
@@ -145,6 +164,31 @@ __device__ __forceinline__ void g1_xyzz29_add_q4(g1_xyzz29_t &acc, const g1_xyzz
 // Q = 1: one lane per logical thread (the throughput form); Q = 4: a quad per logical thread (the latency form)
 template <int Q> __device__ __forceinline__ void g1_vadd(g1_xyzz29_t &acc, const g1_xyzz29_t &o) { if (Q == 4) g1_xyzz29_add_q4(acc, o); else g1_xyzz29_add(acc, o); }
 template <int Q> __device__ __forceinline__ g1_xyzz29_t g1_vdbl(const g1_xyzz29_t &a) { return Q == 4 ? g1_xyzz29_dbl_q4(a) : g1_xyzz29_dbl(a); }
+
+__device__ __forceinline__ void msm_emit_result(const g1_xyzz_t &acc, g1_jac_t *out, int normalise) {
+  if (normalise) { *out = g1_xyzz_to_jac_normalised(acc); return; }
+  // un-normalised Jacobian representative (X ZZ^2, Y ZZZ^2, ZZZ): skips the inversion; used for the per-GPU partial sums, which are
+  // folded (and normalised once) by k_g1_sum
+  g1_jac_t r;
+  if (g1_xyzz_is_identity(acc)) { r.x = Fq::zero(); r.y = Fq::zero(); r.z = Fq::zero(); }
+  else { r.x = fq_mul_ps(acc.x, fq_sqr_ps(acc.zz)); r.y = fq_mul_ps(acc.y, fq_sqr_ps(acc.zzz)); r.z = acc.zzz; }
+  *out = r;
+}
+
+// ---- point-operations policy: what the segment walk, the segmented fix-up and the reduction tail (running sums, trees, Horner) need to
+// know about a group.  The kernels below are written once against it; msm_g2.hpp holds the policy of the twist.
+struct G1Ops {   // G1 on the 29-bit field: 144-byte XYZZ records, one-lane and quad forms of the addition
+  using rec_t = g1_xyzz29_t; using out_t = g1_jac_t;
+  static constexpr bool QUAD = true;
+  static constexpr const char *ROLE = "msm.";   // prefix of the workspace roles
+  static __device__ __forceinline__ rec_t identity() { return g1_xyzz29_identity(); }
+  static __device__ __forceinline__ rec_t load(const rec_t *p) { return load_xyzz29(p); }
+  static __device__ __forceinline__ void store(rec_t *p, const rec_t &v) { store_xyzz29(p, v); }
+  template <int Q> static __device__ __forceinline__ void add(rec_t &acc, const rec_t &o) { g1_vadd<Q>(acc, o); }
+  template <int Q> static __device__ __forceinline__ rec_t dbl(const rec_t &a) { return g1_vdbl<Q>(a); }
+  static __device__ __forceinline__ rec_t shfl_down(const rec_t &v, uint32_t o) { return shfl_down_xyzz29(v, o); }
+  static __device__ __forceinline__ void emit(const rec_t &acc, out_t *out, int normalise) { msm_emit_result(g1_xyzz29_to_sat(acc), out, normalise); }
+};
 
 // ---- 1. digits.  Plane layout enc[w * n + i]: 0 for a zero digit, else |d| (1 .. 2^(c-1)) with bit 31 = sign.
 // up to 8 polynomial pointers travel as a kernel argument (copied at launch: no staging copy, nothing for an asynchronous caller to keep
@@ -428,18 +472,23 @@ template <int EPT> __global__ void __launch_bounds__(1024) k_sort_l2_scatter_spl
 // The segment is chosen so that the entries fill ~40 % of the launched threads (about two rounds of resident wavefronts: enough to keep
 // every SIMD at its three waves, while every further thread only adds partial sums for the fix-up to merge -- calibrated on witness-like,
 // byte-valued and all-ones columns at 2^26, profiles/r02b_segment_calibration.log).
-__device__ __forceinline__ uint32_t msm_seg_eff(uint32_t total, uint32_t threads, uint32_t seg_max, uint32_t seg_min, uint32_t fill_pct) {
+// The host packs (worst-case segment <= 4096) | minimum << 13 | (fill percentage / 2) << 26 into one kernel argument; this is its only decoder.
+__device__ __forceinline__ uint32_t msm_seg_eff(uint32_t total, uint32_t threads, uint32_t seg_arg) {
+  const uint32_t seg_max = seg_arg & 0x1fffu, seg_min = (seg_arg >> 13) & 0x1fffu, fill_pct = (seg_arg >> 26) * 2;
   const uint64_t target = ((uint64_t)threads * (fill_pct > 100u ? 100u : fill_pct) + 99) / 100;   // never more than the launched threads: threads * segment must cover the entries
   uint32_t sg = (uint32_t)(((uint64_t)total + target - 1) / (target ? target : 1));
   sg = sg < seg_min ? seg_min : sg;
   return sg > seg_max ? seg_max : sg;
 }
-template <int VARIANT> __global__ void __launch_bounds__(256) k_msm_accumulate(const g1_affine_t *__restrict__ bases, const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ offsets,
-                                                        uint32_t nbuckets, g1_xyzz29_t *__restrict__ bucket_sums, g1_xyzz29_t *__restrict__ part, int32_t *__restrict__ part_id, uint32_t seg_max,
-                                                        uint32_t nshift, uint64_t row_stride, uint32_t gather_mask) {
+// The walk of accumulate thread t over its entries [t * seg, (t + 1) * seg) of the sorted list, written once for both groups.  G: the
+// point-operations policy (the accumulator is a G::rec_t in registers, flushed as a raw record).  B: how an entry becomes a base --
+// B::base_t, B.load(entry) and B.madd(acc, base, negative digit).  t / threads: this thread and the launch size, read by the kernel itself (the
+// compiler folds blockDim to the uniform workgroup size only where a kernel reads it).
+template <class G, class B> __device__ __forceinline__ void msm_segment_walk(const B &bases, const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ offsets, uint32_t nbuckets,
+                                                                              typename G::rec_t *__restrict__ bucket_sums, typename G::rec_t *__restrict__ part, int32_t *__restrict__ part_id, uint32_t seg_arg,
+                                                                              uint32_t t, uint32_t threads) {
   const uint32_t total = offsets[nbuckets];
-  const uint32_t seg = msm_seg_eff(total, gridDim.x * blockDim.x, seg_max & 0x1fffu, (seg_max >> 13) & 0x1fffu, (seg_max >> 26) * 2);   // worst-case segment | minimum << 13 | (fill % / 2) << 26
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t seg = msm_seg_eff(total, threads, seg_arg);
   const uint64_t start64 = (uint64_t)t * seg;
   if (start64 >= total) { part_id[2 * t] = -1; part_id[2 * t + 1] = -1; return; }
   const uint32_t start = (uint32_t)start64, end = (uint32_t)min((uint64_t)total, start64 + seg);
@@ -447,40 +496,21 @@ template <int VARIANT> __global__ void __launch_bounds__(256) k_msm_accumulate(c
   uint32_t lo = 0, hi = nbuckets;  // invariant offsets[lo] <= start < offsets[hi]
   while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (offsets[mid] <= start) lo = mid; else hi = mid; }
   uint32_t b = lo, b_start = offsets[b], b_end = offsets[b + 1];
-  uint32_t next_end = (b + 2 <= nbuckets) ? offsets[b + 2] : b_end;   // end of bucket b+1, fetched one bucket ahead so that a crossing does not stall on a load
   int32_t id_first = -1, id_last = -1;
-  // the accumulator lives in the 9 x 29-bit unsaturated field (g1_29.hpp): one v_mad_u64_u32 per limb product, no carry chain;
-  // it is flushed as a raw 144-byte record
-  g1_xyzz29_t acc = g1_xyzz29_identity();
-  // row_stride != 0: entry payload (w << nshift) | i names row w of the precomputed table T[w][.] = 2^(c w) P (rows row_stride points apart)
-  auto base_of = [&](uint32_t e) -> const g1_affine_t * {
-    const uint32_t gi = e & gather_mask;   // gather_mask = 0x7fffffff (index bits); smaller only in timing experiments
-    if (row_stride == 0) return &bases[gi];
-    const uint32_t w = gi >> nshift;       // entry payload = (table row << nshift) | point
-    return &bases[(uint64_t)w * row_stride + (gi & ((1u << nshift) - 1))];
-  };
-  auto gather = [&](uint32_t e) -> g1_affine_t { return load_affine(base_of(e)); };
-  // software pipeline: the gather of entry pos+1 (index, then 64-byte base) is issued before the ~10 field multiplications of entry pos.
-  // VARIANT & 1 (A/B knob): the index stream runs one entry further ahead than the bases, so that the gather address is already in a
-  // register when the iteration starts.
+  typename G::rec_t acc = G::identity();
+  // software pipeline: the gather of entry pos+1 (index, then base) is issued before the field multiplications of entry pos
   uint32_t ent = sorted[start];
-  uint32_t ent_next = start + 1 < end ? sorted[start + 1] : 0;
-  g1_affine_t p = gather(ent);
+  uint32_t ent_next = start + 1 < end ? sorted[start + 1] : 0;   // the second index is requested before the first base (kept: the compiler does not hoist it on its own)
+  typename B::base_t p = bases.load(ent);
   for (uint32_t pos = start; pos < end; pos++) {
-    g1_affine_t p_next = p;
-    uint32_t ent_next2 = 0;
-    if (VARIANT & 1) {
-      if (pos + 1 < end) p_next = gather(ent_next);
-      if (pos + 2 < end) ent_next2 = sorted[pos + 2];
-    } else {
-      if (pos + 1 < end) { ent_next = sorted[pos + 1]; p_next = gather(ent_next); }
-    }
+    typename B::base_t p_next = p;
+    if (pos + 1 < end) { ent_next = sorted[pos + 1]; p_next = bases.load(ent_next); }
     if (pos >= b_end) {
       // leave bucket b: it ends inside this thread's range
-      if (b_start >= start) store_xyzz29(&bucket_sums[b], acc);                           // began here too: sole owner
-      else { store_xyzz29(&part[2 * (uint64_t)t], acc); id_first = (int32_t)b; }          // began in an earlier thread
-      acc = g1_xyzz29_identity();
-      b++; b_start = b_end; b_end = (VARIANT & 2) ? next_end : offsets[b + 1];
+      if (b_start >= start) G::store(&bucket_sums[b], acc);                           // began here too: sole owner
+      else { G::store(&part[2 * (uint64_t)t], acc); id_first = (int32_t)b; }          // began in an earlier thread
+      acc = G::identity();
+      b++; b_start = b_end; b_end = offsets[b + 1];
       if (pos >= b_end) {
         // a run of empty buckets follows (low-entropy scalars: an all-equal column leaves ~2^21 / W empty buckets between two giant
         // ones, and walking them one dependent load at a time kept a handful of lanes busy for 35 ms): binary search for the bucket
@@ -489,16 +519,35 @@ template <int VARIANT> __global__ void __launch_bounds__(256) k_msm_accumulate(c
         while (h2 - l2 > 1) { const uint32_t mid = (l2 + h2) >> 1; if (offsets[mid] <= pos) l2 = mid; else h2 = mid; }
         b = l2; b_start = offsets[b]; b_end = offsets[b + 1];
       }
-      if (VARIANT & 2) next_end = (b + 2 <= nbuckets) ? offsets[b + 2] : b_end;
     }
-    g1_xyzz29_madd<true, (VARIANT & 4) != 0>(acc, p, (ent >> 31) != 0);
-    ent = ent_next; if (VARIANT & 1) ent_next = ent_next2; p = p_next;
+    bases.madd(acc, p, (ent >> 31) != 0);
+    ent = ent_next; p = p_next;
   }
   // bucket b is still open at `end`
-  if (b_start >= start && b_end <= end) store_xyzz29(&bucket_sums[b], acc);
-  else if (b_start < start) { store_xyzz29(&part[2 * (uint64_t)t], acc); id_first = (int32_t)b; }   // spans the whole segment or just its head
-  else { store_xyzz29(&part[2 * (uint64_t)t + 1], acc); id_last = (int32_t)b; }                        // began here, continues in the next thread
+  if (b_start >= start && b_end <= end) G::store(&bucket_sums[b], acc);
+  else if (b_start < start) { G::store(&part[2 * (uint64_t)t], acc); id_first = (int32_t)b; }   // spans the whole segment or just its head
+  else { G::store(&part[2 * (uint64_t)t + 1], acc); id_last = (int32_t)b; }                        // began here, continues in the next thread
   part_id[2 * t] = id_first; part_id[2 * t + 1] = id_last;
+}
+// G1 bases: 64-byte affine points; with window tables (row_stride != 0) the entry payload (w << nshift) | i names row w of the precomputed
+// table T[w][.] = 2^(c w) P (rows row_stride points apart).  The accumulator lives in the 9 x 29-bit unsaturated field (g1_29.hpp): one
+// v_mad_u64_u32 per limb product, chained explicitly (fp29.hpp mac_*), no carry chain.
+struct G1Bases {
+  using base_t = g1_affine_t;
+  const g1_affine_t *__restrict__ bases; uint32_t nshift; uint64_t row_stride;
+  __device__ __forceinline__ const g1_affine_t *base_of(uint32_t e) const {
+    const uint32_t gi = e & 0x7fffffffu;   // index bits
+    if (row_stride == 0) return &bases[gi];
+    const uint32_t w = gi >> nshift;       // entry payload = (table row << nshift) | point
+    return &bases[(uint64_t)w * row_stride + (gi & ((1u << nshift) - 1))];
+  }
+  __device__ __forceinline__ g1_affine_t load(uint32_t e) const { return load_affine(base_of(e)); }
+  __device__ __forceinline__ void madd(g1_xyzz29_t &acc, const g1_affine_t &p, bool neg) const { g1_xyzz29_madd<true, true>(acc, p, neg); }
+};
+__global__ void __launch_bounds__(256) k_msm_accumulate(const g1_affine_t *__restrict__ bases, const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ offsets,
+                                                        uint32_t nbuckets, g1_xyzz29_t *__restrict__ bucket_sums, g1_xyzz29_t *__restrict__ part, int32_t *__restrict__ part_id, uint32_t seg_arg,
+                                                        uint32_t nshift, uint64_t row_stride) {
+  msm_segment_walk<G1Ops>(G1Bases{bases, nshift, row_stride}, sorted, offsets, nbuckets, bucket_sums, part, part_id, seg_arg, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // ---- 5. fix-up of buckets that straddle thread boundaries.  Small spans are summed by one lane; a bucket that spans more than
@@ -511,30 +560,18 @@ template <int Q = 1> __device__ __forceinline__ void fixup_take29(g1_xyzz29_t &a
   if (part_id[2 * t] == (int32_t)b) g1_vadd<Q>(acc, load_xyzz29(&part[2 * (uint64_t)t]));
   else if (part_id[2 * t + 1] == (int32_t)b) g1_vadd<Q>(acc, load_xyzz29(&part[2 * (uint64_t)t + 1]));
 }
-__device__ __forceinline__ g1_xyzz29_t shfl_down_xyzz29(const g1_xyzz29_t &v, uint32_t o) {
-  g1_xyzz29_t r; const uint32_t *s = reinterpret_cast<const uint32_t *>(&v); uint32_t *d = reinterpret_cast<uint32_t *>(&r);
-#pragma unroll
-  for (int i = 0; i < 36; i++) d[i] = __shfl_down(s[i], o);
-  return r;
-}
-__device__ __forceinline__ g1_xyzz29_t shfl_xor_xyzz29(const g1_xyzz29_t &v, uint32_t o) {
-  g1_xyzz29_t r; const uint32_t *s = reinterpret_cast<const uint32_t *>(&v); uint32_t *d = reinterpret_cast<uint32_t *>(&r);
-#pragma unroll
-  for (int i = 0; i < 36; i++) d[i] = __shfl_xor(s[i], o);
-  return r;
-}
 // FIXUP_LANES lanes per bucket: a bucket of a mid-size MSM straddles ~15 accumulate threads (2^20 pairs: 240 entries per bucket, 16 per
 // thread), and one lane summing them serially left the kernel at one wavefront per SIMD on a 15-addition chain (184 us of a 2 ms MSM).
 // Each lane of the group sums every FIXUP_LANES-th partial and two shuffle steps combine them; launch = nbuckets * FIXUP_LANES threads
 // (0.60 -> 0.45 ms of tail at 2^14 pairs, 0.73 -> 0.67 ms at 2^20).
 // FIXUP_LANES = 1 (big bucket sets: 2^21 buckets of which few straddle more than two threads) is the plain one-lane-per-bucket kernel.
 template <uint32_t FIXUP_LANES, int Q = 1> __global__ void __launch_bounds__(256) k_msm_fixup(const uint32_t *__restrict__ offsets, uint32_t nbuckets, g1_xyzz29_t *__restrict__ bucket_sums,
-                                                   const g1_xyzz29_t *__restrict__ part, const int32_t *__restrict__ part_id, uint32_t seg_max, uint32_t acc_threads,
+                                                   const g1_xyzz29_t *__restrict__ part, const int32_t *__restrict__ part_id, uint32_t seg_arg, uint32_t acc_threads,
                                                    uint32_t *__restrict__ big_list, uint32_t *__restrict__ big_count, uint32_t big_cap,
                                                    uint32_t *__restrict__ huge_list, uint32_t *__restrict__ huge_count, uint32_t huge_cap, uint32_t serial_max, uint32_t huge_min) {
   const uint32_t gid = (blockIdx.x * blockDim.x + threadIdx.x) / Q, b = gid / FIXUP_LANES, sub = gid % FIXUP_LANES;   // Q lanes per logical thread
   const bool lead = (threadIdx.x & (Q - 1)) == 0;
-  const uint32_t seg = msm_seg_eff(offsets[nbuckets], acc_threads, seg_max & 0x1fffu, (seg_max >> 13) & 0x1fffu, (seg_max >> 26) * 2);   // the segment length k_msm_accumulate used
+  const uint32_t seg = msm_seg_eff(offsets[nbuckets], acc_threads, seg_arg);   // the segment length k_msm_accumulate used
   g1_xyzz29_t acc = g1_xyzz29_identity();
   bool mine = false;   // this group sums a straddling bucket of moderate span
   if (b < nbuckets) {
@@ -623,20 +660,21 @@ __global__ void __launch_bounds__(64) k_msm_fixup_huge_fold(g1_xyzz29_t *__restr
 // two-partial bucket, six for a run that fills the wavefront) and stores the runs that lie strictly inside it; its first and last run may
 // continue in the neighbouring wavefronts and go, two slots per wavefront, to the next level (1/32 of the size), which is the same kernel.
 // Work and depth no longer depend on how the scalars are distributed: O(partials) additions, log-many levels, no lists, no thresholds.
-__global__ void __launch_bounds__(256) k_msm_segfix(const int32_t *__restrict__ ids, const g1_xyzz29_t *__restrict__ recs, uint32_t n, g1_xyzz29_t *__restrict__ bucket_sums,
-                                                    int32_t *__restrict__ ids_out, g1_xyzz29_t *__restrict__ recs_out, int last_level) {
+template <class G> __global__ void __launch_bounds__(256) k_msm_segfix(const int32_t *__restrict__ ids, const typename G::rec_t *__restrict__ recs, uint32_t n, typename G::rec_t *__restrict__ bucket_sums,
+                                                    int32_t *__restrict__ ids_out, typename G::rec_t *__restrict__ recs_out, int last_level) {
+  using rec_t = typename G::rec_t;
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63, wave = j >> 6;
   if (wave >= ((n + 63) >> 6)) return;   // whole wavefronts past the end (the grid is rounded up to workgroups of four)
   const int32_t key0 = j < n ? ids[j] : -1;
-  g1_xyzz29_t val = key0 >= 0 ? load_xyzz29(&recs[j]) : g1_xyzz29_identity();
+  rec_t val = key0 >= 0 ? G::load(&recs[j]) : G::identity();
   int32_t key = key0;
   for (uint32_t o = 1; o < 64; o <<= 1) { const int32_t kk = __shfl_up(key, o); if (lane >= o && key < 0) key = kk; }   // fill-forward over empty slots (they hold identities)
   for (uint32_t o = 1; o < 64; o <<= 1) {
     const int32_t k2 = __shfl_down(key, o);
     const bool take = lane + o < 64 && key >= 0 && k2 == key;
     if (__ballot(take) == 0) continue;                 // wave-uniform: no run is longer than o here
-    const g1_xyzz29_t other = shfl_down_xyzz29(val, o);
-    if (take) g1_xyzz29_add(val, other);
+    const rec_t other = G::shfl_down(val, o);
+    if (take) G::template add<1>(val, other);
   }
   const int32_t kprev = __shfl_up(key, 1);
   const bool head = key >= 0 && (lane == 0 || kprev != key);
@@ -644,10 +682,10 @@ __global__ void __launch_bounds__(256) k_msm_segfix(const int32_t *__restrict__ 
   const uint32_t first_lane = valid ? (uint32_t)__ffsll((unsigned long long)valid) - 1 : 64u;   // after the fill every lane from first_lane on is valid
   const int32_t key_last = __shfl(key, 63), key_first = __shfl(key, first_lane < 64u ? (int)first_lane : 0);
   const bool is_first = head && lane == first_lane, is_last = head && key == key_last;
-  if (last_level) { if (head) store_xyzz29(&bucket_sums[key], val); return; }
-  if (head && !is_first && !is_last) store_xyzz29(&bucket_sums[key], val);
-  if (is_first) { ids_out[2 * wave] = key; store_xyzz29(&recs_out[2 * (uint64_t)wave], val); }
-  if (is_last && !is_first) { ids_out[2 * wave + 1] = key; store_xyzz29(&recs_out[2 * (uint64_t)wave + 1], val); }
+  if (last_level) { if (head) G::store(&bucket_sums[key], val); return; }
+  if (head && !is_first && !is_last) G::store(&bucket_sums[key], val);
+  if (is_first) { ids_out[2 * wave] = key; G::store(&recs_out[2 * (uint64_t)wave], val); }
+  if (is_last && !is_first) { ids_out[2 * wave + 1] = key; G::store(&recs_out[2 * (uint64_t)wave + 1], val); }
   if (lane == 0) {   // unused output slots are marked empty (the slot writers above and these never touch the same slot)
     if (first_lane == 64u) { ids_out[2 * wave] = -1; ids_out[2 * wave + 1] = -1; }
     else if (key_first == key_last) ids_out[2 * wave + 1] = -1;
@@ -663,59 +701,54 @@ __global__ void __launch_bounds__(256) k_msm_bucket_fold(g1_xyzz29_t *__restrict
   store_xyzz29(&buckets[b], acc);
 }
 
-// ---- 6a. chunked running sums: thread j of window w covers buckets [j*K, (j+1)*K) and emits
+// ---- 6a. chunked running sums: logical thread j of bucket set w covers buckets [j*K, (j+1)*K) and emits
 //          T + (j*K) * S  where S = sum B_i, T = sum (i_local + 1) B_i
-template <int Q> __global__ void __launch_bounds__(128) k_msm_bucket_reduce(const g1_xyzz29_t *__restrict__ bucket_sums, g1_xyzz29_t *__restrict__ chunk_out, MsmPlan P, uint32_t chunk) {
-  const uint32_t chunks_per_window = P.nb / chunk;
-  const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) / Q;   // logical thread (Q lanes each)
-  if (g >= chunks_per_window * P.windows) return;
-  const uint32_t w = g / chunks_per_window, j = g - w * chunks_per_window;
-  const g1_xyzz29_t *B = bucket_sums + (uint64_t)w * P.nb + (uint64_t)j * chunk;
-  g1_xyzz29_t run = g1_xyzz29_identity(), T = g1_xyzz29_identity();
-  for (uint32_t i = chunk; i-- > 0;) { g1_vadd<Q>(run, load_xyzz29(&B[i])); g1_vadd<Q>(T, run); }
+// (the tail kernels are templated on the policy G and on Q lanes per logical thread: Q = 4 is G1's quad form)
+template <class G, int Q> __global__ void __launch_bounds__(128) k_msm_bucket_reduce(const typename G::rec_t *__restrict__ bucket_sums, typename G::rec_t *__restrict__ chunk_out, uint32_t nb, uint32_t sets, uint32_t chunk) {
+  using rec_t = typename G::rec_t;
+  const uint32_t chunks_per_set = nb / chunk;
+  const uint32_t gi = (blockIdx.x * blockDim.x + threadIdx.x) / Q;   // logical thread (Q lanes each)
+  if (gi >= chunks_per_set * sets) return;
+  const uint32_t w = gi / chunks_per_set, j = gi - w * chunks_per_set;
+  const rec_t *B = bucket_sums + (uint64_t)w * nb + (uint64_t)j * chunk;
+  rec_t run = G::identity(), T = G::identity();
+  for (uint32_t i = chunk; i-- > 0;) { G::template add<Q>(run, G::load(&B[i])); G::template add<Q>(T, run); }
   if (j != 0) {
     const uint32_t k = j * chunk;
-    g1_xyzz29_t kS = g1_xyzz29_identity();
-    for (int bit = 31 - __clz(k); bit >= 0; bit--) { kS = g1_vdbl<Q>(kS); if ((k >> bit) & 1) g1_vadd<Q>(kS, run); }
-    g1_vadd<Q>(T, kS);
+    rec_t kS = G::identity();
+    for (int bit = 31 - __clz(k); bit >= 0; bit--) { kS = G::template dbl<Q>(kS); if ((k >> bit) & 1) G::template add<Q>(kS, run); }
+    G::template add<Q>(T, kS);
   }
-  if ((threadIdx.x & (Q - 1)) == 0) store_xyzz29(&chunk_out[g], T);
+  if ((threadIdx.x & (Q - 1)) == 0) G::store(&chunk_out[gi], T);
 }
-// ---- 6b. per window: tree-sum of the chunk results.  grid = (blocks, windows); a block folds up to 256 * TREE_PER_THREAD inputs
-//          (wavefront shuffles, then LDS across the 4 waves) into one output; launched repeatedly until one value per window is left.
+// ---- 6b. per bucket set: tree-sum of the chunk results.  grid = (blocks, sets); a block of 256 lanes = 256 / Q logical threads folds up
+//          to (256 / Q) * TREE_PER_THREAD inputs (wavefront shuffles, then LDS across the 4 waves) into one output; launched repeatedly
+//          until one value per set is left.
 constexpr uint32_t TREE_PER_THREAD = 4;
-// a block of 256 lanes = 256 / Q logical threads folds up to (256 / Q) * TREE_PER_THREAD inputs
-template <int Q> __global__ void __launch_bounds__(256) k_msm_tree_sum29(const g1_xyzz29_t *__restrict__ in, uint32_t in_per_window, g1_xyzz29_t *__restrict__ out, uint32_t out_per_window) {
-  __shared__ g1_xyzz29_t lds[4];
+template <class G, int Q> __global__ void __launch_bounds__(256) k_msm_tree_sum(const typename G::rec_t *__restrict__ in, uint32_t in_per_set, typename G::rec_t *__restrict__ out, uint32_t out_per_set) {
+  using rec_t = typename G::rec_t;
+  __shared__ rec_t lds[4];
   constexpr uint32_t VT = 256 / Q;                               // logical threads per block, 64 / Q per wavefront
   const uint32_t w = blockIdx.y, first = blockIdx.x * VT * TREE_PER_THREAD, vt = threadIdx.x / Q;
-  const g1_xyzz29_t *src = in + (uint64_t)w * in_per_window;
-  g1_xyzz29_t acc = g1_xyzz29_identity();
-  for (uint32_t k = 0; k < TREE_PER_THREAD; k++) { const uint32_t i = first + k * VT + vt; if (i < in_per_window) g1_vadd<Q>(acc, load_xyzz29(&src[i])); }
-  for (uint32_t o = 32 / Q; o >= 1; o >>= 1) { const g1_xyzz29_t other = shfl_down_xyzz29(acc, o * Q); g1_vadd<Q>(acc, other); }
+  const rec_t *src = in + (uint64_t)w * in_per_set;
+  rec_t acc = G::identity();
+  for (uint32_t k = 0; k < TREE_PER_THREAD; k++) { const uint32_t i = first + k * VT + vt; if (i < in_per_set) G::template add<Q>(acc, G::load(&src[i])); }
+  for (uint32_t o = 32 / Q; o >= 1; o >>= 1) { const rec_t other = G::shfl_down(acc, o * Q); G::template add<Q>(acc, other); }
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x < Q) { for (uint32_t k = 1; k < 4; k++) g1_vadd<Q>(acc, lds[k]); if (threadIdx.x == 0) store_xyzz29(&out[(uint64_t)w * out_per_window + blockIdx.x], acc); }
+  if (threadIdx.x < Q) { for (uint32_t k = 1; k < 4; k++) G::template add<Q>(acc, lds[k]); if (threadIdx.x == 0) G::store(&out[(uint64_t)w * out_per_set + blockIdx.x], acc); }
 }
-__device__ __forceinline__ void msm_emit_result(const g1_xyzz_t &acc, g1_jac_t *out, int normalise) {
-  if (normalise) { *out = g1_xyzz_to_jac_normalised(acc); return; }
-  // un-normalised Jacobian representative (X ZZ^2, Y ZZZ^2, ZZZ): skips the inversion; used for the per-GPU partial sums, which are
-  // folded (and normalised once) by k_g1_sum
-  g1_jac_t r;
-  if (g1_xyzz_is_identity(acc)) { r.x = Fq::zero(); r.y = Fq::zero(); r.z = Fq::zero(); }
-  else { r.x = fq_mul_ps(acc.x, fq_sqr_ps(acc.zz)); r.y = fq_mul_ps(acc.y, fq_sqr_ps(acc.zzz)); r.z = acc.zzz; }
-  *out = r;
-}
-// ---- 7. Horner over windows + normalisation.  One lane; 255 doublings are inherently serial (none with window tables).
-template <int Q> __global__ void __launch_bounds__(64) k_msm_final29(const g1_xyzz29_t *__restrict__ window_sums, uint32_t windows, uint32_t c, g1_jac_t *__restrict__ out, int normalise) {
+// ---- 7. Horner over the window sums of MSM blockIdx.x + the result in the caller's form (G::emit).  One logical thread; 255 doublings are
+//         inherently serial (none with window tables).
+template <class G, int Q> __global__ void __launch_bounds__(64) k_msm_final(const typename G::rec_t *__restrict__ window_sums, uint32_t windows, uint32_t c, typename G::out_t *__restrict__ out, int normalise) {
   if (threadIdx.x >= Q) return;
   window_sums += (uint64_t)blockIdx.x * windows; out += blockIdx.x;
-  g1_xyzz29_t acc = g1_xyzz29_identity();
+  typename G::rec_t acc = G::identity();
   for (uint32_t w = windows; w-- > 0;) {
-    for (uint32_t k = 0; k < c; k++) acc = g1_vdbl<Q>(acc);
-    g1_vadd<Q>(acc, load_xyzz29(&window_sums[w]));
+    for (uint32_t k = 0; k < c; k++) acc = G::template dbl<Q>(acc);
+    G::template add<Q>(acc, G::load(&window_sums[w]));
   }
-  if (threadIdx.x == 0) msm_emit_result(g1_xyzz29_to_sat(acc), out, normalise);
+  if (threadIdx.x == 0) G::emit(acc, out, normalise);
 }
 // sum of n Jacobian points (fold of per-GPU partial results), normalised
 __global__ void k_g1_sum(const g1_jac_t *__restrict__ pts, uint32_t n, g1_jac_t *__restrict__ out) {

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
 from oracle import cref, pyref
 from tests.gpu_common import (ALL_ONES_LIMBS, R, adversarial_fr_words, affine_of, full_range, ints_to_words, pool_pairs,
-                              rand_points, tile_words, words_to_ints)
+                              rand_fr, rand_points, tile_words, words_to_ints)
 
 pytestmark = pytest.mark.gpu
 
@@ -489,6 +489,127 @@ def test_ntt_plan_knobs(knob_reference, setting):
 @pytest.fixture(scope="module")
 def points(zk):
     return rand_points(np.random.default_rng(42), 2048)
+
+
+# ------------------------------------------------------------------------------------------------ MSM plan knobs (read once, at init: one child process each)
+MSM_KNOB_N = 2048
+MSM_KNOB_TAU = 0x1234567
+MSM_KNOB_SETTINGS = [
+    {"MI355_FIXUP_MODE": "0"},
+    {"MI355_FIXUP_MODE": "1"},
+    {"MI355_FIXUP_MODE": "0", "MI355_TAIL_COOP_MAX": "0"},
+    {"MI355_FIXUP_MODE": "0", "MI355_FIXUP_LANES_MAX_LOG": "0", "MI355_TAIL_COOP_MASK": "14"},
+    {"MI355_FIXUP_MODE": "0", "MI355_FIXUP_SERIAL_MAX": "1"},
+    {"MI355_TAIL_COOP_MASK": "0"},
+    {"MI355_TAIL_COOP_MAX": "16777216"},
+    {"MI355_REDUCE_MIN_CHUNK": "64", "MI355_REDUCE_CHAINS": "1024"},
+    {"MI355_SORT_T1": "8192"},
+    {"MI355_SORT_T2": "16384"},
+    {"MI355_SORT_SPLIT": "2"},
+    {"MI355_SORT_FB": "9"},
+    {"MI355_SEG_MIN": "1", "MI355_SEG_FILL": "100"},
+    {"MI355_SEG_FACTOR": "1"},
+    {"MI355_HOST_CHUNKS": "4", "MI355_HOST_SLICE_MIN_LOG": "10"},      # the host path cuts 2 048 scalars into slices with a bucket set each, then k_msm_bucket_fold
+]
+
+
+def _witness_like(rng, n):
+    """mostly 0 / 1, the rest below 2^16 (canonical), as Montgomery limbs (as in test_gpu_g2_msm.py)"""
+    v = rng.integers(0, 1 << 16, size=n, dtype=np.uint64)
+    r = rng.random(n)
+    v[r < 0.45] = 0
+    v[(r >= 0.45) & (r < 0.9)] = 1
+    can = np.zeros((n, 4), dtype=np.uint64); can[:, 0] = v
+    return cref.f_from_canonical_vec(cref.FR, can)
+
+
+def _g2_expected(bases, scalars):
+    """sum of cref.g2_mul multiples combined with pyref.g2_add (expected() of test_gpu_g2_msm.py)"""
+    rinv_p = pow(pyref.MONT_R, -1, pyref.P_MOD)
+    acc = None
+    for b, s in zip(bases, scalars):
+        limbs = np.asarray(cref.g2_mul(b, s), dtype=np.uint64)
+        pt = None
+        if limbs.any():
+            c = [pyref.from_limbs(limbs[4 * k:4 * k + 4]) * rinv_p % pyref.P_MOD for k in range(4)]
+            pt = ((c[0], c[1]), (c[2], c[3]))
+        acc = pyref.g2_add(acc, pt)
+    return np.array(pyref.g2_to_limbs(acc), dtype=np.uint64)
+
+
+@pytest.fixture(scope="module")
+def msm_knob_reference(tmp_path_factory, points):
+    """inputs and the oracle's results for the MSM knob children, computed once on the CPU"""
+    n = MSM_KNOB_N
+    rng = np.random.default_rng(4242)
+    uniform = full_range("msm", n)
+    ref = {"points": points, "g1_uniform": uniform, "g1_equal": np.repeat(uniform[7:8], n, axis=0), "g1_witness": _witness_like(rng, n)}
+    for kind in ("uniform", "equal", "witness"):
+        ref["want_g1_" + kind] = cref.g1_to_affine(cref.best_multiexp(ref["g1_" + kind], points))
+    for j in range(9):                                                  # the batch entry point: 9 polynomials of 257 scalars (the first 3 alone as well)
+        ref["want_batch%d" % j] = cref.g1_to_affine(cref.best_multiexp(uniform[199 * j:199 * j + 257], points[:257]))
+    can = cref.f_to_canonical_vec(cref.FR, uniform)                     # window tables: commit against p(tau) G on the synthetic SRS
+    p_tau, t = 0, 1
+    for row in can:
+        p_tau = (p_tau + sum(int(v) << (64 * i) for i, v in enumerate(row)) * t) % R; t = t * MSM_KNOB_TAU % R
+    ref["want_commit"] = cref.g1_to_affine(cref.g1_mul(cref.g1_generator(), cref.fr_mont(p_tau)))
+    gen = cref.g2_generator()
+    g2 = np.stack([cref.g2_mul(gen, s) for s in rand_fr(rng, 1000, full=False)])
+    ref["g2_bases"] = g2
+    ref["g2_uniform"] = rand_fr(rng, 1000); ref["g2_equal"] = np.repeat(rand_fr(rng, 1, full=False), 1000, axis=0)
+    for kind in ("uniform", "equal"):
+        ref["want_g2_" + kind] = _g2_expected(g2, ref["g2_" + kind])
+    ref["g2_batch"] = rand_fr(rng, 9 * 64).reshape(9, 64, 4)
+    ref["want_g2_batch"] = np.stack([_g2_expected(g2[:64], sc) for sc in ref["g2_batch"]])
+    path = str(tmp_path_factory.mktemp("msm_knobs") / "ref.npz")
+    np.savez(path, **ref)
+    return path
+
+
+def _msm_knob_child(ref_path):
+    """runs in the child: every MSM of the reference under the environment's plan knobs, bit-exact"""
+    zk = ge.load_package(); zk.init(0)
+    h2 = zk.halo2
+    lib, check = zk._capi.lib(), zk._capi.check
+    ref = np.load(ref_path)
+    n, pts, uniform = MSM_KNOB_N, ref["points"], ref["g1_uniform"]
+    for c in (0, 13, 16):                                               # c = 13: three levels of the segmented fix-up; c = 16: 2^19 buckets, one-lane running sums, two tree passes
+        check(lib.mi355_msm_set_window_bits(c))
+        for kind in ("uniform", "equal", "witness"):
+            assert (affine_of(h2.best_multiexp(ref["g1_" + kind], pts)) == ref["want_g1_" + kind]).all(), ("g1", kind, c)
+    check(lib.mi355_msm_set_window_bits(0))
+    params = h2.ParamsKZG.from_host(11, pts, pts)
+    for m in (3, 9):                                                    # 9: the staged pointer array
+        dev = [_up(zk, uniform[199 * j:199 * j + 257]) for j in range(m)]
+        got = params.commit_many(dev)
+        for j in range(m):
+            assert (affine_of(got[j]) == ref["want_batch%d" % j]).all(), ("batch", m, j)
+        for d in dev:
+            d.free()
+    assert (affine_of(h2.best_multiexp(uniform, params.g_slice(0, n))) == ref["want_g1_uniform"]).all(), "host-pointer entry point"
+    params.release()
+    srs = h2.ParamsKZG.setup(11, MSM_KNOB_TAU)                          # window tables: all windows share one bucket set, no Horner
+    srs.precompute()
+    assert (affine_of(srs.commit(uniform)) == ref["want_commit"]).all(), "window tables"
+    srs.release()
+    g2 = ref["g2_bases"]
+    for kind in ("uniform", "equal"):
+        assert (h2.g2_msm(g2, ref["g2_" + kind]) == ref["want_g2_" + kind]).all(), ("g2", kind)
+    db = h2.DeviceBuffer.from_host(g2[:64]); ds = [h2.DeviceBuffer.from_host(sc) for sc in ref["g2_batch"]]
+    assert (h2.g2_msm_batch_dev(db, ds, 64) == ref["want_g2_batch"]).all(), "g2 batch of 9"
+    for d in [db] + ds:
+        d.free()
+    print("MSM-KNOBS-OK")
+
+
+@pytest.mark.parametrize("setting", MSM_KNOB_SETTINGS, ids=lambda s: ",".join("%s=%s" % (k[6:], v) for k, v in s.items()))
+def test_msm_plan_knobs(msm_knob_reference, setting):
+    """every MI355_* value that selects between the forms of the bucket pipeline (per-bucket / segmented fix-up, one-lane / quad tail kernels,
+    chunk and tile choices, segment packing, host slices) gives the oracle's points: G1 under three window widths, the batch, host-pointer and
+    window-table paths, and G2, which runs the same templated kernels."""
+    code = "import sys; sys.path.insert(0, %r); import tests.test_gpu_fr_full_range as t; t._msm_knob_child(%r)" % (ROOT, msm_knob_reference)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **setting), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "MSM-KNOBS-OK" in r.stdout, (setting, r.stdout[-500:], r.stderr[-2500:])
 
 
 MSM_SPECIAL = [R - 1, R - 2, (R - 1) // 2, (R + 1) // 2, 1 << 253, pyref.FR_ZETA, R - pyref.FR_ZETA]     # canonical values

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """rocpd_timeline.py <results.db> [first_kernel] [last_kernel] -- the kernels of ONE call in launch order with start offsets, durations and the
 idle gap before each (rocprofv3 --kernel-trace rocpd database): where a latency-bound call (a small MSM) spends its time between kernels.
-Defaults: the last k_msm_digits ... k_msm_final29 span of the trace."""
+Defaults: the last k_msm_digits ... k_msm_final span of the trace."""
 import sqlite3
 import sys
 
 db = sqlite3.connect(sys.argv[1])
 first = sys.argv[2] if len(sys.argv) > 2 else "k_msm_digits"
-last = sys.argv[3] if len(sys.argv) > 3 else "k_msm_final29"
+last = sys.argv[3] if len(sys.argv) > 3 else "k_msm_final"
 rows = db.execute("select name, start, end from kernels order by start").fetchall()
 short = lambda n: n.split("(")[0].replace("zk::", "").replace("void ", "")
 idx_last = max((i for i, r in enumerate(rows) if last in r[0]), default=None)
