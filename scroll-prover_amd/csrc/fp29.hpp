@@ -226,6 +226,15 @@ template <class P> struct Fp29 {
     for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + P::fat29_4p(i) - b.l[i];
     return carry(r);
   }
+  // a - b + 4p WITHOUT the carry pass: a limbs <= 2^29 + 8, b TIGHT as for sub4.  Limb i < 8 lies in [0, 2^29 + 8 + fat29_4p(i)] (< 2^30.6), the top limb
+  // is a.l[8] + 0xc19138 - b.l[8] >= 0 (b < 2p: b.l[8] <= 0x60c89c).  Only for a consumer whose own bound admits such limbs: the b operand of mul_sub
+  // beside an a operand <= 2^29 + 8 (g1_29.hpp: the column sums then stay below 0.69 * 2^63 with this modulus and this constant).
+  ZK_HD static fe29_t sub4_lazy(const fe29_t &a, const fe29_t &b) {
+    fe29_t r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + P::fat29_4p(i) - b.l[i];
+    return r;
+  }
   // a - b + 8p:  b limbs <= 2^30 - 2 (carried values, doubled tight values), value(b) < 7.9 p
   ZK_HD static fe29_t sub8(const fe29_t &a, const fe29_t &b) {
     fe29_t r;

@@ -26,7 +26,7 @@
 // window m * W + w: grid.y = m in the digits kernel, a bucket set per polynomial, M workgroups in k_msm_final.
 //
 // Algorithmic HBM bytes: 96 B per (scalar, point) pair.  The accumulation is VALU-integer bound
-// (10 field multiplications = ~1650 v_mad_u64_u32 + ~700 other instructions per mixed addition), see DESIGN.md section 4.
+// (10 field multiplications = 1 467 v_mad_[ui]64 + ~620 other instructions per mixed addition, profiles/accumulate_trim_ab.md), see DESIGN.md section 4.
 #pragma once
 #include "fp_asm.hpp"
 #include "g1_29.hpp"
@@ -542,12 +542,17 @@ struct G1Bases {
     return &bases[(uint64_t)w * row_stride + (gi & ((1u << nshift) - 1))];
   }
   __device__ __forceinline__ g1_affine_t load(uint32_t e) const { return load_affine(base_of(e)); }
-  __device__ __forceinline__ void madd(g1_xyzz29_t &acc, const g1_affine_t &p, bool neg) const { g1_xyzz29_madd<true, true>(acc, p, neg); }
+  __device__ __forceinline__ void madd(g1_xyzz29_t &acc, const g1_affine_t &p, bool neg) const { g1_xyzz29_madd<true, true, true>(acc, p, neg); }
+};
+// the walk's accumulator keeps x negated (g1_29.hpp, NEGX); every flush -- bucket sum or partial -- hands the plain record on, so nothing after
+// k_msm_accumulate sees the difference (a dozen instructions per flushed record, against 55 per addition saved)
+struct G1AccOps : G1Ops {
+  static __device__ __forceinline__ void store(rec_t *p, rec_t v) { g1_xyzz29_negx_to_plain(v); store_xyzz29(p, v); }
 };
 __global__ void __launch_bounds__(256) k_msm_accumulate(const g1_affine_t *__restrict__ bases, const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ offsets,
                                                         uint32_t nbuckets, g1_xyzz29_t *__restrict__ bucket_sums, g1_xyzz29_t *__restrict__ part, int32_t *__restrict__ part_id, uint32_t seg_arg,
                                                         uint32_t nshift, uint64_t row_stride) {
-  msm_segment_walk<G1Ops>(G1Bases{bases, nshift, row_stride}, sorted, offsets, nbuckets, bucket_sums, part, part_id, seg_arg, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  msm_segment_walk<G1AccOps>(G1Bases{bases, nshift, row_stride}, sorted, offsets, nbuckets, bucket_sums, part, part_id, seg_arg, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // ---- 5. fix-up of buckets that straddle thread boundaries.  Small spans are summed by one lane; a bucket that spans more than
