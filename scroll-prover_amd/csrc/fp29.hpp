@@ -39,15 +39,15 @@ struct Fr29P {
   ZK_HD static constexpr uint32_t fat30_16p(int i) { constexpr uint32_t m[9] = {0x40000010u, 0x50fac9f6u, 0x45c2450du, 0x5d090f35u, 0x585d2831u, 0x4db40c08u, 0x4a6e140fu, 0x45c2633eu, 0x30644e5u}; return m[i]; }
 };
 
-// Chained multiplier (A/B experiment).  Written as plain C++ the compiler sums every column's products in a fresh
-// accumulator and joins it to the carried one with a 64-bit add (a shorter dependency chain, but one more 4-cycle instruction per column:
-// 16 per multiplication, ~7 % of its issue slots).  mul_c / sqr_c / mul_sub_c issue the products of a column as one inline-asm block of
-// chained v_mad instead; with three waves per SIMD the chain latency is hidden anyway.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MI355_FP29_NO_CHAIN)
-#define ZK_FP29_CHAIN 1
+// Two multipliers, each named outright at its call sites:
+//   mul / sqr / mul_sub        plain C++, also the host form.  The compiler sums every column's products in a fresh accumulator and joins it to the
+//                              carried one with a 64-bit add: a shorter dependency chain, but one more 4-cycle instruction per column (16 per
+//                              multiplication, ~7 % of its issue slots).
+//   mul_c / sqr_c / mul_sub_c  the products of a column issued as one inline-asm block of chained v_mad (fp29_asm_gen.inc, written by
+//                              tools/gen_fp29_asm.py); with three waves per SIMD the chain latency is hidden.  What the kernels run.  Bit-identical
+//                              results; on the host they are the plain C++ routines.
+#if defined(__HIP_DEVICE_COMPILE__)
 #include "fp29_asm_gen.inc"
-#else
-#define ZK_FP29_CHAIN 0
 #endif
 
 template <class P> struct Fp29 {
@@ -71,6 +71,35 @@ template <class P> struct Fp29 {
     for (int k = 9; k < 17; k++) {
 #pragma unroll
       for (int i = k - 8; i < 9; i++) acc += (uint64_t)a.l[i] * b.l[k - i];
+#pragma unroll
+      for (int i = k - 8; i < 9; i++) acc += (uint64_t)m[i] * P::mod(k - i);
+      r.l[k - 9] = (uint32_t)acc & M29;
+      acc >>= 29;
+    }
+    r.l[8] = (uint32_t)acc;
+    return r;
+  }
+  ZK_HD static fe29_t sqr(const fe29_t &a) {
+    uint64_t acc = 0; uint32_t m[9]; fe29_t r;
+    uint32_t a2[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) a2[i] = a.l[i] << 1;   // limbs < 2^30.3 -> doubled < 2^31.3: a_i * 2a_j < 2^61.6, <= 4 such + 1 square per column
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+      for (int i = 0; 2 * i < k; i++) acc += (uint64_t)a.l[i] * a2[k - i];
+      if ((k & 1) == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
+#pragma unroll
+      for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * P::mod(k - i);
+      m[k] = ((uint32_t)acc * P::INV) & M29;
+      acc += (uint64_t)m[k] * P::mod(0);
+      acc >>= 29;
+    }
+#pragma unroll
+    for (int k = 9; k < 17; k++) {
+#pragma unroll
+      for (int i = k - 8; 2 * i < k; i++) acc += (uint64_t)a.l[i] * a2[k - i];
+      if ((k & 1) == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
 #pragma unroll
       for (int i = k - 8; i < 9; i++) acc += (uint64_t)m[i] * P::mod(k - i);
       r.l[k - 9] = (uint32_t)acc & M29;
@@ -109,10 +138,9 @@ template <class P> struct Fp29 {
     r.l[8] = (uint32_t)((int32_t)acc + (int32_t)P::mod(8));
     return r;
   }
-  // the same three routines with the limb products of every column issued as ONE inline-asm block of chained v_mad (fp29_asm_gen.inc,
-  // written by tools/gen_fp29_asm.py): bit-identical results; on the host they are the plain C++ routines
+  // the chained forms of mul, sqr and mul_sub: same operand bounds, bit-identical results
   ZK_HD static fe29_t mul_c(const fe29_t &a, const fe29_t &b) {
-#if ZK_FP29_CHAIN
+#if defined(__HIP_DEVICE_COMPILE__)
     uint64_t acc = 0, co; uint32_t m[9]; fe29_t r;
     ZK_FP29_MUL_COLUMNS
     (void)co;
@@ -122,7 +150,7 @@ template <class P> struct Fp29 {
 #endif
   }
   ZK_HD static fe29_t sqr_c(const fe29_t &a) {
-#if ZK_FP29_CHAIN
+#if defined(__HIP_DEVICE_COMPILE__)
     uint64_t acc = 0, co; uint32_t m[9]; fe29_t r;
     uint32_t a2[9];
 #pragma unroll
@@ -135,7 +163,7 @@ template <class P> struct Fp29 {
 #endif
   }
   ZK_HD static fe29_t mul_sub_c(const fe29_t &a, const fe29_t &b, const fe29_t &c, const fe29_t &d) {
-#if ZK_FP29_CHAIN
+#if defined(__HIP_DEVICE_COMPILE__)
     int64_t acc = 0; uint64_t co; uint32_t m[9]; fe29_t r;
     int32_t nc[9];
 #pragma unroll
@@ -146,68 +174,6 @@ template <class P> struct Fp29 {
 #else
     return mul_sub(a, b, c, d);
 #endif
-  }
-  template <bool C> ZK_HD static fe29_t mul_t(const fe29_t &a, const fe29_t &b) { return C ? mul_c(a, b) : mul(a, b); }
-  template <bool C> ZK_HD static fe29_t sqr_t(const fe29_t &a) { return C ? sqr_c(a) : sqr(a); }
-  template <bool C> ZK_HD static fe29_t mul_sub_t(const fe29_t &a, const fe29_t &b, const fe29_t &c, const fe29_t &d) { return C ? mul_sub_c(a, b, c, d) : mul_sub(a, b, c, d); }
-  // same product with TWO independent column accumulators (even / odd terms): halves the dependent v_mad_u64_u32 chain
-  // at the price of one 64-bit add per column; pays when few waves share a SIMD (experiment, see tools/microbench.hip)
-  ZK_HD static fe29_t mul2(const fe29_t &a, const fe29_t &b) {
-    uint64_t acc = 0; uint32_t m[9]; fe29_t r;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-      uint64_t e = acc, o = 0;
-#pragma unroll
-      for (int i = 0; i <= k; i++) { if (i & 1) o += (uint64_t)a.l[i] * b.l[k - i]; else e += (uint64_t)a.l[i] * b.l[k - i]; }
-#pragma unroll
-      for (int i = 0; i < k; i++) { if (i & 1) e += (uint64_t)m[i] * P::mod(k - i); else o += (uint64_t)m[i] * P::mod(k - i); }
-      acc = e + o;
-      m[k] = ((uint32_t)acc * P::INV) & M29;
-      acc += (uint64_t)m[k] * P::mod(0);
-      acc >>= 29;
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-      uint64_t e = acc, o = 0;
-#pragma unroll
-      for (int i = k - 8; i < 9; i++) { if (i & 1) o += (uint64_t)a.l[i] * b.l[k - i]; else e += (uint64_t)a.l[i] * b.l[k - i]; }
-#pragma unroll
-      for (int i = k - 8; i < 9; i++) { if (i & 1) e += (uint64_t)m[i] * P::mod(k - i); else o += (uint64_t)m[i] * P::mod(k - i); }
-      acc = e + o;
-      r.l[k - 9] = (uint32_t)acc & M29;
-      acc >>= 29;
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
-  }
-  ZK_HD static fe29_t sqr(const fe29_t &a) {
-    uint64_t acc = 0; uint32_t m[9]; fe29_t r;
-    uint32_t a2[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) a2[i] = a.l[i] << 1;   // limbs < 2^30.3 -> doubled < 2^31.3: a_i * 2a_j < 2^61.6, <= 4 such + 1 square per column
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-#pragma unroll
-      for (int i = 0; 2 * i < k; i++) acc += (uint64_t)a.l[i] * a2[k - i];
-      if ((k & 1) == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
-#pragma unroll
-      for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * P::mod(k - i);
-      m[k] = ((uint32_t)acc * P::INV) & M29;
-      acc += (uint64_t)m[k] * P::mod(0);
-      acc >>= 29;
-    }
-#pragma unroll
-    for (int k = 9; k < 17; k++) {
-#pragma unroll
-      for (int i = k - 8; 2 * i < k; i++) acc += (uint64_t)a.l[i] * a2[k - i];
-      if ((k & 1) == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
-#pragma unroll
-      for (int i = k - 8; i < 9; i++) acc += (uint64_t)m[i] * P::mod(k - i);
-      r.l[k - 9] = (uint32_t)acc & M29;
-      acc >>= 29;
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
   }
   // one carry pass: limbs back below 2^29 + 8 (value unchanged); the top limb absorbs the last carry
   ZK_HD static fe29_t carry(const fe29_t &a) {

@@ -8,9 +8,9 @@
 // instead of 64 in the a*a half.
 //
 // The host build of the same functions (plain C, for tests/hostcheck) uses 128-bit integers in `mac`.
+// This file holds the multiplier and the field policy built on it (FqPs / FrPs), no point code.
 #pragma once
 #include "fp.hpp"
-#include "g1.hpp"
 #include "fp_asm_gen.inc"
 
 namespace zk {
@@ -102,60 +102,15 @@ template <class P> ZK_HD fe_t mont_sqr_ps(const fe_t &a) {
 #endif
 }
 
-ZK_HD fe_t fq_mul_ps(const fe_t &a, const fe_t &b) { return mont_mul_ps<FqP>(a, b); }
-ZK_HD fe_t fq_sqr_ps(const fe_t &a) { return mont_sqr_ps<FqP>(a); }
-ZK_HD fe_t fr_mul_ps(const fe_t &a, const fe_t &b) { return mont_mul_ps<FrP>(a, b); }
-ZK_HD fe_t fr_sqr_ps(const fe_t &a) { return mont_sqr_ps<FrP>(a); }
-
-// XYZZ mixed addition on the tuned multiplier (same formulas and special cases as g1_xyzz_madd)
-ZK_HD g1_xyzz_t g1_xyzz_dbl_affine_ps(const g1_affine_t &p) {
-  fe_t U = Fq::dbl(p.y), V = fq_sqr_ps(U), W = fq_mul_ps(U, V), S = fq_mul_ps(p.x, V);
-  fe_t M = fq_sqr_ps(p.x); M = Fq::add(Fq::dbl(M), M);
-  g1_xyzz_t r;
-  r.x = Fq::sub(fq_sqr_ps(M), Fq::dbl(S));
-  r.y = Fq::sub(fq_mul_ps(M, Fq::sub(S, r.x)), fq_mul_ps(W, p.y));
-  r.zz = V; r.zzz = W;
-  return r;
-}
-ZK_HD g1_xyzz_t g1_xyzz_dbl_ps(const g1_xyzz_t &p) {
-  if (g1_xyzz_is_identity(p)) return p;
-  fe_t U = Fq::dbl(p.y), V = fq_sqr_ps(U), W = fq_mul_ps(U, V), S = fq_mul_ps(p.x, V);
-  fe_t M = fq_sqr_ps(p.x); M = Fq::add(Fq::dbl(M), M);
-  g1_xyzz_t r;
-  r.x = Fq::sub(fq_sqr_ps(M), Fq::dbl(S));
-  r.y = Fq::sub(fq_mul_ps(M, Fq::sub(S, r.x)), fq_mul_ps(W, p.y));
-  r.zz = fq_mul_ps(V, p.zz); r.zzz = fq_mul_ps(W, p.zzz);
-  return r;
-}
-ZK_HD void g1_xyzz_madd_ps(g1_xyzz_t &acc, const g1_affine_t &q) {
-  if (g1_affine_is_identity(q)) return;
-  if (g1_xyzz_is_identity(acc)) { acc.x = q.x; acc.y = q.y; acc.zz = Fq::one(); acc.zzz = Fq::one(); return; }
-  fe_t U2 = fq_mul_ps(q.x, acc.zz), S2 = fq_mul_ps(q.y, acc.zzz);
-  fe_t Pd = Fq::sub(U2, acc.x), Rd = Fq::sub(S2, acc.y);
-  if (Fq::is_zero(Pd)) {
-    if (Fq::is_zero(Rd)) acc = g1_xyzz_dbl_affine_ps(q); else acc = g1_xyzz_identity();
-    return;
-  }
-  fe_t PP = fq_sqr_ps(Pd), PPP = fq_mul_ps(Pd, PP), Q = fq_mul_ps(acc.x, PP);
-  fe_t X3 = Fq::sub(Fq::sub(fq_sqr_ps(Rd), PPP), Fq::dbl(Q));
-  fe_t Y3 = Fq::sub(fq_mul_ps(Rd, Fq::sub(Q, X3)), fq_mul_ps(acc.y, PPP));
-  acc.x = X3; acc.y = Y3; acc.zz = fq_mul_ps(acc.zz, PP); acc.zzz = fq_mul_ps(acc.zzz, PPP);
-}
-ZK_HD void g1_xyzz_add_ps(g1_xyzz_t &acc, const g1_xyzz_t &q) {
-  if (g1_xyzz_is_identity(q)) return;
-  if (g1_xyzz_is_identity(acc)) { acc = q; return; }
-  fe_t U1 = fq_mul_ps(acc.x, q.zz), U2 = fq_mul_ps(q.x, acc.zz);
-  fe_t S1 = fq_mul_ps(acc.y, q.zzz), S2 = fq_mul_ps(q.y, acc.zzz);
-  fe_t Pd = Fq::sub(U2, U1), Rd = Fq::sub(S2, S1);
-  if (Fq::is_zero(Pd)) {
-    if (Fq::is_zero(Rd)) acc = g1_xyzz_dbl_ps(acc); else acc = g1_xyzz_identity();
-    return;
-  }
-  fe_t PP = fq_sqr_ps(Pd), PPP = fq_mul_ps(Pd, PP), Q = fq_mul_ps(U1, PP);
-  fe_t X3 = Fq::sub(Fq::sub(fq_sqr_ps(Rd), PPP), Fq::dbl(Q));
-  fe_t Y3 = Fq::sub(fq_mul_ps(Rd, Fq::sub(Q, X3)), fq_mul_ps(S1, PPP));
-  acc.x = X3; acc.y = Y3;
-  acc.zz = fq_mul_ps(fq_mul_ps(acc.zz, q.zz), PP); acc.zzz = fq_mul_ps(fq_mul_ps(acc.zzz, q.zzz), PPP);
-}
+// The field with the product-scanning multiplier as a policy: everything of Fp<P> but mul / sqr.  The point formulas (g1.hpp, g2.hpp) and the
+// kernels take the field as a template argument or name it outright, so which multiplier a call site runs is written at that call site.
+// The inherited members that multiply inside themselves (pow, pow_u64, inv, inv_sgcd, from_canonical, to_canonical) keep calling the base CIOS
+// mul of fp.hpp -- static functions do not dispatch -- which is what those call sites ran before the policy existed; the values are the same.
+template <class P> struct FpPs : Fp<P> {
+  ZK_HD static fe_t mul(const fe_t &a, const fe_t &b) { return mont_mul_ps<P>(a, b); }
+  ZK_HD static fe_t sqr(const fe_t &a) { return mont_sqr_ps<P>(a); }
+};
+using FqPs = FpPs<FqP>;
+using FrPs = FpPs<FrP>;
 
 }  // namespace zk

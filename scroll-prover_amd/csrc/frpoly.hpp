@@ -1,16 +1,13 @@
 // frpoly.hpp -- the Fr polynomial kernels that are not transforms: eval_polynomial, distribute_powers, the element-wise vector operations, the gate-shaped
 // fused evaluation (k_fr_gate_eval), the coset-part interleave and the partial-sum reduction.  Launched by lib_ntt.hip only.  Arithmetic on the 9 x 29-bit
-// unsaturated field (fp29.hpp) with the domain conventions of ntt29.hpp (data x * 2^256, constants y * 2^261), whose fr29_finish they share.
+// unsaturated field (fp29.hpp) with the domain conventions of ntt29.hpp (data x * 2^256, constants y * 2^261), whose fr29_finish they share.  k_fr_gate_eval's products are the
+// chained Fr29::mul_c, as in the NTT butterflies and the bucket accumulation (round 6 A/B: profiles/r06_gate_chain_ab.json).
 #pragma once
 #include "fp29.hpp"
 #include "fp_asm.hpp"
 #include "ntt29.hpp"
 
 namespace zk {
-
-#ifndef ZK_GATE_CHAIN
-#define ZK_GATE_CHAIN true   // k_fr_gate_eval's products as column blocks of chained v_mad (fp29.hpp mul_c), as in the NTT butterflies and the bucket accumulation: 16 instructions fewer per multiplication (round 6 A/B: profiles/r06_gate_chain_ab.json)
-#endif
 
 #if defined(__HIPCC__)
 // ---- eval_polynomial (halo2_proofs::arithmetic::eval_polynomial, step 9 of create_proof: evaluations at x * omega^rot):
@@ -158,10 +155,10 @@ __global__ void __launch_bounds__(256) k_fr_gate_eval(fe_t *dst, GatePlan G, uin
         // unit coefficients (the common case in halo2 gates: a - b, z(wX) prod - z(X) prod): no multiplication by c_j; -1 negates the canonical first
         // factor instead (r - x, zero stays zero), so the term value stays a tight non-negative representative (< r) like every other
         const uint32_t kind = G.coeff_kind[j];
-        if (kind == 0) t = Fr29::mul_t<ZK_GATE_CHAIN>(Fr29::from_sat_plain(x0), G.coeff29[j]);
+        if (kind == 0) t = Fr29::mul_c(Fr29::from_sat_plain(x0), G.coeff29[j]);
         else t = Fr29::from_sat_plain(kind == 2 ? Fr::neg(x0) : x0);
         for (uint32_t q = 1; q < len; q++)
-          t = Fr29::mul_t<ZK_GATE_CHAIN>(t, Fr29::from_sat(g_load(&G.poly[G.factor_poly[f + q]][(i + (uint64_t)(int64_t)G.factor_rot[f + q]) & mask])));
+          t = Fr29::mul_c(t, Fr29::from_sat(g_load(&G.poly[G.factor_poly[f + q]][(i + (uint64_t)(int64_t)G.factor_rot[f + q]) & mask])));
       }
       f += len;
       acc = Fr29::add(acc, t);

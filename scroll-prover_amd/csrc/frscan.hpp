@@ -41,7 +41,7 @@ template <bool REVERSE, bool FQ = false, bool ADD = false> __device__ fe_t block
   __syncthreads();
   fe_t v = x;
   for (uint32_t o = 1; o < FRSCAN_THREADS; o <<= 1) {
-    if (t >= o) v = ADD ? Fr::add(lds_get(cur + (t - o) * 9), v) : FQ ? fq_mul_ps(lds_get(cur + (t - o) * 9), v) : fr_mul_ps(lds_get(cur + (t - o) * 9), v);
+    if (t >= o) v = ADD ? Fr::add(lds_get(cur + (t - o) * 9), v) : FQ ? FqPs::mul(lds_get(cur + (t - o) * 9), v) : FrPs::mul(lds_get(cur + (t - o) * 9), v);
     lds_put(nxt + t * 9, v);
     __syncthreads();
     uint32_t *tmp = cur; cur = nxt; nxt = tmp;
@@ -51,7 +51,7 @@ template <bool REVERSE, bool FQ = false, bool ADD = false> __device__ fe_t block
   __syncthreads();
   return ex;
 }
-template <bool ADD> __device__ __forceinline__ fe_t fr_scan_op(const fe_t &a, const fe_t &b) { return ADD ? Fr::add(a, b) : fr_mul_ps(a, b); }
+template <bool ADD> __device__ __forceinline__ fe_t fr_scan_op(const fe_t &a, const fe_t &b) { return ADD ? Fr::add(a, b) : FrPs::mul(a, b); }
 
 // MODE 0: self-contained (the tile product is inverted by lane 0) -- for short vectors and the last level;
 // MODE 1: tile_prod[b] = product of the tile's non-zero elements;  MODE 2: invert with tile_prod[b] already holding the INVERSE of the
@@ -68,7 +68,7 @@ template <int MODE> __global__ void __launch_bounds__(FRSCAN_THREADS) k_fr_batch
     const uint64_t i = base + j * FRSCAN_THREADS + threadIdx.x;
     a[j] = i < n ? g_load(&data[i]) : Fr::one();
     if (Fr::is_zero(a[j])) { zero_mask |= 1u << j; a[j] = Fr::one(); }
-    run = j ? fr_mul_ps(run, a[j]) : a[j];
+    run = j ? FrPs::mul(run, a[j]) : a[j];
     pre[j] = run;
   }
   fe_t total, total_r;
@@ -81,11 +81,11 @@ template <int MODE> __global__ void __launch_bounds__(FRSCAN_THREADS) k_fr_batch
     __syncthreads();
     inv_t = lds_get(inv_total);
   } else inv_t = g_load(&tile_prod[blockIdx.x]);
-  fe_t inv = fr_mul_ps(fr_mul_ps(inv_t, left), right);   // (product of this thread's elements)^-1
+  fe_t inv = FrPs::mul(FrPs::mul(inv_t, left), right);   // (product of this thread's elements)^-1
 #pragma unroll
   for (int j = FRSCAN_EPT - 1; j >= 0; j--) {
-    const fe_t out = j ? fr_mul_ps(inv, pre[j - 1]) : inv;
-    inv = fr_mul_ps(inv, a[j]);
+    const fe_t out = j ? FrPs::mul(inv, pre[j - 1]) : inv;
+    inv = FrPs::mul(inv, a[j]);
     const uint64_t i = base + (uint64_t)j * FRSCAN_THREADS + threadIdx.x;
     if (i < n) g_store(&data[i], (zero_mask >> j) & 1u ? Fr::zero() : out);
   }
@@ -170,29 +170,29 @@ template <int FINAL> __global__ void __launch_bounds__(FRSCAN_THREADS) k_fr_linr
 #pragma unroll
   for (uint32_t j = 0; j < FRSCAN_EPT; j++) a[j] = lds_get(tile + threadIdx.x * 65 + j * 8);
   __syncthreads();
-  if (FINAL && tile_tot && blockIdx.x > 0 && threadIdx.x == 0) a[0] = Fr::add(a[0], fr_mul_ps(m, g_load(&tile_tot[blockIdx.x - 1])));
+  if (FINAL && tile_tot && blockIdx.x > 0 && threadIdx.x == 0) a[0] = Fr::add(a[0], FrPs::mul(m, g_load(&tile_tot[blockIdx.x - 1])));
   fe_t run = a[0];
 #pragma unroll
-  for (uint32_t j = 1; j < FRSCAN_EPT; j++) run = Fr::add(a[j], fr_mul_ps(m, run));
+  for (uint32_t j = 1; j < FRSCAN_EPT; j++) run = Fr::add(a[j], FrPs::mul(m, run));
   // inclusive scan of the thread offsets with multiplier m^8 per thread step
-  fe_t pw = fr_sqr_ps(fr_sqr_ps(fr_sqr_ps(m)));   // m^8
+  fe_t pw = FrPs::sqr(FrPs::sqr(FrPs::sqr(m)));   // m^8
   uint32_t *cur = buf, *nxt = buf + FRSCAN_THREADS * 9;
   const uint32_t t = threadIdx.x;
   fe_t v = run;
   lds_put(cur + t * 9, v);
   __syncthreads();
   for (uint32_t o = 1; o < FRSCAN_THREADS; o <<= 1) {
-    if (t >= o) v = Fr::add(v, fr_mul_ps(lds_get(cur + (t - o) * 9), pw));
+    if (t >= o) v = Fr::add(v, FrPs::mul(lds_get(cur + (t - o) * 9), pw));
     lds_put(nxt + t * 9, v);
     __syncthreads();
     uint32_t *tmp = cur; cur = nxt; nxt = tmp;
-    pw = fr_sqr_ps(pw);
+    pw = FrPs::sqr(pw);
   }
   if (!FINAL) { if (t == FRSCAN_THREADS - 1) g_store(&tile_tot[blockIdx.x], v); return; }
   fe_t P = t ? lds_get(cur + (t - 1) * 9) : Fr::zero();   // value of the recurrence just before this thread's run
   __syncthreads();   // every thread has its carried-in value before the tile region is overwritten with the results
 #pragma unroll
-  for (uint32_t j = 0; j < FRSCAN_EPT; j++) { P = Fr::add(a[j], fr_mul_ps(m, P)); lds_put(tile + threadIdx.x * 65 + j * 8, P); }
+  for (uint32_t j = 0; j < FRSCAN_EPT; j++) { P = Fr::add(a[j], FrPs::mul(m, P)); lds_put(tile + threadIdx.x * 65 + j * 8, P); }
   __syncthreads();
 #pragma unroll
   for (uint32_t j = 0; j < FRSCAN_EPT; j++) {
@@ -206,7 +206,7 @@ template <int FINAL> __global__ void __launch_bounds__(FRSCAN_THREADS) k_fr_linr
 // ---- group::Curve::batch_normalize(&[G1], &mut [G1Affine]) [EXT-recalled halo2curves / group crate; create_proof turns each vector of
 // projective commitments into affine points with it before they enter the transcript, SURVEY 8f-3]: out[i] = (X / Z^2, Y / Z^3), the
 // identity (Z = 0) becomes (0, 0).  Montgomery's trick per 256-point tile: the Z coordinates are scanned from both ends through LDS
-// (zeros replaced by one), lane 0 inverts the tile product once (Euclidean inverse), every thread finishes with two multiplications.
+// (zeros replaced by one), lane 0 inverts the tile product once (division-step inverse, inv_sgcd), every thread finishes with two multiplications.
 __global__ void __launch_bounds__(FRSCAN_THREADS) k_g1_batch_normalize(const g1_jac_t *__restrict__ in, g1_affine_t *__restrict__ out, uint64_t n) {
   __shared__ uint32_t buf[2 * FRSCAN_THREADS * 9];
   __shared__ uint32_t inv_total[8];
@@ -222,8 +222,8 @@ __global__ void __launch_bounds__(FRSCAN_THREADS) k_g1_batch_normalize(const g1_
   if (i >= n) return;
   g1_affine_t r; r.x = Fq::zero(); r.y = Fq::zero();
   if (!ident) {
-    const fe_t zi = fq_mul_ps(fq_mul_ps(lds_get(inv_total), left), right), zi2 = fq_sqr_ps(zi);
-    r.x = fq_mul_ps(g_load(&in[i].x), zi2); r.y = fq_mul_ps(g_load(&in[i].y), fq_mul_ps(zi2, zi));
+    const fe_t zi = FqPs::mul(FqPs::mul(lds_get(inv_total), left), right), zi2 = FqPs::sqr(zi);
+    r.x = FqPs::mul(g_load(&in[i].x), zi2); r.y = FqPs::mul(g_load(&in[i].y), FqPs::mul(zi2, zi));
   }
   g_store(&out[i].x, r.x); g_store(&out[i].y, r.y);
 }

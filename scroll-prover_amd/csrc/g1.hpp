@@ -25,58 +25,61 @@ ZK_HD g1_xyzz_t g1_xyzz_from_affine(const g1_affine_t &p) {
 }
 ZK_HD g1_affine_t g1_affine_neg(const g1_affine_t &p) { g1_affine_t r; r.x = p.x; r.y = Fq::neg(p.y); return r; }  // neg(0) = 0 keeps identity
 
+// The four formulas below take the field flavour as a template argument: Fq (the plain C++ CIOS multiplier of fp.hpp; the default, and what
+// g1_xyzz_mul_small runs in the fixed-base table builder) or FqPs (the product-scanning multiplier of fp_asm.hpp; what the kernels name).  Both
+// return the same fully reduced Montgomery values.
 // 2 * (affine point), mdbl-2008-s.  p must not be the identity.
-ZK_HD g1_xyzz_t g1_xyzz_dbl_affine(const g1_affine_t &p) {
-  fe_t U = Fq::dbl(p.y), V = Fq::sqr(U), W = Fq::mul(U, V), S = Fq::mul(p.x, V);
-  fe_t M = Fq::sqr(p.x); M = Fq::add(Fq::dbl(M), M);
+template <class F = Fq> ZK_HD g1_xyzz_t g1_xyzz_dbl_affine(const g1_affine_t &p) {
+  fe_t U = F::dbl(p.y), V = F::sqr(U), W = F::mul(U, V), S = F::mul(p.x, V);
+  fe_t M = F::sqr(p.x); M = F::add(F::dbl(M), M);
   g1_xyzz_t r;
-  r.x = Fq::sub(Fq::sqr(M), Fq::dbl(S));
-  r.y = Fq::sub(Fq::mul(M, Fq::sub(S, r.x)), Fq::mul(W, p.y));
+  r.x = F::sub(F::sqr(M), F::dbl(S));
+  r.y = F::sub(F::mul(M, F::sub(S, r.x)), F::mul(W, p.y));
   r.zz = V; r.zzz = W;
   return r;
 }
 // dbl-2008-s-1
-ZK_HD g1_xyzz_t g1_xyzz_dbl(const g1_xyzz_t &p) {
+template <class F = Fq> ZK_HD g1_xyzz_t g1_xyzz_dbl(const g1_xyzz_t &p) {
   if (g1_xyzz_is_identity(p)) return p;
-  fe_t U = Fq::dbl(p.y), V = Fq::sqr(U), W = Fq::mul(U, V), S = Fq::mul(p.x, V);
-  fe_t M = Fq::sqr(p.x); M = Fq::add(Fq::dbl(M), M);
+  fe_t U = F::dbl(p.y), V = F::sqr(U), W = F::mul(U, V), S = F::mul(p.x, V);
+  fe_t M = F::sqr(p.x); M = F::add(F::dbl(M), M);
   g1_xyzz_t r;
-  r.x = Fq::sub(Fq::sqr(M), Fq::dbl(S));
-  r.y = Fq::sub(Fq::mul(M, Fq::sub(S, r.x)), Fq::mul(W, p.y));
-  r.zz = Fq::mul(V, p.zz); r.zzz = Fq::mul(W, p.zzz);
+  r.x = F::sub(F::sqr(M), F::dbl(S));
+  r.y = F::sub(F::mul(M, F::sub(S, r.x)), F::mul(W, p.y));
+  r.zz = F::mul(V, p.zz); r.zzz = F::mul(W, p.zzz);
   return r;
 }
 // acc += q (affine), madd-2008-s with the exceptional cases (identity operands, q == +-acc)
-ZK_HD void g1_xyzz_madd(g1_xyzz_t &acc, const g1_affine_t &q) {
+template <class F = Fq> ZK_HD void g1_xyzz_madd(g1_xyzz_t &acc, const g1_affine_t &q) {
   if (g1_affine_is_identity(q)) return;
-  if (g1_xyzz_is_identity(acc)) { acc.x = q.x; acc.y = q.y; acc.zz = Fq::one(); acc.zzz = Fq::one(); return; }
-  fe_t U2 = Fq::mul(q.x, acc.zz), S2 = Fq::mul(q.y, acc.zzz);
-  fe_t Pd = Fq::sub(U2, acc.x), Rd = Fq::sub(S2, acc.y);
-  if (Fq::is_zero(Pd)) {
-    if (Fq::is_zero(Rd)) acc = g1_xyzz_dbl_affine(q); else acc = g1_xyzz_identity();
+  if (g1_xyzz_is_identity(acc)) { acc.x = q.x; acc.y = q.y; acc.zz = F::one(); acc.zzz = F::one(); return; }
+  fe_t U2 = F::mul(q.x, acc.zz), S2 = F::mul(q.y, acc.zzz);
+  fe_t Pd = F::sub(U2, acc.x), Rd = F::sub(S2, acc.y);
+  if (F::is_zero(Pd)) {
+    if (F::is_zero(Rd)) acc = g1_xyzz_dbl_affine<F>(q); else acc = g1_xyzz_identity();
     return;
   }
-  fe_t PP = Fq::sqr(Pd), PPP = Fq::mul(Pd, PP), Q = Fq::mul(acc.x, PP);
-  fe_t X3 = Fq::sub(Fq::sub(Fq::sqr(Rd), PPP), Fq::dbl(Q));
-  fe_t Y3 = Fq::sub(Fq::mul(Rd, Fq::sub(Q, X3)), Fq::mul(acc.y, PPP));
-  acc.x = X3; acc.y = Y3; acc.zz = Fq::mul(acc.zz, PP); acc.zzz = Fq::mul(acc.zzz, PPP);
+  fe_t PP = F::sqr(Pd), PPP = F::mul(Pd, PP), Q = F::mul(acc.x, PP);
+  fe_t X3 = F::sub(F::sub(F::sqr(Rd), PPP), F::dbl(Q));
+  fe_t Y3 = F::sub(F::mul(Rd, F::sub(Q, X3)), F::mul(acc.y, PPP));
+  acc.x = X3; acc.y = Y3; acc.zz = F::mul(acc.zz, PP); acc.zzz = F::mul(acc.zzz, PPP);
 }
 // acc += q (XYZZ), add-2008-s with the exceptional cases
-ZK_HD void g1_xyzz_add(g1_xyzz_t &acc, const g1_xyzz_t &q) {
+template <class F = Fq> ZK_HD void g1_xyzz_add(g1_xyzz_t &acc, const g1_xyzz_t &q) {
   if (g1_xyzz_is_identity(q)) return;
   if (g1_xyzz_is_identity(acc)) { acc = q; return; }
-  fe_t U1 = Fq::mul(acc.x, q.zz), U2 = Fq::mul(q.x, acc.zz);
-  fe_t S1 = Fq::mul(acc.y, q.zzz), S2 = Fq::mul(q.y, acc.zzz);
-  fe_t Pd = Fq::sub(U2, U1), Rd = Fq::sub(S2, S1);
-  if (Fq::is_zero(Pd)) {
-    if (Fq::is_zero(Rd)) acc = g1_xyzz_dbl(acc); else acc = g1_xyzz_identity();
+  fe_t U1 = F::mul(acc.x, q.zz), U2 = F::mul(q.x, acc.zz);
+  fe_t S1 = F::mul(acc.y, q.zzz), S2 = F::mul(q.y, acc.zzz);
+  fe_t Pd = F::sub(U2, U1), Rd = F::sub(S2, S1);
+  if (F::is_zero(Pd)) {
+    if (F::is_zero(Rd)) acc = g1_xyzz_dbl<F>(acc); else acc = g1_xyzz_identity();
     return;
   }
-  fe_t PP = Fq::sqr(Pd), PPP = Fq::mul(Pd, PP), Q = Fq::mul(U1, PP);
-  fe_t X3 = Fq::sub(Fq::sub(Fq::sqr(Rd), PPP), Fq::dbl(Q));
-  fe_t Y3 = Fq::sub(Fq::mul(Rd, Fq::sub(Q, X3)), Fq::mul(S1, PPP));
+  fe_t PP = F::sqr(Pd), PPP = F::mul(Pd, PP), Q = F::mul(U1, PP);
+  fe_t X3 = F::sub(F::sub(F::sqr(Rd), PPP), F::dbl(Q));
+  fe_t Y3 = F::sub(F::mul(Rd, F::sub(Q, X3)), F::mul(S1, PPP));
   acc.x = X3; acc.y = Y3;
-  acc.zz = Fq::mul(Fq::mul(acc.zz, q.zz), PP); acc.zzz = Fq::mul(Fq::mul(acc.zzz, q.zzz), PPP);
+  acc.zz = F::mul(F::mul(acc.zz, q.zz), PP); acc.zzz = F::mul(F::mul(acc.zzz, q.zzz), PPP);
 }
 // XYZZ -> affine (one field inversion)
 ZK_HD g1_affine_t g1_xyzz_to_affine(const g1_xyzz_t &p) {
@@ -102,10 +105,10 @@ ZK_HD g1_xyzz_t g1_jac_to_xyzz(const g1_jac_t &p) {
   r.x = p.x; r.y = p.y; r.zz = Fq::sqr(p.z); r.zzz = Fq::mul(r.zz, p.z);
   return r;
 }
-// k * p for a small unsigned k (double-and-add from the top bit); used by the bucket-reduce kernel
-ZK_HD g1_xyzz_t g1_xyzz_mul_small(const g1_xyzz_t &p, uint32_t k) {
+// k * p for a small unsigned k (double-and-add from the top bit); the fixed-base table builder runs it on the default, the CIOS multiplier
+template <class F = Fq> ZK_HD g1_xyzz_t g1_xyzz_mul_small(const g1_xyzz_t &p, uint32_t k) {
   g1_xyzz_t acc = g1_xyzz_identity();
-  for (int i = 31; i >= 0; i--) { acc = g1_xyzz_dbl(acc); if ((k >> i) & 1) g1_xyzz_add(acc, p); }
+  for (int i = 31; i >= 0; i--) { acc = g1_xyzz_dbl<F>(acc); if ((k >> i) & 1) g1_xyzz_add<F>(acc, p); }
   return acc;
 }
 

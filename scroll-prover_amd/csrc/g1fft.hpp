@@ -19,14 +19,14 @@ namespace zk {
 #ifdef __HIPCC__
 
 // k * p for a canonical (non-Montgomery) 256-bit k: fixed 2-bit windows from the top, table {p, 2p, 3p} in registers.  Uniform schedule
-// across the wavefront (the digit only selects the table entry), the exceptional cases are handled inside g1_xyzz_add_ps.
+// across the wavefront (the digit only selects the table entry), the exceptional cases are handled inside g1_xyzz_add<FqPs>.
 __device__ __noinline__ g1_xyzz_t g1_xyzz_mul_fr(const g1_xyzz_t &p, const fe_t &k) {
   if (g1_xyzz_is_identity(p)) return p;
-  const g1_xyzz_t p2 = g1_xyzz_dbl_ps(p);
-  g1_xyzz_t p3 = p2; g1_xyzz_add_ps(p3, p);
+  const g1_xyzz_t p2 = g1_xyzz_dbl<FqPs>(p);
+  g1_xyzz_t p3 = p2; g1_xyzz_add<FqPs>(p3, p);
   g1_xyzz_t acc = g1_xyzz_identity();
   for (int i = 126; i >= 0; i--) {   // r < 2^254: digit 127 is always zero
-    acc = g1_xyzz_dbl_ps(g1_xyzz_dbl_ps(acc));
+    acc = g1_xyzz_dbl<FqPs>(g1_xyzz_dbl<FqPs>(acc));
     const uint32_t d = (k.l[i >> 4] >> ((i & 15) * 2)) & 3u;
     if (d) {
       g1_xyzz_t sel;
@@ -37,7 +37,7 @@ __device__ __noinline__ g1_xyzz_t g1_xyzz_mul_fr(const g1_xyzz_t &p, const fe_t 
         sel.zz.l[j] = d == 1 ? p.zz.l[j] : d == 2 ? p2.zz.l[j] : p3.zz.l[j];
         sel.zzz.l[j] = d == 1 ? p.zzz.l[j] : d == 2 ? p2.zzz.l[j] : p3.zzz.l[j];
       }
-      g1_xyzz_add_ps(acc, sel);
+      g1_xyzz_add<FqPs>(acc, sel);
     }
   }
   return acc;
@@ -117,7 +117,7 @@ template <int JAC> __global__ void __launch_bounds__(256) k_g1fft_load(const voi
     const g1_jac_t *src = static_cast<const g1_jac_t *>(in) + i;
     g1_jac_t q; q.x = g_load(&src->x); q.y = g_load(&src->y); q.z = g_load(&src->z);
     if (Fq::is_zero(q.z)) v = g1_xyzz_identity();
-    else { v.x = q.x; v.y = q.y; v.zz = fq_sqr_ps(q.z); v.zzz = fq_mul_ps(v.zz, q.z); }
+    else { v.x = q.x; v.y = q.y; v.zz = FqPs::sqr(q.z); v.zzz = FqPs::mul(v.zz, q.z); }
   } else {
     const g1_affine_t *src = static_cast<const g1_affine_t *>(in) + i;
     g1_affine_t q; q.x = g_load(&src->x); q.y = g_load(&src->y);
@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   g1_xyzz29_t wb = g1_xyzz29_from_sat(g1fft_load_xyzz(&work[ib]));
   if (j) {
     fe_t one_c = Fr::zero(); one_c.l[0] = 1;
-    const fe_t k = fr_mul_ps(g_load(&tw[(uint64_t)j << (log_n - 1 - s)]), one_c);   // Montgomery -> canonical
+    const fe_t k = FrPs::mul(g_load(&tw[(uint64_t)j << (log_n - 1 - s)]), one_c);   // Montgomery -> canonical
     wb = g1_xyzz29_mul_scalar(wb, k);
   }
   // `a` is loaded AFTER the scalar multiple (inlined: no call, no scratch memory): 32 registers less across the ladder, the kernel stays at
@@ -155,7 +155,7 @@ template <int JAC> __global__ void __launch_bounds__(256) k_g1fft_store(const g1
   g1_xyzz_t v = g1fft_load_xyzz(&work[i]);
   if (has_scale) {
     fe_t one_c = Fr::zero(); one_c.l[0] = 1;
-    v = g1_xyzz29_to_sat(g1_xyzz29_mul_scalar(g1_xyzz29_from_sat(v), fr_mul_ps(scale, one_c)));
+    v = g1_xyzz29_to_sat(g1_xyzz29_mul_scalar(g1_xyzz29_from_sat(v), FrPs::mul(scale, one_c)));
   }
   const g1_jac_t r = g1_xyzz_to_jac_normalised(v);
   if (JAC) { g1_jac_t *dst = static_cast<g1_jac_t *>(out) + i; g_store(&dst->x, r.x); g_store(&dst->y, r.y); g_store(&dst->z, r.z); }

@@ -4,8 +4,8 @@
 // g2_affine_t = {x: {c0, c1}, y: {c0, c1}} = 128 B of Montgomery limbs == halo2curves bn256::G2Affine == the `g2` / `s_g2`
 // fields of a RawBytes params file; identity = all zero.  Same XYZZ formulas as g1.hpp with Fq2 in the place of Fq
 // (madd-2008-s / add-2008-s / dbl-2008-s-1 / mdbl-2008-s), every exceptional case handled.  The point functions take the Fq2 flavour
-// as a template argument: Fq2 (plain C++ CIOS multiplier of fp.hpp; k_g2_mul, one lane) or Fq2ps (the product-scanning multiplier of
-// fp_asm.hpp; the MSM kernels).  Both return the same fully reduced Montgomery values.
+// as a template argument: Fq2 = Fq2T<Fq> (plain C++ CIOS multiplier of fp.hpp; k_g2_mul, one lane) or Fq2ps = Fq2T<FqPs> (the product-scanning
+// multiplier of fp_asm.hpp; the MSM kernels).  Both return the same fully reduced Montgomery values.
 // ZK_G2_DEVICE_ONLY: the translation unit wants the functions, not k_g2_mul (that kernel belongs to lib_aux.hip).
 #pragma once
 #include "fp.hpp"
@@ -17,8 +17,8 @@ struct fe2_t { fe_t c0, c1; };
 struct alignas(16) g2_affine_t { fe2_t x, y; };
 struct g2_xyzz_t { fe2_t x, y, zz, zzz; };
 
-template <bool PS> struct Fq2T {
-  ZK_HD static fe_t fmul(const fe_t &a, const fe_t &b) { return PS ? fq_mul_ps(a, b) : Fq::mul(a, b); }
+template <class F> struct Fq2T {   // F: Fq or FqPs, the base field whose mul the products below take
+  ZK_HD static fe_t fmul(const fe_t &a, const fe_t &b) { return F::mul(a, b); }
   ZK_HD static fe2_t zero() { fe2_t r; r.c0 = Fq::zero(); r.c1 = Fq::zero(); return r; }
   ZK_HD static fe2_t one() { fe2_t r; r.c0 = Fq::one(); r.c1 = Fq::zero(); return r; }
   ZK_HD static bool is_zero(const fe2_t &a) { return Fq::is_zero(a.c0) && Fq::is_zero(a.c1); }
@@ -39,8 +39,8 @@ template <bool PS> struct Fq2T {
     fe2_t r; r.c0 = fmul(a.c0, n); r.c1 = fmul(Fq::neg(a.c1), n); return r;
   }
 };
-using Fq2 = Fq2T<false>;
-using Fq2ps = Fq2T<true>;
+using Fq2 = Fq2T<Fq>;
+using Fq2ps = Fq2T<FqPs>;
 
 ZK_HD bool g2_affine_is_identity(const g2_affine_t &p) { return Fq2::is_zero(p.x) && Fq2::is_zero(p.y); }
 ZK_HD g2_xyzz_t g2_xyzz_identity() { g2_xyzz_t r; r.x = Fq2::zero(); r.y = Fq2::zero(); r.zz = Fq2::zero(); r.zzz = Fq2::zero(); return r; }

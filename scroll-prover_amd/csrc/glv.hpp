@@ -96,7 +96,7 @@ ZK_HD g1_xyzz29_t g1_xyzz29_mul_glv(const g1_xyzz29_t &p, const fe_t &k) {
   glv_recode(k1, code1); glv_recode(k2, code2);
   fe29_t beta; for (int i = 0; i < 9; i++) beta.l[i] = GlvP::beta29(i);
   const g1_xyzz29_t p2 = g1_xyzz29_dbl(p);                     // x < 9.1 p, y < 5.4 p (limbs <= 2^29 + 8), zz / zzz tight
-  const fe29_t bx1 = FQ29_MUL(p.x, beta), bx2 = FQ29_MUL(p2.x, beta);   // tight
+  const fe29_t bx1 = Fq29::mul_c(p.x, beta), bx2 = Fq29::mul_c(p2.x, beta);   // tight
   // -y is formed when a digit asks for it (8p - y, limbs <= 2^29 + 8: a multiplication operand of the addition): two fewer table entries in
   // registers keep the kernel at two waves per SIMD
   g1_xyzz29_t acc = g1_xyzz29_identity();

@@ -15,7 +15,7 @@
 //     k_msm_segfix      the same as one segmented reduction by key over the partial records
 //   5 k_msm_bucket_reduce / k_msm_tree_sum   sum_b (b+1) * B[b] by short chunked running sums, then multi-block
 //                       wavefront-shuffle + LDS trees
-//   6 k_msm_final       Horner over windows (none with window tables), normalise to (x, y, 1) with a one-lane Euclidean inverse
+//   6 k_msm_final       Horner over windows (none with window tables), normalise to (x, y, 1) with a one-lane division-step inverse (Fq::inv_sgcd)
 //
 // Steps 3-6 are group-agnostic: the walk, k_msm_segfix and the tail kernels are templates over a point-operations policy (record type,
 // load / store / shuffle, addition and doubling, identity, result emission).  G1Ops below is G1 on the 29-bit field (g1_xyzz29_add / _dbl,
@@ -125,15 +125,15 @@ __device__ __forceinline__ g1_xyzz29_t g1_xyzz29_dbl_q4(const g1_xyzz29_t &a) {
   const fe29_t xt = Fq29::reduce_small(Fq29::normalise(a.x));   // tight, < 2 p
   const fe29_t yc = Fq29::carry(a.y);                           // limbs <= 2^29 + 2, value < 6.1 p
   const fe29_t U = Fq29::dbl(yc);                               // limbs <= 2^30 + 4, < 12.2 p
-  fe29_t m = FQ29_MUL(quad_sel(q, U, xt, U, xt), quad_sel(q, U, xt, U, xt));
+  fe29_t m = Fq29::mul_c(quad_sel(q, U, xt, U, xt), quad_sel(q, U, xt, U, xt));
   const fe29_t V = quad_bcast<0>(m), xx = quad_bcast<1>(m);
   const fe29_t M = Fq29::carry(Fq29::add(Fq29::dbl(xx), xx));   // 3 x^2, limbs <= 2^29 + 8, < 3.3 p
-  m = FQ29_MUL(quad_sel(q, U, xt, M, V), quad_sel(q, V, V, M, a.zz));
+  m = Fq29::mul_c(quad_sel(q, U, xt, M, V), quad_sel(q, V, V, M, a.zz));
   const fe29_t W = quad_bcast<0>(m), S = quad_bcast<1>(m), MM = quad_bcast<2>(m), ZZ3 = quad_bcast<3>(m);
   g1_xyzz29_t r;
   r.x = Fq29::sub8(MM, Fq29::dbl(S));                           // < 1.1 p + 8 p
   const fe29_t t = Fq29::sub16(S, r.x);                          // < 17.1 p
-  m = FQ29_MUL(quad_sel(q, M, W, W, W), quad_sel(q, t, yc, a.zzz, a.zzz));
+  m = Fq29::mul_c(quad_sel(q, M, W, W, W), quad_sel(q, t, yc, a.zzz, a.zzz));
   r.y = Fq29::sub4(quad_bcast<0>(m), quad_bcast<1>(m));         // < 1.4 p + 4 p
   r.zz = ZZ3; r.zzz = quad_bcast<2>(m);
   return r;
@@ -142,13 +142,13 @@ __device__ __forceinline__ void g1_xyzz29_add_q4(g1_xyzz29_t &acc, const g1_xyzz
   if (g1_xyzz29_is_identity(o)) return;
   if (g1_xyzz29_is_identity(acc)) { acc = o; return; }
   const uint32_t q = threadIdx.x & 3u;
-  fe29_t m = FQ29_MUL(quad_sel(q, acc.x, acc.y, o.x, o.y), quad_sel(q, o.zz, o.zzz, acc.zz, acc.zzz));
+  fe29_t m = Fq29::mul_c(quad_sel(q, acc.x, acc.y, o.x, o.y), quad_sel(q, o.zz, o.zzz, acc.zz, acc.zzz));
   const fe29_t U1 = quad_bcast<0>(m), S1 = quad_bcast<1>(m), U2 = quad_bcast<2>(m), S2 = quad_bcast<3>(m);   // tight, < 1.1 p
   const fe29_t Pd = Fq29::sub4(U2, U1), Rd = Fq29::sub4(S2, S1);                                              // < 5.1 p
-  m = FQ29_MUL(quad_sel(q, Pd, Rd, acc.zz, acc.zzz), quad_sel(q, Pd, Rd, o.zz, o.zzz));
+  m = Fq29::mul_c(quad_sel(q, Pd, Rd, acc.zz, acc.zzz), quad_sel(q, Pd, Rd, o.zz, o.zzz));
   const fe29_t PP = quad_bcast<0>(m), RR = quad_bcast<1>(m), ZZ12 = quad_bcast<2>(m), ZZZ12 = quad_bcast<3>(m);
   const fe29_t one = Fq29::one();
-  m = FQ29_MUL(quad_sel(q, Pd, U1, ZZ12, Rd), quad_sel(q, PP, PP, PP, one));
+  m = Fq29::mul_c(quad_sel(q, Pd, U1, ZZ12, Rd), quad_sel(q, PP, PP, PP, one));
   const fe29_t PPP = quad_bcast<0>(m), Q = quad_bcast<1>(m), ZZ3 = quad_bcast<2>(m), Rone = quad_bcast<3>(m);
   if (Fq29::is_zero_tight(ZZ3)) {   // Pd == 0 (both zz != 0): o == +-acc, doubling or annihilation
     if (Fq29::is_zero_tight(Rone)) acc = g1_xyzz29_dbl_q4(acc);
@@ -157,7 +157,7 @@ __device__ __forceinline__ void g1_xyzz29_add_q4(g1_xyzz29_t &acc, const g1_xyzz
   }
   const fe29_t X3 = Fq29::sub4_8(RR, PPP, Fq29::dbl(Q));                                                      // 13.2 p, one carry
   const fe29_t t = Fq29::sub16(Q, X3);
-  m = FQ29_MUL(quad_sel(q, Rd, S1, ZZZ12, ZZZ12), quad_sel(q, t, PPP, PPP, PPP));
+  m = Fq29::mul_c(quad_sel(q, Rd, S1, ZZZ12, ZZZ12), quad_sel(q, t, PPP, PPP, PPP));
   acc.x = X3; acc.y = Fq29::sub4(quad_bcast<0>(m), quad_bcast<1>(m));                                         // < 1.6 p + 4 p
   acc.zz = ZZ3; acc.zzz = quad_bcast<2>(m);
 }
@@ -171,7 +171,7 @@ __device__ __forceinline__ void msm_emit_result(const g1_xyzz_t &acc, g1_jac_t *
   // folded (and normalised once) by k_g1_sum
   g1_jac_t r;
   if (g1_xyzz_is_identity(acc)) { r.x = Fq::zero(); r.y = Fq::zero(); r.z = Fq::zero(); }
-  else { r.x = fq_mul_ps(acc.x, fq_sqr_ps(acc.zz)); r.y = fq_mul_ps(acc.y, fq_sqr_ps(acc.zzz)); r.z = acc.zzz; }
+  else { r.x = FqPs::mul(acc.x, FqPs::sqr(acc.zz)); r.y = FqPs::mul(acc.y, FqPs::sqr(acc.zzz)); r.z = acc.zzz; }
   *out = r;
 }
 
@@ -531,7 +531,7 @@ template <class G, class B> __device__ __forceinline__ void msm_segment_walk(con
 }
 // G1 bases: 64-byte affine points; with window tables (row_stride != 0) the entry payload (w << nshift) | i names row w of the precomputed
 // table T[w][.] = 2^(c w) P (rows row_stride points apart).  The accumulator lives in the 9 x 29-bit unsaturated field (g1_29.hpp): one
-// v_mad_u64_u32 per limb product, chained explicitly (fp29.hpp mac_*), no carry chain.
+// v_mad_u64_u32 per limb product, chained explicitly (fp29.hpp mul_c / sqr_c / mul_sub_c), no carry chain.
 struct G1Bases {
   using base_t = g1_affine_t;
   const g1_affine_t *__restrict__ bases; uint32_t nshift; uint64_t row_stride;
@@ -542,9 +542,9 @@ struct G1Bases {
     return &bases[(uint64_t)w * row_stride + (gi & ((1u << nshift) - 1))];
   }
   __device__ __forceinline__ g1_affine_t load(uint32_t e) const { return load_affine(base_of(e)); }
-  __device__ __forceinline__ void madd(g1_xyzz29_t &acc, const g1_affine_t &p, bool neg) const { g1_xyzz29_madd<true, true, true>(acc, p, neg); }
+  __device__ __forceinline__ void madd(g1_xyzz29_t &acc, const g1_affine_t &p, bool neg) const { g1_xyzz29_madd(acc, p, neg); }
 };
-// the walk's accumulator keeps x negated (g1_29.hpp, NEGX); every flush -- bucket sum or partial -- hands the plain record on, so nothing after
+// the walk's accumulator keeps x negated (the convention of g1_xyzz29_madd, g1_29.hpp); every flush -- bucket sum or partial -- hands the plain record on, so nothing after
 // k_msm_accumulate sees the difference (a dozen instructions per flushed record, against 55 per addition saved)
 struct G1AccOps : G1Ops {
   static __device__ __forceinline__ void store(rec_t *p, rec_t v) { g1_xyzz29_negx_to_plain(v); store_xyzz29(p, v); }
@@ -759,7 +759,7 @@ template <class G, int Q> __global__ void __launch_bounds__(64) k_msm_final(cons
 __global__ void k_g1_sum(const g1_jac_t *__restrict__ pts, uint32_t n, g1_jac_t *__restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   g1_xyzz_t acc = g1_xyzz_identity();
-  for (uint32_t i = 0; i < n; i++) { g1_jac_t p = pts[i]; g1_xyzz_add_ps(acc, g1_jac_to_xyzz(p)); }
+  for (uint32_t i = 0; i < n; i++) { g1_jac_t p = pts[i]; g1_xyzz_add<FqPs>(acc, g1_jac_to_xyzz(p)); }
   *out = g1_xyzz_to_jac_normalised(acc);
 }
 
@@ -767,11 +767,11 @@ __global__ void k_g1_sum(const g1_jac_t *__restrict__ pts, uint32_t n, g1_jac_t 
 __global__ void k_g1_sum_strided(const g1_jac_t *__restrict__ pts, uint32_t count, uint32_t stride, g1_jac_t *__restrict__ out, int normalise) {
   if (threadIdx.x != 0) return;
   g1_xyzz_t acc = g1_xyzz_identity();
-  for (uint32_t k = 0; k < count; k++) { g1_jac_t p = pts[(size_t)k * stride + blockIdx.x]; g1_xyzz_add_ps(acc, g1_jac_to_xyzz(p)); }
+  for (uint32_t k = 0; k < count; k++) { g1_jac_t p = pts[(size_t)k * stride + blockIdx.x]; g1_xyzz_add<FqPs>(acc, g1_jac_to_xyzz(p)); }
   if (normalise) { out[blockIdx.x] = g1_xyzz_to_jac_normalised(acc); return; }
   g1_jac_t r;
   if (g1_xyzz_is_identity(acc)) { r.x = Fq::zero(); r.y = Fq::zero(); r.z = Fq::zero(); }
-  else { r.x = fq_mul_ps(acc.x, fq_sqr_ps(acc.zz)); r.y = fq_mul_ps(acc.y, fq_sqr_ps(acc.zzz)); r.z = acc.zzz; }
+  else { r.x = FqPs::mul(acc.x, FqPs::sqr(acc.zz)); r.y = FqPs::mul(acc.y, FqPs::sqr(acc.zzz)); r.z = acc.zzz; }
   out[blockIdx.x] = r;
 }
 
@@ -790,7 +790,7 @@ __global__ void __launch_bounds__(256) k_g1_validate(const g1_affine_t *__restri
     }
     if (ok) {
       fe_t three = Fq::zero(); three.l[0] = 3; three = Fq::from_canonical(three);
-      ok = Fq::eq(fq_sqr_ps(p.y), Fq::add(fq_mul_ps(fq_sqr_ps(p.x), p.x), three));
+      ok = Fq::eq(FqPs::sqr(p.y), Fq::add(FqPs::mul(FqPs::sqr(p.x), p.x), three));
     }
     if (!ok) local++;
   }
@@ -799,7 +799,7 @@ __global__ void __launch_bounds__(256) k_g1_validate(const g1_affine_t *__restri
 
 // ---- window precomputation for a registered basis: T[w][i] = 2^(c w) * P_i, affine, w < W (row 0 = the basis itself).
 // One thread per point and c doublings per row; the conversion back to affine coordinates shares ONE inversion per row among the 256
-// points of a workgroup (Montgomery's trick through the LDS scans of frscan.hpp, the tile product inverted by lane 0's Euclidean
+// points of a workgroup (Montgomery's trick through the LDS scans of frscan.hpp, the tile product inverted by lane 0's division-step
 // inverse): ~210 field multiplications per point and row instead of ~550 with a Fermat ladder per point (3.05 s per 2^26 basis before).
 // One-off cost at registration.
 __global__ void __launch_bounds__(FRSCAN_THREADS) k_srs_precompute(const g1_affine_t *__restrict__ base, g1_affine_t *__restrict__ table, uint64_t n, uint32_t W, uint32_t c) {
@@ -815,12 +815,12 @@ __global__ void __launch_bounds__(FRSCAN_THREADS) k_srs_precompute(const g1_affi
     g1_xyzz_t acc = g1_xyzz_identity();
     fe_t z = Fq::one();
     if (!ident && !dead) {
-      acc = g1_xyzz_dbl_affine_ps(P);
-      for (uint32_t k = 1; k < c; k++) acc = g1_xyzz_dbl_ps(acc);
+      acc = g1_xyzz_dbl_affine<FqPs>(P);
+      for (uint32_t k = 1; k < c; k++) acc = g1_xyzz_dbl<FqPs>(acc);
       // BN254 G1 has prime order and no 2-torsion: doubling a non-identity CURVE point never gives the identity, so ZZ ZZZ != 0.  Bases are
       // not validated at registration (mi355_srs_register_host / _dev), and an input with y = 0 or off the curve can reach ZZ ZZZ = 0: such a
       // point becomes the identity in this row and every later one, and must not zero the shared product of its 255 neighbours
-      z = fq_mul_ps(acc.zz, acc.zzz);
+      z = FqPs::mul(acc.zz, acc.zzz);
       if (Fq::is_zero(z)) { dead = true; z = Fq::one(); }
     }
     fe_t total, total_r;
@@ -830,8 +830,8 @@ __global__ void __launch_bounds__(FRSCAN_THREADS) k_srs_precompute(const g1_affi
     __syncthreads();
     if (dead) { P.x = Fq::zero(); P.y = Fq::zero(); }
     else if (!ident) {
-      const fe_t inv = fq_mul_ps(fq_mul_ps(lds_get(inv_total), left), right);   // 1 / (ZZ ZZZ) of this thread's point
-      P.x = fq_mul_ps(acc.x, fq_mul_ps(inv, acc.zzz)); P.y = fq_mul_ps(acc.y, fq_mul_ps(inv, acc.zz));
+      const fe_t inv = FqPs::mul(FqPs::mul(lds_get(inv_total), left), right);   // 1 / (ZZ ZZZ) of this thread's point
+      P.x = FqPs::mul(acc.x, FqPs::mul(inv, acc.zzz)); P.y = FqPs::mul(acc.y, FqPs::mul(inv, acc.zz));
     }
     if (live) { g_store(&table[w * n + i].x, P.x); g_store(&table[w * n + i].y, P.y); }
   }
@@ -846,7 +846,7 @@ __global__ void k_fixed_base_table(g1_affine_t *table) {
   g1_xyzz_t P = g1_xyzz_mul_small(g1_xyzz_from_affine(G), d);
   for (uint32_t j = 0; j < 32; j++) {
     table[j * 256 + d] = g1_xyzz_to_affine(P);
-    for (int k = 0; k < 8; k++) P = g1_xyzz_dbl_ps(P);
+    for (int k = 0; k < 8; k++) P = g1_xyzz_dbl<FqPs>(P);
   }
 }
 // points[i] = scalars[i] * G, affine.  One thread per point: 32 mixed additions + one inversion.
@@ -854,11 +854,11 @@ __global__ void __launch_bounds__(256) k_fixed_base_mul(const g1_affine_t *__res
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   fe_t one_c = Fr::zero(); one_c.l[0] = 1;
-  const fe_t k = fr_mul_ps(g_load(&scalars[i]), one_c);
+  const fe_t k = FrPs::mul(g_load(&scalars[i]), one_c);
   g1_xyzz_t acc = g1_xyzz_identity();
   for (uint32_t j = 0; j < 32; j++) {
     const uint32_t d = (k.l[j >> 2] >> ((j & 3) * 8)) & 0xff;
-    if (d) g1_xyzz_madd_ps(acc, load_affine(&table[j * 256 + d]));
+    if (d) g1_xyzz_madd<FqPs>(acc, load_affine(&table[j * 256 + d]));
   }
   g1_affine_t r = g1_xyzz_to_affine(acc);
   g_store(&out[i].x, r.x); g_store(&out[i].y, r.y);
@@ -870,7 +870,7 @@ __global__ void __launch_bounds__(256) k_srs_scalars(fe_t *__restrict__ g_scal, 
   g_store(&g_scal[i], Fr::pow_u64(tau, i));
   const fe_t wi = Fr::pow_u64(omega, i);
   const fe_t d = Fr::inv_sgcd(Fr::sub(tau, wi));   // division steps: the same instruction stream in every lane
-  g_store(&gl_scal[i], fr_mul_ps(fr_mul_ps(wi, tn1_over_n), d));
+  g_store(&gl_scal[i], FrPs::mul(FrPs::mul(wi, tn1_over_n), d));
 }
 #endif  // __HIPCC__
 

@@ -11,7 +11,8 @@
 // pass also applies the digit-reversal permutation, so it runs out of place (scratch -> destination).
 // HBM traffic = 64 B per element per pass (2-3 passes; algorithmic minimum is one pass = 64*N bytes).
 //
-// Arithmetic inside the tile: one v_mad_u64_u32 per limb product and lazy additions.
+// Arithmetic inside the tile: one v_mad_u64_u32 per limb product and lazy additions; the butterfly and inter-level twiddle products are the chained multiplier
+// Fr29::mul_c (fp29.hpp: 8.61 vs 8.86 ms at 2^26 against the compiler-scheduled Fr29::mul in round 3), the once-per-element pre / post factors Fr29::mul.
 //   * data stay in the ABI domain (x * 2^256): they are only re-sliced (from_sat_plain) on load; twiddles are kept as
 //     w * 2^261 mod r (canonical, SoA tables), so Montgomery products with R' = 2^261 land back in the x * 2^256 domain
 //   * butterfly (DIF): sum = carry(u + v), dif = (u - v + 64 r) * w  -- no branch for w = 1 (table entry 0 is the unit)
@@ -38,9 +39,6 @@ namespace zk {
 #endif
 #ifndef ZK_NTT_LAZY_LAST
 #define ZK_NTT_LAZY_LAST true   // trivial-twiddle differences of a tile's last stage stay un-reduced (see lds_dif29_round)
-#endif
-#ifndef ZK_NTT_CHAIN
-#define ZK_NTT_CHAIN true    // limb products of the NTT butterflies as column blocks of chained v_mad (fp29.hpp mul_c): 8.61 vs 8.86 ms at 2^26 in round 3 (round 2 measured no gain; false restores the C++ multiplier for A/B builds)
 #endif
 // tw_in / has_in (round 6, the coset shift folded into the first pass): element (m, column) of the FIRST strided pass is multiplied by tw_in[m] = (f^(2^log_t))^m on load, and the
 // pass's inter-level table (direct 2 layout) carries f^column next to w_S^(column k) -- together the f^i of distribute_powers, for one multiplication per element and no pass of its own
@@ -142,7 +140,7 @@ template <int R, bool LAST> __device__ __forceinline__ void lds_dif29_round(cons
         // < 2^60.4 per column plus the reduction terms stay below 2^64; (103 r)(r) / 2^261 + r < 1.7 r), the closing pass ends with
         // reduce_small(normalise(.)) or a multiplication itself.  One reduction (~70 instructions) per butterfly of that stage saved.
         if (LAST && (q0 & ((1u << bit) - 1)) == 0) { x[q1] = (ZK_NTT_LAZY_LAST && lazy_last && t == R - 1) ? fr29_sub64(u, v) : Fr29::reduce_small(Fr29::normalise(fr29_sub64(u, v))); n++; }
-        else x[q1] = Fr29::mul_t<ZK_NTT_CHAIN>(fr29_sub64(u, v), tw[t][n++]);
+        else x[q1] = Fr29::mul_c(fr29_sub64(u, v), tw[t][n++]);
         x[q0] = sum;
       }
     }
@@ -193,7 +191,7 @@ template <int RMAX> __global__ void __launch_bounds__(RMAX >= 2 ? 512 : 1024) k_
     const uint32_t c = e & (C - 1), m = e >> log_c;
     fe29_t v = load_input29(src, base + ((uint64_t)m << L.log_t) + c, src_len, pre3);
     // canonical input (< r, exact limbs) times a canonical table entry: tight (< 1.4 r), what a pass may start from (header); uniform branch (kernel argument)
-    if (L.has_in) v = Fr29::mul_t<ZK_NTT_CHAIN>(v, soa29_load(L.tw_in, m));
+    if (L.has_in) v = Fr29::mul_c(v, soa29_load(L.tw_in, m));
     soa29_store(S, e, v);
   }
   __syncthreads();
@@ -206,11 +204,11 @@ template <int RMAX> __global__ void __launch_bounds__(RMAX >= 2 ? 512 : 1024) k_
     // the passes are ALU-bound and leave most of the HBM bandwidth idle: a big level reads its twiddles from a 2^log_s-entry table laid out
     // like the data (coalesced) instead of multiplying two half-size table entries -- one multiplication per element less in the first pass
     const fe29_t w = L.direct == 2 ? soa29_load(L.tw_s_lo, ((uint32_t)k << L.log_t) + (cb << log_c) + c)
-                   : L.direct ? soa29_load(L.tw_s_lo, ex) : Fr29::mul_t<ZK_NTT_CHAIN>(soa29_load(L.tw_s_lo, ex & smask), soa29_load(L.tw_s_hi, ex >> L.split));
+                   : L.direct ? soa29_load(L.tw_s_lo, ex) : Fr29::mul_c(soa29_load(L.tw_s_lo, ex & smask), soa29_load(L.tw_s_hi, ex >> L.split));
     // the strided passes only ever write the library's scratch buffer: their outputs stay the multiplication's tight value (< 1.4 r < 2^256, exact
     // limbs) re-sliced to 8 x 32 bits -- no conditional subtraction; the next pass starts from < 1.4 r (five doublings: < 45 r < the 64 r limit) and
     // only the closing pass, whose output the caller sees, makes everything canonical
-    g_store(&dst[base + ((uint64_t)k << L.log_t) + c], Fr29::to_sat_plain(Fr29::mul_t<ZK_NTT_CHAIN>(v, w)));
+    g_store(&dst[base + ((uint64_t)k << L.log_t) + c], Fr29::to_sat_plain(Fr29::mul_c(v, w)));
   }
 }
 
@@ -257,7 +255,7 @@ __global__ void k_pow_table29(uint4 *lo, uint4 *hi, uint32_t *top, fe_t base, ui
   if (i >= count) return;
   const fe_t b = step == 1 ? base : Fr::pow_u64(base, step);
   fe_t m32; { constexpr uint32_t c[8] = {0x8fffff57u, 0x2fd4e156u, 0xa494b01au, 0x75bba827u, 0x819caa80u, 0x5301fa84u, 0x563d4475u, 0xdc83629u}; for (int q = 0; q < 8; q++) m32.l[q] = c[q]; }   // 32 in Montgomery form
-  soa29_store(Soa29{lo, hi, top}, i, Fr29::from_sat_plain(fr_mul_ps(Fr::pow_u64(b, i), m32)));   // (w * 2^256) * 32 = w * 2^261 mod r, canonical
+  soa29_store(Soa29{lo, hi, top}, i, Fr29::from_sat_plain(FrPs::mul(Fr::pow_u64(b, i), m32)));   // (w * 2^256) * 32 = w * 2^261 mod r, canonical
 }
 // table [k][col] (col < 2^log_t) of base^(col k) * 2^261 mod r: the inter-level twiddles of a big level in the order the pass reads them
 // use_col: the entry also carries colbase^col (the column part f^col of a folded coset shift; colbase in Montgomery form)
@@ -267,8 +265,8 @@ __global__ void k_pow_table29_2d(uint4 *lo, uint4 *hi, uint32_t *top, fe_t base,
   const uint64_t k = i >> log_t, col = i & ((1ull << log_t) - 1);
   fe_t m32; { constexpr uint32_t c[8] = {0x8fffff57u, 0x2fd4e156u, 0xa494b01au, 0x75bba827u, 0x819caa80u, 0x5301fa84u, 0x563d4475u, 0xdc83629u}; for (int q = 0; q < 8; q++) m32.l[q] = c[q]; }   // 32 in Montgomery form
   fe_t e = Fr::pow_u64(base, k * col);
-  if (use_col) e = fr_mul_ps(e, Fr::pow_u64(colbase, col));
-  soa29_store(Soa29{lo, hi, top}, i, Fr29::from_sat_plain(fr_mul_ps(e, m32)));
+  if (use_col) e = FrPs::mul(e, Fr::pow_u64(colbase, col));
+  soa29_store(Soa29{lo, hi, top}, i, Fr29::from_sat_plain(FrPs::mul(e, m32)));
 }
 // dst[i] = src[i] * d (d: Montgomery form of the ABI): a twiddle table with a constant folded in -- the inverse transform's divisor rides on
 // the inter-level twiddles of its last strided pass instead of costing the closing pass one more multiplication per element

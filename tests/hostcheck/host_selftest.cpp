@@ -1,7 +1,8 @@
 // host_selftest.cpp -- TEST INFRASTRUCTURE: compiles the product's __host__ __device__ limb code
-// (scroll-prover_amd/csrc/fp.hpp, g1.hpp) for the CPU with plain g++ so that the 8x32-bit Montgomery
-// and XYZZ formulas can be checked against the oracle in the GPU-less container.  Never shipped,
-// never linked into libmi355zk.so.
+// (scroll-prover_amd/csrc/fp.hpp, fp_asm.hpp, g1.hpp, fp29.hpp, g1_29.hpp, glv.hpp) for the CPU with plain g++ so that
+// the Montgomery and XYZZ formulas can be checked against the oracle in the GPU-less container.  The G1 formulas
+// are exported once per multiplier policy: plain names run F = Fq (CIOS), the `_ps` names F = FqPs (product
+// scanning, what the kernels name).  Never shipped, never linked into libmi355zk.so.
 #include "../../scroll-prover_amd/csrc/g1.hpp"
 #include "../../scroll-prover_amd/csrc/fp_asm.hpp"
 #include "../../scroll-prover_amd/csrc/fp29.hpp"
@@ -21,7 +22,6 @@ template <class F, class P> static void binop(int op, fe_t *o, const fe_t *a, co
     case 6: *o = F::to_canonical(*a); break;
     case 7: *o = mont_mul_ps<P>(*a, *b); break;
     case 8: *o = mont_sqr_ps<P>(*a); break;
-    case 9: *o = F::inv_bgcd(*a); break;
     case 10: *o = F::inv_sgcd(*a); break;
     case 11: *o = F::redc(*a); break;
   }
@@ -30,23 +30,28 @@ extern "C" void hs_f_op(int which, int op, void *o, const void *a, const void *b
   if (which) binop<Fr, FrP>(op, (fe_t *)o, (const fe_t *)a, (const fe_t *)b); else binop<Fq, FqP>(op, (fe_t *)o, (const fe_t *)a, (const fe_t *)b);
 }
 // sum_i k_i * P_i with k_i canonical 256-bit, via XYZZ double-and-add (exercises madd / add / dbl and their special cases)
-extern "C" void hs_msm_naive(void *out_jac, const void *scalars_canonical, const void *bases, uint64_t n) {
+template <class F> static void msm_naive(void *out_jac, const void *scalars_canonical, const void *bases, uint64_t n) {
   const fe_t *k = (const fe_t *)scalars_canonical; const g1_affine_t *b = (const g1_affine_t *)bases;
   g1_xyzz_t total = g1_xyzz_identity();
   for (uint64_t i = 0; i < n; i++) {
     g1_xyzz_t acc = g1_xyzz_identity();
-    for (int bit = 255; bit >= 0; bit--) { acc = g1_xyzz_dbl(acc); if ((k[i].l[bit >> 5] >> (bit & 31)) & 1) g1_xyzz_madd(acc, b[i]); }
-    g1_xyzz_add(total, acc);
+    for (int bit = 255; bit >= 0; bit--) { acc = g1_xyzz_dbl<F>(acc); if ((k[i].l[bit >> 5] >> (bit & 31)) & 1) g1_xyzz_madd<F>(acc, b[i]); }
+    g1_xyzz_add<F>(total, acc);
   }
   *(g1_jac_t *)out_jac = g1_xyzz_to_jac_normalised(total);
 }
-extern "C" void hs_xyzz_madd(void *acc_xyzz, const void *affine) { g1_xyzz_madd(*(g1_xyzz_t *)acc_xyzz, *(const g1_affine_t *)affine); }
-extern "C" void hs_xyzz_add(void *acc_xyzz, const void *q) { g1_xyzz_add(*(g1_xyzz_t *)acc_xyzz, *(const g1_xyzz_t *)q); }
+extern "C" void hs_msm_naive(void *out_jac, const void *k, const void *bases, uint64_t n) { msm_naive<Fq>(out_jac, k, bases, n); }
+extern "C" void hs_msm_naive_ps(void *out_jac, const void *k, const void *bases, uint64_t n) { msm_naive<FqPs>(out_jac, k, bases, n); }
+extern "C" void hs_xyzz_madd(void *acc_xyzz, const void *affine) { g1_xyzz_madd<Fq>(*(g1_xyzz_t *)acc_xyzz, *(const g1_affine_t *)affine); }
+extern "C" void hs_xyzz_madd_ps(void *acc_xyzz, const void *affine) { g1_xyzz_madd<FqPs>(*(g1_xyzz_t *)acc_xyzz, *(const g1_affine_t *)affine); }
+extern "C" void hs_xyzz_add(void *acc_xyzz, const void *q) { g1_xyzz_add<Fq>(*(g1_xyzz_t *)acc_xyzz, *(const g1_xyzz_t *)q); }
+extern "C" void hs_xyzz_add_ps(void *acc_xyzz, const void *q) { g1_xyzz_add<FqPs>(*(g1_xyzz_t *)acc_xyzz, *(const g1_xyzz_t *)q); }
+extern "C" void hs_xyzz_dbl(void *out, const void *p) { *(g1_xyzz_t *)out = g1_xyzz_dbl<Fq>(*(const g1_xyzz_t *)p); }
+extern "C" void hs_xyzz_dbl_ps(void *out, const void *p) { *(g1_xyzz_t *)out = g1_xyzz_dbl<FqPs>(*(const g1_xyzz_t *)p); }
+extern "C" void hs_xyzz_mul_small(void *out, const void *p, uint32_t k) { *(g1_xyzz_t *)out = g1_xyzz_mul_small<Fq>(*(const g1_xyzz_t *)p, k); }
+extern "C" void hs_xyzz_mul_small_ps(void *out, const void *p, uint32_t k) { *(g1_xyzz_t *)out = g1_xyzz_mul_small<FqPs>(*(const g1_xyzz_t *)p, k); }
 extern "C" void hs_xyzz_to_jac(void *out_jac, const void *p) { *(g1_jac_t *)out_jac = g1_xyzz_to_jac_normalised(*(const g1_xyzz_t *)p); }
 extern "C" void hs_jac_to_xyzz(void *out, const void *p) { *(g1_xyzz_t *)out = g1_jac_to_xyzz(*(const g1_jac_t *)p); }
-extern "C" void hs_xyzz_mul_small(void *out, const void *p, uint32_t k) { *(g1_xyzz_t *)out = g1_xyzz_mul_small(*(const g1_xyzz_t *)p, k); }
-extern "C" void hs_xyzz_madd_ps(void *acc_xyzz, const void *affine) { g1_xyzz_madd_ps(*(g1_xyzz_t *)acc_xyzz, *(const g1_affine_t *)affine); }
-extern "C" void hs_xyzz_add_ps(void *acc_xyzz, const void *q) { g1_xyzz_add_ps(*(g1_xyzz_t *)acc_xyzz, *(const g1_xyzz_t *)q); }
 
 // ---- 29-bit unsaturated arithmetic (fp29.hpp): every op takes/returns saturated ABI elements so the test can use the oracle
 template <class F29> static void op29(int op, fe_t *o, const fe_t *a, const fe_t *b) {
@@ -73,12 +78,16 @@ extern "C" int hs_f29_is_zero(int which, const void *a, const void *b) {   // is
   fe29_t d = Fq29::sub4(Fq29::from_sat(*x), Fq29::mul(Fq29::from_sat(*y), Fq29::one())); return Fq29::is_zero_tight(Fq29::mul(d, Fq29::one()));
 }
 
+// a run of mixed additions as k_msm_accumulate does it: x is held negated while the run lasts and made plain where the kernel would flush
+static g1_xyzz29_t bucket_sum29(const g1_affine_t *p, const uint8_t *signs, uint64_t from, uint64_t to) {
+  g1_xyzz29_t acc = g1_xyzz29_identity();
+  for (uint64_t i = from; i < to; i++) g1_xyzz29_madd(acc, p[i], signs[i] & 1);
+  g1_xyzz29_negx_to_plain(acc);
+  return acc;
+}
 // bucket-style accumulation with the 29-bit accumulator: out = sum_i (+-) pts[i] (sign bit = bit 0 of signs[i]), flushed to the saturated XYZZ record
 extern "C" void hs_bucket_sum29(void *out_xyzz, const void *pts, const uint8_t *signs, uint64_t n) {
-  const g1_affine_t *p = (const g1_affine_t *)pts;
-  g1_xyzz29_t acc = g1_xyzz29_identity();
-  for (uint64_t i = 0; i < n; i++) g1_xyzz29_madd(acc, p[i], signs[i] & 1);
-  *(g1_xyzz_t *)out_xyzz = g1_xyzz29_to_sat(acc);
+  *(g1_xyzz_t *)out_xyzz = g1_xyzz29_to_sat(bucket_sum29((const g1_affine_t *)pts, signs, 0, n));
 }
 
 // reduce_small on k*p + delta inputs given as plain 9-limb integers (limbs < 2^29): returns 1 when the result is tight, < 2p and congruent
@@ -94,16 +103,13 @@ extern "C" void hs_xyzz29_grouped_sum(void *out_xyzz, const void *affine, const 
   const g1_affine_t *p = (const g1_affine_t *)affine;
   g1_xyzz29_t total = g1_xyzz29_identity();
   for (uint64_t g0 = 0; g0 < n; g0 += group) {
-    g1_xyzz29_t acc = g1_xyzz29_identity();
-    for (uint64_t i = g0; i < n && i < g0 + group; i++) g1_xyzz29_madd(acc, p[i], signs[i] & 1);
-    g1_xyzz29_add(total, acc);
+    g1_xyzz29_add(total, bucket_sum29(p, signs, g0, g0 + group < n ? g0 + group : n));
   }
   *(g1_xyzz_t *)out_xyzz = g1_xyzz29_to_sat(total);
 }
 extern "C" void hs_xyzz29_ladder(void *out_xyzz, const void *affine, const uint8_t *signs, uint64_t n, uint32_t k) {
   const g1_affine_t *p = (const g1_affine_t *)affine;
-  g1_xyzz29_t base = g1_xyzz29_identity();
-  for (uint64_t i = 0; i < n; i++) g1_xyzz29_madd(base, p[i], signs[i] & 1);   // a loose accumulator as the ladder's base point
+  const g1_xyzz29_t base = bucket_sum29(p, signs, 0, n);   // a loose accumulator as the ladder's base point
   g1_xyzz29_t acc = g1_xyzz29_identity();
   for (int bit = 31; bit >= 0; bit--) { acc = g1_xyzz29_dbl(acc); if ((k >> bit) & 1) g1_xyzz29_add(acc, base); }
   *(g1_xyzz_t *)out_xyzz = g1_xyzz29_to_sat(acc);
@@ -118,7 +124,8 @@ extern "C" void hs_glv_decompose(const void *k_canonical, uint32_t *k1, int *neg
 }
 extern "C" void hs_g1_mul_glv(void *out_xyzz, const void *affine, const void *k_canonical) {
   const g1_affine_t *q = (const g1_affine_t *)affine;
-  g1_xyzz29_t base = g1_xyzz29_identity();
-  g1_xyzz29_madd(base, *q, false);                              // tight coordinates, zz = zzz = one (what g1_xyzz29_from_sat hands over)
+  const uint8_t plus = 0;
+  g1_xyzz29_t base = bucket_sum29(q, &plus, 0, 1);              // y tight, zz = zzz = one; the flush leaves x = 12 p + x: tighten it again, and base
+  base.x = Fq29::reduce_small(Fq29::normalise(base.x));         // is what g1_xyzz29_from_sat hands over (the identity stays all zero)
   *(g1_xyzz_t *)out_xyzz = g1_xyzz29_to_sat(g1_xyzz29_mul_glv(base, *(const fe_t *)k_canonical));
 }

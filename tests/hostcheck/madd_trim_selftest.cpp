@@ -1,11 +1,11 @@
-// madd_trim_selftest.cpp -- TEST INFRASTRUCTURE: the mixed addition k_msm_accumulate runs (g1_29.hpp, g1_xyzz29_madd<true, true, NEGX = true>: x held
+// madd_trim_selftest.cpp -- TEST INFRASTRUCTURE: the mixed addition k_msm_accumulate runs (g1_29.hpp, g1_xyzz29_madd: x held
 // negated between additions, flushed through g1_xyzz29_negx_to_plain) compiled for the CPU with plain g++.  Never shipped.
 #include "../../scroll-prover_amd/csrc/g1.hpp"
 #include "../../scroll-prover_amd/csrc/fp29.hpp"
 #include "../../scroll-prover_amd/csrc/g1_29.hpp"
 using namespace zk;
 
-// the invariants g1_29.hpp documents for an accumulator of the NEGX form between additions; returns a bit mask of what is violated
+// the invariants g1_29.hpp documents for an accumulator of the mixed addition (x negated) between additions; returns a bit mask of what is violated
 static uint32_t check_acc(const g1_xyzz29_t &a) {
   uint32_t bad = 0;
   if (g1_xyzz29_is_identity(a)) return 0;
@@ -31,7 +31,7 @@ extern "C" uint32_t mt_bucket_sums(void *out_affine, const void *pts, const uint
   const g1_affine_t *p = (const g1_affine_t *)pts; g1_affine_t *o = (g1_affine_t *)out_affine; uint32_t bad = 0;
   for (uint64_t s = 0; s < nseq; s++) {
     g1_xyzz29_t acc = g1_xyzz29_identity();
-    for (uint64_t i = off[s]; i < off[s + 1]; i++) { g1_xyzz29_madd<true, true, true>(acc, p[i], signs[i] & 1); bad |= check_acc(acc); }
+    for (uint64_t i = off[s]; i < off[s + 1]; i++) { g1_xyzz29_madd(acc, p[i], signs[i] & 1); bad |= check_acc(acc); }
     o[s] = finish(acc);
   }
   return bad;
@@ -39,14 +39,14 @@ extern "C" uint32_t mt_bucket_sums(void *out_affine, const void *pts, const uint
 // one addition on a raw accumulator (36 words: x, y, zz, zzz as 9 limbs each), so that a test can place lazy coordinates itself
 extern "C" uint32_t mt_madd_raw(uint32_t *acc36, const void *pt, int negate) {
   g1_xyzz29_t &acc = *(g1_xyzz29_t *)acc36;
-  g1_xyzz29_madd<true, true, true>(acc, *(const g1_affine_t *)pt, negate != 0);
+  g1_xyzz29_madd(acc, *(const g1_affine_t *)pt, negate != 0);
   return check_acc(acc);
 }
 // the same with the addend given as 29-bit limbs (x2, y2 as madd_core takes them): any representative of y2 modulo p with limbs < 2^30
 extern "C" uint32_t mt_madd_core_raw(uint32_t *acc36, const uint32_t *x2, const uint32_t *y2, int normalise_y) {
   g1_xyzz29_t &acc = *(g1_xyzz29_t *)acc36; fe29_t x, y;
   for (int i = 0; i < 9; i++) { x.l[i] = x2[i]; y.l[i] = y2[i]; }
-  g1_xyzz29_madd_core<true, true, true>(acc, x, y, normalise_y != 0);
+  g1_xyzz29_madd_core(acc, x, y, normalise_y != 0);
   return check_acc(acc);
 }
 extern "C" void mt_from_sat(uint32_t *out9, const void *fe) { const fe29_t r = Fq29::from_sat(*(const fe_t *)fe); for (int i = 0; i < 9; i++) out9[i] = r.l[i]; }

@@ -1,7 +1,8 @@
 """
 Runs the product's __host__ __device__ limb code (fp.hpp 8x32-bit Montgomery, g1.hpp XYZZ formulas) on the CPU
-via tests/hostcheck/host_selftest.cpp and checks it bit-exactly against the oracle.  This is a check OF the
-device arithmetic, compiled for x86 -- it is not a product path.  CPU only.
+via tests/hostcheck/host_selftest.cpp and checks it bit-exactly against the oracle.  The XYZZ formulas run under both
+multiplier policies: Fq (CIOS, fp.hpp) and FqPs (product scanning, fp_asm.hpp -- the one the kernels name).  This is a
+check OF the device arithmetic, compiled for x86 -- it is not a product path.  CPU only.
 """
 import ctypes as C
 import os
@@ -56,8 +57,6 @@ def test_field_ops_bit_exact(hs):
             assert pyref.from_limbs(op(hs, w, 11, np.array(pyref.to_limbs(vals[i]), dtype=np.uint64))) == vals[i] * pow(1 << 256, -1, m) % m
         for i in range(0, 40):
             assert (op(hs, w, 3, mont[i]) == cref.f_inv(w, mont[i])).all()
-        for i in range(len(vals)):                                        # binary-Euclid inverse used by the one-lane normalisations
-            assert (op(hs, w, 9, mont[i]) == cref.f_inv(w, mont[i])).all(), vals[i]
         # division-step ("safegcd") inverse: constant instruction stream, every edge value plus a long random run; 0 -> 0
         more = [rng.randrange(m) for _ in range(3000)] + [(1 << k) % m for k in range(0, 256, 5)] + [m - (1 << k) for k in range(0, 250, 7)]
         mont2 = cref.f_from_canonical_vec(w, np.array([pyref.to_limbs(v) for v in more], dtype=np.uint64))
@@ -73,7 +72,12 @@ def _pt(Pt):
     return np.array(x + y, dtype=np.uint64)
 
 
-def test_xyzz_formulas_against_oracle(hs):
+# the G1 XYZZ formulas are exported once per multiplier policy: plain names F = Fq, `_ps` names F = FqPs
+POLICIES = pytest.mark.parametrize("ps", ["", "_ps"], ids=["Fq", "FqPs"])
+
+
+@POLICIES
+def test_xyzz_formulas_against_oracle(hs, ps):
     rng = random.Random(12)
     n = 24
     pts = [pyref.g1_mul(pyref.G1_GEN, rng.randrange(1, R)) for _ in range(n)]
@@ -83,36 +87,40 @@ def test_xyzz_formulas_against_oracle(hs):
     sc[0] = 0; sc[1] = 1; sc[2] = R - 1; sc[3] = 2
     canon = np.array([pyref.to_limbs(s) for s in sc], dtype=np.uint64)
     out = np.zeros(12, dtype=np.uint64)
-    hs.hs_msm_naive(p_(out), p_(canon), p_(bases), C.c_uint64(n))
+    getattr(hs, "hs_msm_naive" + ps)(p_(out), p_(canon), p_(bases), C.c_uint64(n))
     want = cref.g1_to_affine(cref.msm_naive(cref.f_from_canonical_vec(cref.FR, canon), bases))
     assert (out[:8] == want).all() and (out[8:] == ONE_Q).all()
 
 
-def test_xyzz_special_cases(hs):
+@POLICIES
+def test_xyzz_special_cases(hs, ps):
+    madd, add, dbl, mul_small = (getattr(hs, "hs_xyzz_" + f + ps) for f in ("madd", "add", "dbl", "mul_small"))
     G = pyref.G1_GEN
     A = pyref.g1_mul(G, 12345)
 
     def xyzz_of(Pt):
-        acc = np.zeros(16, dtype=np.uint64); hs.hs_xyzz_madd(p_(acc), p_(_pt(Pt))); return acc
+        acc = np.zeros(16, dtype=np.uint64); madd(p_(acc), p_(_pt(Pt))); return acc
 
     def aff(acc):
         out = np.zeros(12, dtype=np.uint64); hs.hs_xyzz_to_jac(p_(out), p_(acc))
         return pyref.g1_jacobian_from_limbs(out[:4], out[4:8], out[8:])
 
     a = xyzz_of(A); assert aff(a) == A
-    hs.hs_xyzz_madd(p_(a), p_(_pt(A))); assert aff(a) == pyref.g1_mul(A, 2)           # madd doubling branch
-    hs.hs_xyzz_madd(p_(a), p_(_pt(pyref.g1_neg(pyref.g1_mul(A, 2))))); assert aff(a) is None  # madd inverse branch
-    hs.hs_xyzz_madd(p_(a), p_(np.zeros(8, dtype=np.uint64))); assert aff(a) is None    # identity + identity
+    madd(p_(a), p_(_pt(A))); assert aff(a) == pyref.g1_mul(A, 2)           # madd doubling branch
+    madd(p_(a), p_(_pt(pyref.g1_neg(pyref.g1_mul(A, 2))))); assert aff(a) is None  # madd inverse branch
+    madd(p_(a), p_(np.zeros(8, dtype=np.uint64))); assert aff(a) is None    # identity + identity
     b = xyzz_of(A); c = xyzz_of(A)
-    hs.hs_xyzz_madd(p_(b), p_(_pt(G)))   # b = A+G with a non-trivial ZZ
-    hs.hs_xyzz_madd(p_(c), p_(_pt(G)))
-    hs.hs_xyzz_add(p_(b), p_(c)); assert aff(b) == pyref.g1_mul(pyref.g1_add(A, G), 2)   # add doubling branch
+    madd(p_(b), p_(_pt(G)))   # b = A+G with a non-trivial ZZ
+    madd(p_(c), p_(_pt(G)))
+    add(p_(b), p_(c)); assert aff(b) == pyref.g1_mul(pyref.g1_add(A, G), 2)   # add doubling branch
     d = xyzz_of(pyref.g1_neg(pyref.g1_mul(pyref.g1_add(A, G), 2)))
-    hs.hs_xyzz_add(p_(b), p_(d)); assert aff(b) is None                                # add inverse branch
-    hs.hs_xyzz_add(p_(b), p_(c)); assert aff(b) == pyref.g1_add(A, G)                   # identity + q
+    add(p_(b), p_(d)); assert aff(b) is None                                # add inverse branch
+    add(p_(b), p_(c)); assert aff(b) == pyref.g1_add(A, G)                   # identity + q
     out = np.zeros(16, dtype=np.uint64)
     for k in (0, 1, 2, 3, 1000, 65535, 2**31 + 5):
-        hs.hs_xyzz_mul_small(p_(out), p_(c), C.c_uint32(k)); assert aff(out) == pyref.g1_mul(pyref.g1_add(A, G), k)
+        mul_small(p_(out), p_(c), C.c_uint32(k)); assert aff(out) == pyref.g1_mul(pyref.g1_add(A, G), k)
+    dbl(p_(out), p_(c)); assert aff(out) == pyref.g1_mul(pyref.g1_add(A, G), 2)          # doubling on its own, non-trivial ZZ
+    dbl(p_(out), p_(np.zeros(16, dtype=np.uint64))); assert aff(out) is None            # the identity doubles to the identity
     # Jacobian (non-normalised) -> XYZZ
     j = cref.g1_mul(_pt(G), cref.fr_mont(777)); x = np.zeros(16, dtype=np.uint64)
     hs.hs_jac_to_xyzz(p_(x), p_(j)); assert aff(x) == pyref.g1_mul(G, 777)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """build_variant.py NAME -DFLAG ... -- builds scroll-prover_amd/libmi355zk_NAME.so with extra compile-time switches for A/B runs
-(MI355ZK_LIB=<path> selects it in the Python binding).  E.g.:  python tools/build_variant.py chain -DZK_NTT_CHAIN=true
+(MI355ZK_LIB=<path> selects it in the Python binding).  E.g.:  python tools/build_variant.py eager -DZK_NTT_LAZY_LAST=false
 Objects go to scroll-prover_amd/build_NAME/ (per-unit, content-hashed like the shipped build: scroll-prover_amd/build.py)."""
 import importlib.util, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
