@@ -282,6 +282,19 @@ int mi355_fr_prefix_sum_dev(void *dst_dev, const void *src_dev, uint64_t n, void
  * returns it).  Runs on the library stream of the device that owns m_dev and returns when m is written (the result decides the error).  */
 int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *table_dev, uint64_t table_rows, const void *const *inputs_dev,
                                        uint32_t n_inputs, uint64_t input_rows, uint32_t flags, uint64_t *missing_out);
+/* sigma columns of the permutation argument from the copy mapping [EXT-recalled halo2_proofs src/plonk/permutation/keygen.rs, build_pk / build_vk:
+ * permutations[i][j] = delta^i' omega^j' for mapping[i][j] = (i', j'), which halo2 fills on the CPU from a num_cols x n table].  sigma_dev: host array of
+ * n_cols device pointers, each n = 2^log_n words out (Lagrange basis); delta, omega: 32-byte words on the host.  A cell is the integer column * n + row
+ * (column = position in the permutation).  Every cell gets sigma[j][r] = delta^j omega^r (the identity permutation); every t < count then overrides
+ * sigma[cells_host[t]] = delta^j' omega^r' for (j', r') = images_host[t].  count == 0 gives the identity, count == n_cols * n is the dense mapping.  The
+ * lists are checked on the host before anything is uploaded or launched: MI355_EBADARG, with the first offending index t in mi355_last_error(), for a cell
+ * or image >= n_cols * n, a cell listed twice, or images that are not exactly the listed cells (on MI355_EBADARG the columns are untouched); also for
+ * n_cols == 0, log_n > 28 and columns on different devices.  flags bit 0: the caller vouches for its mapping (halo2's Assembly is a permutation by
+ * construction) and only the range check runs; cells listed twice then end on either value.  Only the listed cells cross the link (16 B each).
+ * Workspace: one pooled mi355_buf block (pointers, n_cols + 2^ceil(log_n / 2) + 2^floor(log_n / 2) table words, at most 2^22 staged overrides;
+ * mi355_mem_info counts it, mi355_buf_trim returns it).  Runs on the library stream of the device that owns the columns and returns when they are written.  */
+int mi355_fr_permutation_sigma_dev(void *const *sigma_dev, uint32_t n_cols, uint32_t log_n, const void *delta, const void *omega,
+                                   const uint64_t *cells_host, const uint64_t *images_host, uint64_t count, uint32_t flags);
 
 /* ---- halo2_proofs::arithmetic::eval_polynomial(poly, point) = sum_i poly[i] * point^i  (the evaluations written to the
  *      transcript in step 9 of create_proof); out_fr_host receives 32 B.  First widening into SURVEY 8f-3.   */

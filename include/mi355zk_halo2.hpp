@@ -379,6 +379,36 @@ class ParamsKZG {
   uint64_t g_ = 0, gl_ = 0;
 };
 
+// ------------------------------------------------------------------------------------------------ plonk/permutation/keygen.rs
+// The copy-constraint bookkeeping of permutation::keygen::Assembly [EXT-recalled halo2_proofs src/plonk/permutation/keygen.rs, `Assembly::copy`]: every cell starts as
+// a cycle of its own; copy() joins the cycles of two cells by relabelling the smaller into the larger and swapping the two cells' `mapping` entries, and is a no-op
+// inside one cycle.  The cycle ORDER this produces is what sigma -- and so the verifying key -- depends on, which is why the device builds sigma from `mapping`
+// (mi355_fr_permutation_sigma_dev) and never from an unordered list of equalities.  A cell is the integer column * n + row (column = position in the permutation):
+// mapping[cell] = its image, aux[cell] = the cell that names its cycle, sizes[cell] = the length of the cycle a naming cell names.
+class PermutationAssembly {
+ public:
+  uint32_t n_cols; uint64_t n;
+  std::vector<uint64_t> mapping, aux, sizes;
+  PermutationAssembly(uint32_t n_cols_, uint64_t n_) : n_cols(n_cols_), n(n_), mapping((size_t)n_cols_ * n_), aux((size_t)n_cols_ * n_), sizes((size_t)n_cols_ * n_, 1) {
+    for (uint64_t c = 0; c < mapping.size(); c++) mapping[c] = aux[c] = c;
+  }
+  void copy(uint32_t col_a, uint64_t row_a, uint32_t col_b, uint64_t row_b) {
+    if (col_a >= n_cols || col_b >= n_cols || row_a >= n || row_b >= n) throw std::invalid_argument("PermutationAssembly::copy: cell outside the permutation");
+    const uint64_t a = col_a * n + row_a, b = col_b * n + row_b;
+    uint64_t keep = aux[a], fold = aux[b];
+    if (keep == fold) return;
+    if (sizes[keep] < sizes[fold]) std::swap(keep, fold);
+    sizes[keep] += sizes[fold];
+    for (uint64_t c = fold;;) { aux[c] = keep; c = mapping[c]; if (c == fold) break; }
+    std::swap(mapping[a], mapping[b]);
+  }
+  // exactly the cells with mapping != identity, in cell order, and their images: the two lists mi355_fr_permutation_sigma_dev takes
+  void overrides(std::vector<uint64_t> &cells, std::vector<uint64_t> &images) const {
+    cells.clear(); images.clear();
+    for (uint64_t c = 0; c < mapping.size(); c++) if (mapping[c] != c) { cells.push_back(c); images.push_back(mapping[c]); }
+  }
+};
+
 }  // namespace halo2
 }  // namespace mi355zk
 

@@ -236,6 +236,7 @@ struct ProvingKey {
   uint32_t identity_common = 0;
   std::vector<uint8_t> vk;                                                                                  // u32 BE k | u32 BE fixed columns | compressed commitments
   uint64_t bytes = 0;
+  double sigma_ms = 0, sigma_host_prep_ms = 0;   // keygen's sigma stage, wall time: default route = sigma_column + upload of every sigma column; device_sigma = the one call (host_prep: PermutationAssembly + overrides before it)
   const DevicePoly &coeff(const Atom &a) const { return a.kind == A_COMMON ? common_coeff.at(a.idx) : pre_coeff.at(a.idx); }
   const DevicePoly *coset(const Atom &a, uint32_t q) const { if (!resident_cosets) return nullptr; return a.kind == A_COMMON ? &common_cosets.at(a.idx)[q] : &pre_cosets.at(a.idx)[q]; }
 };
@@ -336,7 +337,9 @@ inline ResidencyPlan plan_residency(const std::vector<const Protocol *> &protos,
   return R;
 }
 
-inline std::unique_ptr<ProvingKey> keygen(const Protocol &P, const Circuit &C, uint64_t h_g_lagrange, bool resident_cosets, int devices) {
+// device_sigma: every sigma column is produced on the device by ONE mi355_fr_permutation_sigma_dev call from the copy mapping (Circuit::pairs fed through
+// halo2::PermutationAssembly): no sigma column is computed or uploaded by the host.  The key (vk bytes included) is the default route's, bit for bit.
+inline std::unique_ptr<ProvingKey> keygen(const Protocol &P, const Circuit &C, uint64_t h_g_lagrange, bool resident_cosets, int devices, bool device_sigma = false) {
   auto pk = std::make_unique<ProvingKey>(); pk->P = &P; pk->resident_cosets = resident_cosets; pk->devices = std::max(1, devices);
   pk->dom = std::make_unique<EvaluationDomain>(P.Q + 1, P.k);
   const EvaluationDomain &dom = *pk->dom;
@@ -360,11 +363,29 @@ inline std::unique_ptr<ProvingKey> keygen(const Protocol &P, const Circuit &C, u
   pk->vk.resize(8 + 32 * (size_t)P.num_pre);
   { const uint32_t nf = P.num_pre - P.num_sigma(); for (int i = 0; i < 4; i++) { pk->vk[i] = (uint8_t)(P.k >> (24 - 8 * i)); pk->vk[4 + i] = (uint8_t)(nf >> (24 - 8 * i)); } }
   std::vector<Fr> sig;
+  std::vector<DevicePoly> sig_dev;   // device_sigma: the sigma column of every permutation position
+  using SigmaClock = std::chrono::steady_clock;
+  auto ms_since = [](SigmaClock::time_point t0) { return std::chrono::duration<double, std::milli>(SigmaClock::now() - t0).count(); };
+  if (device_sigma) {
+    const uint32_t NP = (uint32_t)C.pcols.size();
+    const Fr delta = NP > 1 ? C.pcols[1].delta_pow : fr_one();
+    { Fr dp = fr_one(); for (uint32_t j = 0; j < NP; j++) { if (!(C.pcols[j].delta_pow == dp)) throw std::invalid_argument("keygen: the permutation's constants are not the powers of one delta"); dp = fr_mul(dp, delta); } }
+    const auto t0 = SigmaClock::now();
+    std::vector<uint64_t> cells, images;
+    { halo2::PermutationAssembly as(NP, n); for (const auto &cp : C.pairs) as.copy(cp.ja, cp.ra, cp.jb, cp.rb); as.overrides(cells, images); }
+    pk->sigma_host_prep_ms = ms_since(t0);
+    std::vector<void *> ptrs;
+    for (uint32_t j = 0; j < NP; j++) { sig_dev.emplace_back(n, 0); ptrs.push_back(sig_dev.back().p); }
+    check(mi355_synchronize());
+    const auto t1 = SigmaClock::now();
+    check(mi355_fr_permutation_sigma_dev(ptrs.data(), NP, P.k, delta.data(), P.omega.data(), cells.data(), images.data(), cells.size(), 0));
+    pk->sigma_ms = ms_since(t1);
+  }
   for (uint32_t p = 0; p < P.num_pre; p++) {
-    DevicePoly lag(n, 0);
     int j = -1; for (size_t t = 0; t < C.pcols.size(); t++) if (C.pcols[t].sigma == p) j = (int)t;
-    if (j >= 0) { C.sigma_column((uint32_t)j, sig); check(mi355_buf_upload(lag.p, sig.data(), n * 32)); }
-    else check(mi355_buf_upload(lag.p, C.pre[p].data(), n * 32));
+    DevicePoly lag = j >= 0 && device_sigma ? std::move(sig_dev[(size_t)j]) : DevicePoly(n, 0);
+    if (j >= 0 && !device_sigma) { const auto t0 = SigmaClock::now(); C.sigma_column((uint32_t)j, sig); check(mi355_buf_upload(lag.p, sig.data(), n * 32)); pk->sigma_ms += ms_since(t0); }
+    else if (j < 0) check(mi355_buf_upload(lag.p, C.pre[p].data(), n * 32));
     G1 c; check(mi355_msm_g1_dev(h_g_lagrange, 0, lag.p, n, c.data()));
     halo2::G1Affine a; std::memcpy(a.data(), c.data(), 64); const halo2::G1Bytes b = halo2::g1_to_bytes(a);
     std::memcpy(pk->vk.data() + 8 + 32 * (size_t)p, b.data(), 32);

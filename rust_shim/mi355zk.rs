@@ -96,6 +96,8 @@ extern "C" {
     pub fn mi355_fr_prefix_sum_dev(dst_dev: *mut c_void, src_dev: *const c_void, n: u64, total_out_host: *mut c_void) -> c_int;
     pub fn mi355_fr_lookup_multiplicities_dev(m_dev: *mut c_void, n: u64, table_dev: *const c_void, table_rows: u64, inputs_dev: *const *const c_void,
                                               n_inputs: u32, input_rows: u64, flags: u32, missing_out: *mut u64) -> c_int;
+    pub fn mi355_fr_permutation_sigma_dev(sigma_dev: *const *mut c_void, n_cols: u32, log_n: u32, delta: *const c_void, omega: *const c_void,
+                                          cells_host: *const u64, images_host: *const u64, count: u64, flags: u32) -> c_int;
     pub fn mi355_fr_kate_division_dev(dst_dev: *mut c_void, poly_dev: *const c_void, n: u64, z: *const c_void) -> c_int;
     pub fn mi355_eval_polynomial_batch_dev(polys_dev: *const *const c_void, batch: u32, n: u64, points: *const c_void, out_fr_host: *mut c_void) -> c_int;
     pub fn mi355_eval_polynomial_dev(poly_dev: *const c_void, n: u64, point: *const c_void, out_fr_host: *mut c_void) -> c_int;
@@ -261,6 +263,23 @@ impl DevicePoly {
         let rc = unsafe { mi355_eval_polynomial_dev(self.ptr, self.len as u64, point as *const Fr as *const c_void, out.as_mut_ptr() as *mut c_void) };
         if rc == MI355_OK { Some(unsafe { out.assume_init() }) } else { None }
     }
+}
+/// The sigma columns of `permutation::keygen::Assembly::build_pk` / `build_vk` as resident polynomials, from the non-identity cells of `Assembly::mapping`
+/// (cell = column * n + row; `cells[t]` maps to `images[t]`): only those cells cross the link.  `trusted`: the lists come from an `Assembly`, which is a
+/// permutation by construction, so the library checks the range only.  None -> the caller runs the CPU code (a rejected mapping is logged by the library's error text).
+pub fn permutation_sigma(k: u32, n_cols: usize, delta: &Fr, omega: &Fr, cells: &[u64], images: &[u64], trusted: bool, slot: c_int) -> Option<Vec<DevicePoly>> {
+    if !available() || n_cols == 0 || k > 28 || cells.len() != images.len() { return None; }
+    let n = 1usize << k;
+    let mut cols: Vec<DevicePoly> = Vec::with_capacity(n_cols);
+    for _ in 0..n_cols {
+        let mut p: *mut c_void = std::ptr::null_mut();
+        if unsafe { mi355_buf_alloc((n * 32) as u64, slot, &mut p) } != MI355_OK { return None; }
+        cols.push(DevicePoly { ptr: p, len: n, slot });
+    }
+    let ptrs: Vec<*mut c_void> = cols.iter().map(|c| c.ptr).collect();
+    let rc = unsafe { mi355_fr_permutation_sigma_dev(ptrs.as_ptr(), n_cols as u32, k, delta as *const Fr as *const c_void, omega as *const Fr as *const c_void,
+                                                     cells.as_ptr(), images.as_ptr(), cells.len() as u64, if trusted { 1 } else { 0 }) };
+    if rc == MI355_OK { Some(cols) } else { None }
 }
 impl GpuBasis {
     /// commit / commit_lagrange of a resident polynomial: the scalars never leave HBM (with several devices each shard's slice crosses xGMI).

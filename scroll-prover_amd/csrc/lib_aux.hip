@@ -1,12 +1,13 @@
 // lib_aux.hip -- libmi355zk.so, the translation unit of the kernels either side of MSM / NTT: the DFT over G1 points
 // (g1fft.hpp: g_to_lagrange, ParamsKZG::downsize), the multiplicative scans of the permutation / lookup arguments and kate_division
 // (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), the multiplicities of the mv-lookup argument
-// (lookup.hpp), and the compressed-point codec of G1 (g1codec.hpp).  Host logic only.
+// (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), and the compressed-point codec of G1 (g1codec.hpp).  Host logic only.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #include "g1fft.hpp"
 #include "frscan.hpp"
 #include "g2.hpp"
 #include "lookup.hpp"
+#include "perm.hpp"
 #include "g1codec.hpp"
 #include "lib_common.hpp"
 #include <thread>
@@ -487,6 +488,64 @@ int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *tabl
     if (missing_out) *missing_out = err_host;
     return fail(MI355_EBADARG, "fr_lookup_multiplicities: input " + std::to_string(err_host >> 40) + ", row " + std::to_string(err_host & ((1ull << 40) - 1)) + " is not in the table");
   }
+  return finish_async();
+  });
+}
+
+// ---- the sigma columns of the permutation argument from the copy mapping (perm.hpp).  The mapping is checked on the host first (perm_check): on MI355_EBADARG nothing has
+// been uploaded or launched.  Workspace: ONE pooled mi355_buf block -- the column pointers, the three power tables (n_cols + 2 x 2^(log_n / 2) words) and a staging area for
+// at most PERM_STAGE overrides (16 B each) -- handed back to the pool on return.  Longer lists go through the staging area piece by piece: an upload into it waits for the
+// kernel that reads the previous piece (mi355_buf_upload into a block in use).  Synchronous: the call returns when the columns are written.
+constexpr uint64_t PERM_STAGE = 1ull << 22;
+int mi355_fr_permutation_sigma_dev(void *const *sigma_dev, uint32_t n_cols, uint32_t log_n, const void *delta, const void *omega, const uint64_t *cells_host,
+                                   const uint64_t *images_host, uint64_t count, uint32_t flags) {
+  return guarded([&]() -> int {
+  int slot = 0;
+  for (uint32_t j = 0; sigma_dev && j < n_cols; j++) { int s2; CHK(common_slot({sigma_dev[0], sigma_dev[j]}, &s2, "fr_permutation_sigma")); if (j == 0) slot = s2; }
+  DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (n_cols == 0 || n_cols > 65535u * PERM_COL_TILE) return fail(MI355_EBADARG, "fr_permutation_sigma: n_cols must be 1 .. " + std::to_string(65535u * PERM_COL_TILE));
+  if (log_n > PERM_MAX_LOG_N) return fail(MI355_EBADARG, "fr_permutation_sigma: log_n > 28");
+  if (!sigma_dev || !delta || !omega || (count && (!cells_host || !images_host))) return fail(MI355_EBADARG, "fr_permutation_sigma: null pointer");
+  if (flags & ~PERM_FLAG_TRUSTED) return fail(MI355_EBADARG, "fr_permutation_sigma: unknown flag bits");
+  const uint64_t n = 1ull << log_n, total = (uint64_t)n_cols * n;
+  for (uint32_t j = 0; j < n_cols; j++) {
+    if (!sigma_dev[j]) return fail(MI355_EBADARG, "fr_permutation_sigma: null column " + std::to_string(j));
+    if ((uintptr_t)sigma_dev[j] & 15) return fail(MI355_EBADARG, "fr_permutation_sigma: device pointers must be 16-byte aligned");
+    CHK(buf_check_range(sigma_dev[j], n * sizeof(fe_t), "fr_permutation_sigma"));
+  }
+  { uint64_t bad = 0; std::string why; if (perm_check(cells_host, images_host, count, total, flags, &bad, &why)) return fail(MI355_EBADARG, "fr_permutation_sigma: override " + std::to_string(bad) + ": " + why); }
+  const uint32_t lo_bits = perm_lo_bits(log_n), n_lo = 1u << lo_bits, n_hi = 1u << (log_n - lo_bits);
+  const uint64_t stage = std::min(count, PERM_STAGE);
+  const uint64_t off_dpow = ((uint64_t)n_cols * 8 + 255) & ~255ull, off_lo = off_dpow + (uint64_t)n_cols * sizeof(fe_t), off_hi = off_lo + (uint64_t)n_lo * sizeof(fe_t),
+                 off_cells = off_hi + (uint64_t)n_hi * sizeof(fe_t), off_images = off_cells + stage * 8, bytes = off_images + stage * 8;
+  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
+  int rc = MI355_OK;
+  [&]() {
+    char *base = (char *)ws; hipStream_t s = g.stream;
+    fe_t *const *cols = (fe_t *const *)base; fe_t *dpow = (fe_t *)(base + off_dpow), *tw_lo = (fe_t *)(base + off_lo), *tw_hi = (fe_t *)(base + off_hi);
+    if ((rc = mi355_buf_upload(ws, sigma_dev, (uint64_t)n_cols * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
+    fe_t d, w; memcpy(&d, delta, 32); memcpy(&w, omega, 32);
+    const PermTables T{tw_lo, tw_hi, dpow, lo_bits};
+    {
+      Scope sc("permutation_sigma");
+      if ((rc = launch_pow_table(dpow, d, 1, n_cols)) != MI355_OK || (rc = launch_pow_table(tw_lo, w, 1, n_lo)) != MI355_OK || (rc = launch_pow_table(tw_hi, w, n_lo, n_hi)) != MI355_OK) return;
+      hipLaunchKernelGGL(k_perm_identity, dim3(ceil_div(n, PERM_THREADS), ceil_div(n_cols, PERM_COL_TILE)), dim3(PERM_THREADS), 0, s, cols, n_cols, log_n, T, d);
+    }
+    if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: kernel launch failed"); return; }
+    for (uint64_t lo = 0; lo < count; lo += stage) {
+      const uint64_t len = std::min(stage, count - lo);
+      if ((rc = mi355_buf_upload(base + off_cells, cells_host + lo, len * 8)) != MI355_OK || (rc = mi355_buf_upload(base + off_images, images_host + lo, len * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
+      Scope sc("permutation_sigma");
+      hipLaunchKernelGGL(k_perm_override, dim3((uint32_t)std::min<uint64_t>(ceil_div(len, PERM_THREADS), 65535u * 4)), dim3(PERM_THREADS), 0, s, cols, log_n, T,
+                         (const uint64_t *)(base + off_cells), (const uint64_t *)(base + off_images), len);
+      sc.close();
+      if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: kernel launch failed"); return; }
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: stream synchronize failed"); return; }
+  }();
+  (void)mi355_buf_free(ws);
+  if (rc != MI355_OK) return rc;
   return finish_async();
   });
 }

@@ -316,6 +316,62 @@ def lookup_multiplicities(table, inputs, table_rows: int, input_rows: int, last:
     return m
 
 
+class PermutationAssembly:
+    """the copy-constraint bookkeeping of permutation::keygen::Assembly [EXT-recalled halo2_proofs src/plonk/permutation/keygen.rs]; the twin of
+    halo2::PermutationAssembly in include/mi355zk_halo2.hpp.  A cell is the integer column * n + row.  `mapping[cell]` is the cell's image, `aux[cell]` the
+    cell that names its cycle, `sizes[cell]` the length of the cycle a naming cell names.  copy() joins two cycles the way halo2 does -- the smaller one is
+    relabelled into the larger, then the two cells' mapping entries are swapped -- and does nothing inside one cycle, so the cycle order is halo2's."""
+
+    def __init__(self, n_cols: int, n: int):
+        self.n_cols, self.n = int(n_cols), int(n)
+        self.mapping = np.arange(self.n_cols * self.n, dtype=np.uint64)
+        self.aux = self.mapping.copy()
+        self.sizes = np.ones(self.n_cols * self.n, dtype=np.uint64)
+
+    def copy(self, col_a: int, row_a: int, col_b: int, row_b: int) -> None:
+        assert 0 <= col_a < self.n_cols and 0 <= col_b < self.n_cols and 0 <= row_a < self.n and 0 <= row_b < self.n, "PermutationAssembly.copy: cell outside the permutation"
+        mapping, aux, sizes = self.mapping, self.aux, self.sizes
+        a, b = col_a * self.n + row_a, col_b * self.n + row_b
+        keep, fold = int(aux[a]), int(aux[b])
+        if keep == fold:
+            return
+        if sizes[keep] < sizes[fold]:
+            keep, fold = fold, keep
+        sizes[keep] += sizes[fold]
+        c = fold
+        while True:
+            aux[c] = keep
+            c = int(mapping[c])
+            if c == fold:
+                break
+        mapping[a], mapping[b] = mapping[b], mapping[a]
+
+    def overrides(self):
+        """(cells, images): exactly the cells with mapping != identity, in cell order -- the two lists permutation_sigma takes"""
+        cells = np.nonzero(self.mapping != np.arange(self.mapping.size, dtype=np.uint64))[0].astype(np.uint64)
+        return cells, self.mapping[cells].copy()
+
+
+def permutation_sigma(n_cols: int, log_n: int, delta: np.ndarray, omega: np.ndarray, cells=(), images=(), device=None, trusted: bool = False, out=None):
+    """the sigma columns of the permutation argument (mi355_fr_permutation_sigma_dev) as device tensors: sigma[j][r] = delta^j omega^r, then
+    sigma[cells[t]] = delta^j' omega^r' for (j', r') = images[t] (cell = column * n + row; PermutationAssembly.overrides() gives the lists).  Returns a list of
+    n_cols tensors of [2^log_n, 4] int64 (`out`: write into these instead).  A list that is no permutation of its cells raises Mi355Error (EBADARG) naming the
+    first offending index, before anything reaches the device; trusted=True keeps the range check only."""
+    cells = np.ascontiguousarray(cells, dtype=np.uint64).reshape(-1)
+    images = np.ascontiguousarray(images, dtype=np.uint64).reshape(-1)
+    assert cells.size == images.size, "permutation_sigma: cells and images differ in length"
+    if out is None:
+        import torch
+        out = [torch.empty((1 << log_n, 4), dtype=torch.int64, device=device) for _ in range(n_cols)]
+    assert len(out) == n_cols
+    for t in out:
+        assert t.numel() * t.element_size() == 32 << log_n, "permutation_sigma: a column is not 2^log_n words"
+    arr = (C.c_void_p * max(1, n_cols))(*[t.data_ptr() for t in out])
+    u64p = C.POINTER(C.c_uint64)
+    check(lib().mi355_fr_permutation_sigma_dev(arr, n_cols, log_n, ptr(delta), ptr(omega), cells.ctypes.data_as(u64p), images.ctypes.data_as(u64p), cells.size, 1 if trusted else 0))
+    return out
+
+
 # halo2curves bn256 G2 generator (x.c0, x.c1, y.c0, y.c1) [EXT-recalled src/bn256/curve.rs]; the same four words are the first pairing
 # input of the released verifier [REF release-v0.13.1/evm_verifier.yul:1230-1233] (tests/test_oracle_golden.py)
 G2_GENERATOR = (0x1800DEEF121F1E76426A00665E5C4479674322D4F75EDADD46DEBD5CD992F6ED, 0x198E9393920D483A7260BFB731FB5D25F1AA493335A9E71297E485B7AEF312C2,

@@ -109,3 +109,29 @@ def run_lookup_multiplicities(layer: int, k: int | None = None, out_dir: str | N
             with open(p, "rb") as f:
                 rec[name] = f.read()
     return rec
+
+
+def run_permutation_keygen(layer: int, k: int | None = None, out_dir: str | None = None, args=(), env=None, timeout: int = 1800, protocol_file: str | None = None, **shape) -> dict:
+    """tests/cpp/test_permutation_keygen.cpp: one layer's key and one proof by the default route (Circuit::sigma_column on the host, every sigma column uploaded) and by
+    the device route (keygen(..., device_sigma = true): one mi355_fr_permutation_sigma_dev call).  Returns the program's record with `vk_host`, `vk_device`,
+    `proof_host`, `proof_device` and `instances`; args: "--keygen-only"."""
+    from . import build
+    out_dir = out_dir or tempfile.mkdtemp(prefix=f"mi355_perm_keygen_l{layer}_")
+    os.makedirs(out_dir, exist_ok=True)
+    proto = write_protocol(layer, out_dir, k, protocol_file, **shape)
+    e = dict(os.environ)
+    e.update(env or {})
+    t0 = time.perf_counter()
+    out = subprocess.run([build.build_cpp("test_permutation_keygen"), "--protocol", proto, "--out", out_dir] + list(args), capture_output=True, text=True, timeout=timeout, env=e)
+    line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
+    rec = {"layer": layer, "ok": False, "returncode": out.returncode, "out_dir": out_dir, "protocol_path": proto, "process_wall_s": time.perf_counter() - t0}
+    if out.returncode != 0 or line is None:
+        rec["error"] = (out.stdout + out.stderr)[-1200:]
+        return rec
+    rec.update(json.loads(line))
+    for name in ("vk_host", "vk_device", "proof_host", "proof_device", "instances"):
+        p = os.path.join(out_dir, name + ".bin")
+        if os.path.exists(p):
+            with open(p, "rb") as f:
+                rec[name] = f.read()
+    return rec
