@@ -295,6 +295,22 @@ int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *tabl
  * mi355_mem_info counts it, mi355_buf_trim returns it).  Runs on the library stream of the device that owns the columns and returns when they are written.  */
 int mi355_fr_permutation_sigma_dev(void *const *sigma_dev, uint32_t n_cols, uint32_t log_n, const void *delta, const void *omega,
                                    const uint64_t *cells_host, const uint64_t *images_host, uint64_t count, uint32_t flags);
+/* ---- a witness judged where it lives [EXT-recalled halo2_proofs src/dev.rs, MockProver::verify: gate, lookup and permutation failures]: the two reductions that turn
+ * "a gate evaluated on every row" and "the copy mapping" into a short list of failures (csrc/check.hpp); plonk::check_witness (mi355zk_plonk.hpp) is the driver.
+ * A failing witness is NOT an error: both calls return MI355_OK and report through their outputs.  Both are synchronous (the result is the answer), run on the library
+ * stream of the device that owns the operands, and are deterministic: same counts, same indices on every run.  cap <= 65536; cap == 0 returns the counts only (the index
+ * output may then be NULL).  Workspace: one pooled mi355_buf block (mi355_mem_info counts it, mi355_buf_trim returns it).  MI355_EBADARG, before any launch, with the
+ * offending index in mi355_last_error(): batch == 0, n == 0, n_cols == 0, log_n > 28, cap > 65536, a cell or image >= n_cols << log_n, operands on different devices.
+ *
+ * MockProver's gate check: vecs_dev is a host array of `batch` device pointers, each n words (n need not be a power of two).  counts_out_host[v] = the rows of vector v
+ * whose 32-byte word is not all-zero (all eight 32-bit limbs take part); rows_out_host[v * cap ..] = the smallest `cap` such rows, ascending, unused slots ~0.          */
+int mi355_fr_nonzero_rows_dev(const void *const *vecs_dev, uint32_t batch, uint64_t n, uint32_t cap, uint64_t *counts_out_host, uint64_t *rows_out_host);
+/* MockProver's permutation check: cols_dev is a host array of n_cols device pointers, each 2^log_n words (the columns in permutation position order); a cell is the integer
+ * column * n + row, as mi355_fr_permutation_sigma_dev takes it.  Pair t fails when the words of cells_host[t] and images_host[t] differ.  *n_failed_out = the failing pairs,
+ * failed_t_out_host[0 .. cap) = the smallest `cap` failing t, ascending, unused slots ~0.  The lists need not be a permutation; they are staged in pieces of at most 2^22
+ * pairs (16 B per pair cross the link).                                                                                                                                  */
+int mi355_fr_copy_check_dev(const void *const *cols_dev, uint32_t n_cols, uint32_t log_n, const uint64_t *cells_host, const uint64_t *images_host, uint64_t count,
+                            uint32_t cap, uint64_t *n_failed_out, uint64_t *failed_t_out_host);
 
 /* ---- halo2_proofs::arithmetic::eval_polynomial(poly, point) = sum_i poly[i] * point^i  (the evaluations written to the
  *      transcript in step 9 of create_proof); out_fr_host receives 32 B.  First widening into SURVEY 8f-3.   */

@@ -409,6 +409,23 @@ class PermutationAssembly {
   }
 };
 
+// ------------------------------------------------------------------------------------------------ dev.rs
+// The two reductions of MockProver::verify on resident data [EXT-recalled halo2_proofs src/dev.rs, MockProver::verify].  A failing witness is not an error: the failures
+// come back as counts and indices (the smallest `cap`, ascending; unused slots ~0).  plonk::check_witness (mi355zk_plonk.hpp) drives them for a PlonkProtocol.
+struct NonzeroRows { std::vector<uint64_t> counts, rows; uint32_t cap; const uint64_t *rows_of(size_t v) const { return rows.data() + v * cap; } };
+inline NonzeroRows nonzero_rows(const std::vector<const void *> &vecs_dev, uint64_t n, uint32_t cap = 16) {
+  NonzeroRows r; r.cap = cap; r.counts.assign(vecs_dev.size(), 0); r.rows.assign(vecs_dev.size() * cap, ~uint64_t(0));
+  check(mi355_fr_nonzero_rows_dev(vecs_dev.data(), (uint32_t)vecs_dev.size(), n, cap, r.counts.data(), cap ? r.rows.data() : nullptr));
+  return r;
+}
+struct CopyCheck { uint64_t n_failed = 0; std::vector<uint64_t> failed_t; };
+inline CopyCheck copy_check(const std::vector<const void *> &cols_dev, uint32_t log_n, const std::vector<uint64_t> &cells, const std::vector<uint64_t> &images, uint32_t cap = 16) {
+  if (cells.size() != images.size()) throw std::invalid_argument("copy_check: cells and images differ in length");
+  CopyCheck r; r.failed_t.assign(cap, ~uint64_t(0));
+  check(mi355_fr_copy_check_dev(cols_dev.data(), (uint32_t)cols_dev.size(), log_n, cells.data(), images.data(), cells.size(), cap, &r.n_failed, cap ? r.failed_t.data() : nullptr));
+  return r;
+}
+
 }  // namespace halo2
 }  // namespace mi355zk
 

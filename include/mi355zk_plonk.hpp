@@ -16,6 +16,8 @@
 //                   the quotient part by part, its Q pieces in, x out; the evaluations in the protocol's order; SHPLONK over the rotation sets the protocol's
 //                   `queries` imply (per set: interpolated remainders, division by the set's vanishing polynomial; one combined quotient commitment, the
 //                   linearised polynomial at u, its kate_division) -- two closing commitments, as the fixtures' two trailing G1 words.
+//   check_witness   MockProver::verify on the device: every gate on every row, every copy constraint, every lookup input, reported as (constraint, row) failures
+//                   (csrc/check.hpp); ProofOptions::check_witness runs it ahead of the proof
 //   the proof       bytes in the reference's layout: 32-byte compressed G1 commitments in transcript order, canonical little-endian
 //                   Fr evaluations, two compressed SHPLONK points: 896 B for layer 2 ([1,1,3] witness polynomials, Q = 4, 17 evaluations), 1 312 B for layer 4.
 //
@@ -419,6 +421,142 @@ inline std::unique_ptr<ProvingKey> keygen(const Protocol &P, const Circuit &C, u
   return pk;
 }
 
+// ------------------------------------------------------------------------------------------------ check_witness
+// halo2_proofs::dev::MockProver::verify for a PlonkProtocol, on the device [EXT-recalled halo2_proofs src/dev.rs, MockProver::verify: gate, lookup and permutation
+// failures]; the reference runs it on every trace before proving [REF integration/src/mock.rs:16-24], [REF bin/src/prove_utils.rs:54-55,81-88].  create_proof takes any
+// witness and a wrong cell only shows as a proof the verifier rejects; this names the constraint and the row.
+//   gates     every constraint i of the numerator the recogniser classifies as a gate (Protocol::gates), compiled ON ITS OWN, without powers of y, into a temporary on
+//             the Lagrange domain (rotations in rows, as step 4 runs the plan), and held to zero on ALL n rows -- what divisibility by X^n - 1 needs; a superset of
+//             MockProver's usable rows (selectors are zero on the blinding rows).  Temporaries are judged a batch at a time by one mi355_fr_nonzero_rows_dev call.
+//             Fixed / common polynomials whose Lagrange values the key does not keep (lagrange_needed) come back from their coefficients by a forward transform into
+//             scratch, lazily and only those.  index = the constraint's position in the numerator's list (the protocol file's numbering).
+//   copies    Circuit::pairs through halo2::PermutationAssembly, as keygen(..., device_sigma = true) feeds them; the columns in permutation position order (advice,
+//             instance, fixed: Lagrange values); one mi355_fr_copy_check_dev call.  index = t in the override lists; both cells decoded.
+//   lookups   table and input compressed with a theta drawn from theta_seed (the builder's splitmix stream, nonzero), then mi355_fr_lookup_multiplicities_dev into a
+//             scratch m over the usable rows, as step 3's device_multiplicities route.  Two different tuples compress to one value for at most (columns - 1) of the r
+//             choices of theta: a tuple mismatch escapes with probability at most (columns - 1) / r.  The entry point reports only the SMALLEST missing (input, row),
+//             so a lookup yields at most one failure (count = 1, col_a = the input index the entry point names: 0, the one compressed column).
+// The argument polynomials' own constraints (z, phi) are not checked: they hold by construction once copies and lookups do.  The check uploads the advice and instance
+// columns itself and frees everything it allocated before it returns.
+struct VerifyFailure { enum Kind { Gate, Copy, Lookup } kind; uint32_t index; uint64_t row; uint64_t count; uint32_t col_a, col_b; uint64_t row_b; };
+struct CheckOptions { int threads = 8 /* host threads; one upload thread per four */; uint32_t cap = 16 /* failures reported per gate / for the copies; counts stay full */; uint64_t theta_seed = 1; };
+inline const char *failure_kind_name(VerifyFailure::Kind k) { return k == VerifyFailure::Gate ? "gate" : k == VerifyFailure::Copy ? "copy" : "lookup"; }
+inline std::string describe(const VerifyFailure &f) {
+  if (f.kind == VerifyFailure::Gate) return "gate constraint " + std::to_string(f.index) + " fails at row " + std::to_string(f.row) + " (" + std::to_string(f.count) + " rows in all)";
+  if (f.kind == VerifyFailure::Copy) return "copy constraint " + std::to_string(f.index) + " fails: permutation column " + std::to_string(f.col_a) + " row " + std::to_string(f.row) + " differs from column " +
+                                            std::to_string(f.col_b) + " row " + std::to_string(f.row_b) + " (" + std::to_string(f.count) + " pairs in all)";
+  return "lookup " + std::to_string(f.index) + ": input row " + std::to_string(f.row) + " is not in the table";
+}
+struct WitnessError : std::runtime_error {
+  std::vector<VerifyFailure> failures;
+  explicit WitnessError(std::vector<VerifyFailure> f) : std::runtime_error("witness check: " + describe(f.at(0)) + (f.size() > 1 ? "; " + std::to_string(f.size()) + " failures reported" : std::string())), failures(std::move(f)) {}
+};
+inline std::vector<VerifyFailure> check_witness(const ProvingKey &pk, const Circuit &wit, const CheckOptions &opt) {
+  const Protocol &P = *pk.P; const EvaluationDomain &dom = *pk.dom;
+  const uint64_t n = P.n, u = P.usable; const uint32_t A = P.num_advice(), NL = (uint32_t)P.lookups.size();
+  if (wit.advice.size() != A) throw std::invalid_argument("check_witness: the witness has " + std::to_string(wit.advice.size()) + " advice columns, the protocol " + std::to_string(A));
+  if (wit.instances.size() > n) throw std::invalid_argument("check_witness: more instance values than rows");
+  std::vector<VerifyFailure> out;
+  // ---- the witness crosses the link
+  std::vector<DevicePoly> adv(A); DevicePoly inst(n, 0);
+  check(mi355_buf_zero(inst.p, n * 32));
+  if (!wit.instances.empty()) check(mi355_buf_upload(inst.p, wit.instances.data(), wit.instances.size() * 32));
+  {
+    const size_t UT = (size_t)std::max(1, std::min<int>(std::min(3, opt.threads / 4), (int)A));
+    std::mutex mu; std::string upload_error;
+    auto worker = [&](size_t first) {
+      try { for (size_t i = first; i < A; i += UT) { if (wit.advice[i].size() != n) throw std::invalid_argument("advice column " + std::to_string(i) + " is not n rows"); DevicePoly d(n, 0); check(mi355_buf_upload(d.p, wit.advice[i].data(), n * 32)); adv[i] = std::move(d); } }
+      catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu); upload_error = e.what(); }
+    };
+    std::vector<std::thread> th; for (size_t w = 1; w < UT; w++) th.emplace_back(worker, w);
+    worker(0);
+    for (auto &t : th) t.join();
+    if (!upload_error.empty()) throw Error(MI355_EHIP, "check_witness: witness upload: " + upload_error);
+  }
+  // ---- operands: Lagrange values; what the key holds as coefficients only comes back by a forward transform, once, when first named
+  std::map<Atom, DevicePoly> scratch; std::vector<DevicePoly> tmp;
+  auto tmp_at = [&](uint32_t i) -> DevicePoly & { while (tmp.size() <= i) tmp.emplace_back(n, 0); return tmp[i]; };
+  auto from_coeff = [&](const Atom &a) -> const void * {
+    auto it = scratch.find(a);
+    if (it == scratch.end()) { DevicePoly c = clone(pk.coeff(a), 0); check(mi355_ntt_fr_dev(c.p, dom.k, dom.omega.data())); it = scratch.emplace(a, std::move(c)).first; }
+    return it->second.p;
+  };
+  auto column = [&](uint32_t poly) -> const void * {
+    if (P.is_pre(poly)) return pk.pre_lagrange[poly].p ? pk.pre_lagrange[poly].p : from_coeff(Atom{A_POLY, poly, 0});
+    if (P.is_instance(poly)) return inst.p;
+    if (poly >= P.phase0[0] && poly < P.phase0[0] + A) return adv[poly - P.phase0[0]].p;
+    throw std::invalid_argument("check_witness: polynomial " + std::to_string(poly) + " is neither fixed, instance nor advice");
+  };
+  constexpr uint32_t RESULT_BASE = 1u << 20;   // ids of a batch's result temporaries, above every id the compiler hands out
+  std::vector<DevicePoly> result;
+  auto resolve = [&](const Atom &a) -> const void * {
+    if (a.kind == A_TMP) return a.idx >= RESULT_BASE ? result.at(a.idx - RESULT_BASE).p : tmp_at(a.idx).p;
+    if (a.kind == A_COMMON) return pk.common_lagrange[a.idx].p ? pk.common_lagrange[a.idx].p : from_coeff(a);
+    return column(a.idx);
+  };
+  auto dst_of = [&](int dst) -> void * { return (uint32_t)dst >= RESULT_BASE ? result.at((uint32_t)dst - RESULT_BASE).p : tmp_at((uint32_t)dst).p; };
+  // ---- gates: batches of temporaries, one synchronisation per batch
+  {
+    Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, {});   // no challenge is drawn before the gates: one that names a challenge is no gate of a one-phase circuit
+    const uint32_t B = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, (uint64_t(1) << 28) / n));   // 8 GiB of temporaries at most
+    const size_t NG = P.gates.size();
+    for (size_t g0 = 0; g0 < NG; g0 += B) {
+      const uint32_t nb = (uint32_t)std::min<size_t>(B, NG - g0);
+      while (result.size() < nb) result.emplace_back(n, 0);
+      std::vector<const void *> ptrs(nb);
+      for (uint32_t b = 0; b < nb; b++) {
+        cmp.tmp_base = 0; cmp.tmp_next = 0;
+        cmp.emit((int)(RESULT_BASE + b), cmp.compile(*P.gates[g0 + b].expr));
+        for (const auto &L : cmp.out) run_launch(L, dst_of(L.dst), n, fr_one(), L.accumulate, resolve);
+        cmp.out.clear();
+        ptrs[b] = result[b].p;
+      }
+      const halo2::NonzeroRows r = halo2::nonzero_rows(ptrs, n, opt.cap);
+      for (uint32_t b = 0; b < nb; b++) {
+        const uint32_t index = (uint32_t)(P.gates[g0 + b].expr - P.numerator.kids.data());
+        for (uint32_t s = 0; s < opt.cap && r.rows_of(b)[s] != ~uint64_t(0); s++) out.push_back({VerifyFailure::Gate, index, r.rows_of(b)[s], r.counts[b], 0, 0, 0});
+        if (opt.cap == 0 && r.counts[b]) out.push_back({VerifyFailure::Gate, index, ~uint64_t(0), r.counts[b], 0, 0, 0});   // counts only: the row is not known
+      }
+    }
+    result.clear(); tmp.clear();
+  }
+  // ---- copy constraints
+  {
+    const uint32_t NP = (uint32_t)wit.pcols.size();
+    std::vector<uint64_t> cells, images;
+    { halo2::PermutationAssembly as(NP, n); for (const auto &cp : wit.pairs) as.copy(cp.ja, cp.ra, cp.jb, cp.rb); as.overrides(cells, images); }
+    std::vector<const void *> cols(NP); for (uint32_t j = 0; j < NP; j++) cols[j] = column(wit.pcols[j].column);
+    if (NP) {
+      const halo2::CopyCheck r = halo2::copy_check(cols, P.k, cells, images, opt.cap);
+      const uint64_t mask = n - 1;
+      for (uint32_t s = 0; s < opt.cap && r.failed_t[s] != ~uint64_t(0); s++) {
+        const uint64_t t = r.failed_t[s], c = cells[t], im = images[t];
+        out.push_back({VerifyFailure::Copy, (uint32_t)t, c & mask, r.n_failed, (uint32_t)(c >> P.k), (uint32_t)(im >> P.k), im & mask});
+      }
+      if (opt.cap == 0 && r.n_failed) out.push_back({VerifyFailure::Copy, ~0u, ~uint64_t(0), r.n_failed, 0, 0, 0});
+    }
+  }
+  // ---- lookups, under a theta of the check's own
+  if (NL) {
+    detail::Rng rng(opt.theta_seed); Fr theta = rng.uniform(); while (fr_is_zero(theta)) theta = rng.uniform();
+    Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, {theta});
+    DevicePoly m(n, 0);
+    for (uint32_t l = 0; l < NL; l++) {
+      const Lookup &lk = P.lookups[l];
+      cmp.tmp_base = 2; cmp.tmp_next = 0;
+      cmp.emit(0, cmp.compile(*lk.table)); cmp.emit(1, cmp.compile(*lk.input));
+      for (const auto &L : cmp.out) run_launch(L, dst_of(L.dst), n, fr_one(), L.accumulate, resolve);
+      cmp.out.clear();
+      const void *inputs[1] = {tmp_at(1).p}; uint64_t missing = ~uint64_t(0);
+      const int rc = mi355_fr_lookup_multiplicities_dev(m.p, n, tmp_at(0).p, u, inputs, 1, u, 0, &missing);
+      if (rc == MI355_EBADARG && missing != ~uint64_t(0)) out.push_back({VerifyFailure::Lookup, l, missing & ((uint64_t(1) << 40) - 1), 1, (uint32_t)(missing >> 40), 0, 0});
+      else check(rc);
+    }
+  }
+  check(mi355_synchronize());
+  return out;
+}
+
 // ------------------------------------------------------------------------------------------------ create_proof
 struct ProofOptions { int devices = 1; int threads = 8; uint32_t commit_batch = 0 /* 0: by column count */; int upload_threads = 1; int early_intt = -1 /* -1: by column count */;
                       bool sparse_uploads = false /* columns that are at least half zeros cross PCIe as (index, value) pairs */;
@@ -426,6 +564,8 @@ struct ProofOptions { int devices = 1; int threads = 8; uint32_t commit_batch = 
                       bool device_multiplicities = false /* step 3 computes the multiplicity columns on the device after theta (mi355_fr_lookup_multiplicities_dev), as the scroll fork's
                                                             mv_lookup prover does on the CPU: the caller's `m` columns are not read (they may be empty), only Circuit::m_blind */;
                       bool multiplicity_rule_last = false /* with device_multiplicities: a repeated table value's count goes to its LAST usable row (default: the first) */;
+                      bool check_witness = false /* run plonk::check_witness on the witness first and throw WitnessError (the failures, the first one named in the message) before anything is written to the
+                                                    transcript.  The check does its own upload, so the witness crosses the link twice; sharing the prover's uploads is not done */;
                       TranscriptKind transcript = TranscriptKind::ByLayer /* the reference's choice for the protocol's layer (reference_transcript below): Poseidon for 0-5, Evm for 6; or name one */; };
 // the transcript the reference proves a layer with: Poseidon for every proof the next layer verifies in-circuit (layers 0-5, [REF integration/src/prove.rs:30-43,67,95-97] -> snark-verifier-sdk
 // gen_snark_shplonk), Keccak in the EVM layout for layer 6 (gen_evm_proof_shplonk: what the released verifier contract reads).  Files without a layer number are the reference's fixtures (layers 2, 4).
@@ -476,6 +616,7 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
   if (pk.resident_cosets && pk.devices != std::max(1, opt.devices)) throw std::invalid_argument("create_proof: ProofOptions::devices (" + std::to_string(opt.devices) + ") differs from the proving key's (" + std::to_string(pk.devices) + ") while its coset parts are resident");
   const int D = std::max(1, std::min<int>(opt.devices, (int)Q));
   auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+  if (opt.check_witness) { CheckOptions co; co.threads = opt.threads; std::vector<VerifyFailure> bad = check_witness(pk, wit, co); if (!bad.empty()) throw WitnessError(std::move(bad)); }
   const auto t_start = Clock::now(); auto tl = t_start;
   auto lap = [&](int step) { R.step_ms[step] += ms_since(tl); tl = Clock::now(); };
   Transcript T(opt.transcript == TranscriptKind::ByLayer ? reference_transcript(P) : opt.transcript);

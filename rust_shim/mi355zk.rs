@@ -98,6 +98,9 @@ extern "C" {
                                               n_inputs: u32, input_rows: u64, flags: u32, missing_out: *mut u64) -> c_int;
     pub fn mi355_fr_permutation_sigma_dev(sigma_dev: *const *mut c_void, n_cols: u32, log_n: u32, delta: *const c_void, omega: *const c_void,
                                           cells_host: *const u64, images_host: *const u64, count: u64, flags: u32) -> c_int;
+    pub fn mi355_fr_nonzero_rows_dev(vecs_dev: *const *const c_void, batch: u32, n: u64, cap: u32, counts_out_host: *mut u64, rows_out_host: *mut u64) -> c_int;
+    pub fn mi355_fr_copy_check_dev(cols_dev: *const *const c_void, n_cols: u32, log_n: u32, cells_host: *const u64, images_host: *const u64, count: u64, cap: u32,
+                                   n_failed_out: *mut u64, failed_t_out_host: *mut u64) -> c_int;
     pub fn mi355_fr_kate_division_dev(dst_dev: *mut c_void, poly_dev: *const c_void, n: u64, z: *const c_void) -> c_int;
     pub fn mi355_eval_polynomial_batch_dev(polys_dev: *const *const c_void, batch: u32, n: u64, points: *const c_void, out_fr_host: *mut c_void) -> c_int;
     pub fn mi355_eval_polynomial_dev(poly_dev: *const c_void, n: u64, point: *const c_void, out_fr_host: *mut c_void) -> c_int;
@@ -280,6 +283,29 @@ pub fn permutation_sigma(k: u32, n_cols: usize, delta: &Fr, omega: &Fr, cells: &
     let rc = unsafe { mi355_fr_permutation_sigma_dev(ptrs.as_ptr(), n_cols as u32, k, delta as *const Fr as *const c_void, omega as *const Fr as *const c_void,
                                                      cells.as_ptr(), images.as_ptr(), cells.len() as u64, if trusted { 1 } else { 0 }) };
     if rc == MI355_OK { Some(cols) } else { None }
+}
+/// `MockProver::verify`'s gate check on resident vectors (each a gate evaluated on the Lagrange domain): per vector the number of non-zero rows and the smallest `cap`
+/// of them, ascending (unused slots `u64::MAX`).  A failing witness is not an error.  None -> the library refused the call.
+pub fn nonzero_rows(vecs: &[&DevicePoly], cap: u32) -> Option<(Vec<u64>, Vec<u64>)> {
+    if !available() || vecs.is_empty() { return None; }
+    let n = vecs[0].len();
+    if n == 0 || vecs.iter().any(|v| v.len() != n) { return None; }
+    let ptrs: Vec<*const c_void> = vecs.iter().map(|v| v.as_ptr()).collect();
+    let mut counts = vec![0u64; vecs.len()];
+    let mut rows = vec![u64::MAX; vecs.len() * cap as usize];
+    let rc = unsafe { mi355_fr_nonzero_rows_dev(ptrs.as_ptr(), vecs.len() as u32, n as u64, cap, counts.as_mut_ptr(), if cap == 0 { std::ptr::null_mut() } else { rows.as_mut_ptr() }) };
+    if rc == MI355_OK { Some((counts, rows)) } else { None }
+}
+/// `MockProver::verify`'s permutation check: the pairs (cell, image) of `Assembly::mapping` (cell = column * n + row) whose two cells hold different words, over the
+/// resident columns in permutation position order.  Returns the number of failing pairs and the smallest `cap` failing t, ascending (unused slots `u64::MAX`).
+pub fn copy_check(k: u32, cols: &[&DevicePoly], cells: &[u64], images: &[u64], cap: u32) -> Option<(u64, Vec<u64>)> {
+    if !available() || cols.is_empty() || k > 28 || cells.len() != images.len() || cols.iter().any(|c| c.len() != 1usize << k) { return None; }
+    let ptrs: Vec<*const c_void> = cols.iter().map(|c| c.as_ptr()).collect();
+    let mut n_failed = 0u64;
+    let mut failed = vec![u64::MAX; cap as usize];
+    let rc = unsafe { mi355_fr_copy_check_dev(ptrs.as_ptr(), cols.len() as u32, k, cells.as_ptr(), images.as_ptr(), cells.len() as u64, cap, &mut n_failed,
+                                              if cap == 0 { std::ptr::null_mut() } else { failed.as_mut_ptr() }) };
+    if rc == MI355_OK { Some((n_failed, failed)) } else { None }
 }
 impl GpuBasis {
     /// commit / commit_lagrange of a resident polynomial: the scalars never leave HBM (with several devices each shard's slice crosses xGMI).

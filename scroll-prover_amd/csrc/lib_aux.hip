@@ -1,7 +1,8 @@
 // lib_aux.hip -- libmi355zk.so, the translation unit of the kernels either side of MSM / NTT: the DFT over G1 points
 // (g1fft.hpp: g_to_lagrange, ParamsKZG::downsize), the multiplicative scans of the permutation / lookup arguments and kate_division
 // (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), the multiplicities of the mv-lookup argument
-// (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), and the compressed-point codec of G1 (g1codec.hpp).  Host logic only.
+// (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), the compressed-point codec of G1 (g1codec.hpp), and the two reductions of the witness
+// check (check.hpp).  Host logic only.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #include "g1fft.hpp"
 #include "frscan.hpp"
@@ -9,6 +10,7 @@
 #include "lookup.hpp"
 #include "perm.hpp"
 #include "g1codec.hpp"
+#include "check.hpp"
 #include "lib_common.hpp"
 #include <thread>
 
@@ -543,6 +545,106 @@ int mi355_fr_permutation_sigma_dev(void *const *sigma_dev, uint32_t n_cols, uint
       if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: kernel launch failed"); return; }
     }
     if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: stream synchronize failed"); return; }
+  }();
+  (void)mi355_buf_free(ws);
+  if (rc != MI355_OK) return rc;
+  return finish_async();
+  });
+}
+
+// ---- the reductions of the witness check (check.hpp): count + the smallest `cap` failing indices, ascending.  Three launches per vector batch / staged piece --
+// count per workgroup, scan of the counts, ranked write -- and ONE synchronisation at the end, when the totals and the indices come back.  Workspace: ONE pooled
+// mi355_buf block (the pointer table, the totals, the index lists, 8 B per workgroup of CHECK_TILE elements; copy_check: two lists of at most CHECK_STAGE entries),
+// handed back to the pool on return.
+constexpr uint64_t CHECK_STAGE = 1ull << 22;   // a multiple of CHECK_TILE
+static uint64_t align256(uint64_t b) { return (b + 255) & ~255ull; }
+int mi355_fr_nonzero_rows_dev(const void *const *vecs_dev, uint32_t batch, uint64_t n, uint32_t cap, uint64_t *counts_out_host, uint64_t *rows_out_host) {
+  return guarded([&]() -> int {
+  int slot = 0;
+  for (uint32_t v = 0; vecs_dev && v < batch; v++) { int s2; CHK(common_slot({vecs_dev[0], vecs_dev[v]}, &s2, "fr_nonzero_rows")); if (v == 0) slot = s2; }
+  DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (batch == 0 || n == 0) return fail(MI355_EBADARG, "fr_nonzero_rows: batch and n must not be zero");
+  if (n >= (1ull << 40)) return fail(MI355_EBADARG, "fr_nonzero_rows: n too large");
+  if (cap > CHECK_MAX_CAP) return fail(MI355_EBADARG, "fr_nonzero_rows: cap " + std::to_string(cap) + " exceeds " + std::to_string(CHECK_MAX_CAP));
+  if (!vecs_dev || !counts_out_host || (cap && !rows_out_host)) return fail(MI355_EBADARG, "fr_nonzero_rows: null pointer");
+  for (uint32_t v = 0; v < batch; v++) {
+    if (!vecs_dev[v]) return fail(MI355_EBADARG, "fr_nonzero_rows: null vector " + std::to_string(v));
+    if ((uintptr_t)vecs_dev[v] & 15) return fail(MI355_EBADARG, "fr_nonzero_rows: vector " + std::to_string(v) + " is not 16-byte aligned");
+    CHK(buf_check_range(vecs_dev[v], n * sizeof(fe_t), "fr_nonzero_rows"));
+  }
+  const uint32_t nblocks = (uint32_t)ceil_div(n, CHECK_TILE);
+  const uint64_t off_tot = align256((uint64_t)batch * 8), off_rows = off_tot + align256((uint64_t)batch * 8), off_cnt = off_rows + align256((uint64_t)batch * cap * 8),
+                 off_pre = off_cnt + align256((uint64_t)batch * nblocks * 4), bytes = off_pre + align256((uint64_t)batch * nblocks * 4);
+  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
+  int rc = MI355_OK;
+  [&]() {
+    char *base = (char *)ws; hipStream_t s = g.stream;
+    if ((rc = mi355_buf_upload(ws, vecs_dev, (uint64_t)batch * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
+    const fe_t *const *vecs = (const fe_t *const *)base; unsigned long long *tot = (unsigned long long *)(base + off_tot); uint64_t *rows = (uint64_t *)(base + off_rows);
+    uint32_t *cnt = (uint32_t *)(base + off_cnt), *pre = (uint32_t *)(base + off_pre);
+    if (hipMemsetAsync(tot, 0, (uint64_t)batch * 8, s) != hipSuccess || (cap && hipMemsetAsync(rows, 0xff, (uint64_t)batch * cap * 8, s) != hipSuccess)) { rc = fail(MI355_EHIP, "fr_nonzero_rows: memset failed"); return; }
+    {
+      Scope sc("nonzero_rows");
+      for (uint32_t v0 = 0; v0 < batch; v0 += 65535) {   // blockIdx.y = vector
+        const uint32_t nv = std::min<uint32_t>(65535, batch - v0); const uint64_t o = (uint64_t)v0 * nblocks;
+        hipLaunchKernelGGL(k_fr_nonzero_rows<0>, dim3(nblocks, nv), dim3(CHECK_THREADS), 0, s, vecs + v0, n, cap, cnt + o, (const uint32_t *)(pre + o), rows + (uint64_t)v0 * cap);
+        hipLaunchKernelGGL(k_check_scan, dim3(nv), dim3(CHECK_THREADS), 0, s, (const uint32_t *)(cnt + o), pre + o, nblocks, tot + v0);
+        if (cap) hipLaunchKernelGGL(k_fr_nonzero_rows<1>, dim3(nblocks, nv), dim3(CHECK_THREADS), 0, s, vecs + v0, n, cap, cnt + o, (const uint32_t *)(pre + o), rows + (uint64_t)v0 * cap);
+      }
+    }
+    if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_nonzero_rows: kernel launch failed"); return; }
+    if (hipMemcpyAsync(counts_out_host, tot, (uint64_t)batch * 8, hipMemcpyDeviceToHost, s) != hipSuccess || (cap && hipMemcpyAsync(rows_out_host, rows, (uint64_t)batch * cap * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_nonzero_rows: stream synchronize failed"); return; }
+  }();
+  (void)mi355_buf_free(ws);
+  if (rc != MI355_OK) return rc;
+  return finish_async();
+  });
+}
+int mi355_fr_copy_check_dev(const void *const *cols_dev, uint32_t n_cols, uint32_t log_n, const uint64_t *cells_host, const uint64_t *images_host, uint64_t count, uint32_t cap,
+                            uint64_t *n_failed_out, uint64_t *failed_t_out_host) {
+  return guarded([&]() -> int {
+  int slot = 0;
+  for (uint32_t j = 0; cols_dev && j < n_cols; j++) { int s2; CHK(common_slot({cols_dev[0], cols_dev[j]}, &s2, "fr_copy_check")); if (j == 0) slot = s2; }
+  DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (n_cols == 0) return fail(MI355_EBADARG, "fr_copy_check: n_cols must not be zero");
+  if (log_n > PERM_MAX_LOG_N) return fail(MI355_EBADARG, "fr_copy_check: log_n > 28");
+  if (cap > CHECK_MAX_CAP) return fail(MI355_EBADARG, "fr_copy_check: cap " + std::to_string(cap) + " exceeds " + std::to_string(CHECK_MAX_CAP));
+  if (!cols_dev || !n_failed_out || (cap && !failed_t_out_host) || (count && (!cells_host || !images_host))) return fail(MI355_EBADARG, "fr_copy_check: null pointer");
+  const uint64_t n = 1ull << log_n, total = (uint64_t)n_cols * n;
+  for (uint32_t j = 0; j < n_cols; j++) {
+    if (!cols_dev[j]) return fail(MI355_EBADARG, "fr_copy_check: null column " + std::to_string(j));
+    if ((uintptr_t)cols_dev[j] & 15) return fail(MI355_EBADARG, "fr_copy_check: column " + std::to_string(j) + " is not 16-byte aligned");
+    CHK(buf_check_range(cols_dev[j], n * sizeof(fe_t), "fr_copy_check"));
+  }
+  // a cell >= n_cols * n would be a load outside the columns: the range check of perm_check (the bijection is not this call's business: any list of pairs may be compared)
+  { uint64_t bad = 0; std::string why; if (perm_check(cells_host, images_host, count, total, PERM_FLAG_TRUSTED, &bad, &why)) return fail(MI355_EBADARG, "fr_copy_check: pair " + std::to_string(bad) + ": " + why); }
+  const uint64_t stage = std::min(count, CHECK_STAGE); const uint32_t max_blocks = (uint32_t)ceil_div(stage, CHECK_TILE);
+  const uint64_t off_tot = align256((uint64_t)n_cols * 8), off_failed = off_tot + 256, off_cnt = off_failed + align256((uint64_t)cap * 8), off_pre = off_cnt + align256((uint64_t)max_blocks * 4),
+                 off_cells = off_pre + align256((uint64_t)max_blocks * 4), off_images = off_cells + align256(stage * 8), bytes = off_images + align256(stage * 8);
+  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
+  int rc = MI355_OK;
+  [&]() {
+    char *base = (char *)ws; hipStream_t s = g.stream;
+    if ((rc = mi355_buf_upload(ws, cols_dev, (uint64_t)n_cols * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
+    const fe_t *const *cols = (const fe_t *const *)base; unsigned long long *tot = (unsigned long long *)(base + off_tot); uint64_t *failed = (uint64_t *)(base + off_failed);
+    uint32_t *cnt = (uint32_t *)(base + off_cnt), *pre = (uint32_t *)(base + off_pre);
+    const uint64_t *cells = (const uint64_t *)(base + off_cells), *images = (const uint64_t *)(base + off_images);
+    if (hipMemsetAsync(tot, 0, 8, s) != hipSuccess || (cap && hipMemsetAsync(failed, 0xff, (uint64_t)cap * 8, s) != hipSuccess)) { rc = fail(MI355_EHIP, "fr_copy_check: memset failed"); return; }
+    for (uint64_t lo = 0; lo < count; lo += stage) {   // an upload into the staging area waits for the kernels that read the previous piece (mi355_buf_upload into a block in use)
+      const uint64_t len = std::min(stage, count - lo); const uint32_t nblocks = (uint32_t)ceil_div(len, CHECK_TILE);
+      if ((rc = mi355_buf_upload(base + off_cells, cells_host + lo, len * 8)) != MI355_OK || (rc = mi355_buf_upload(base + off_images, images_host + lo, len * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
+      Scope sc("copy_check");
+      hipLaunchKernelGGL(k_fr_copy_check<0>, dim3(nblocks), dim3(CHECK_THREADS), 0, s, cols, log_n, cells, images, len, lo, cap, cnt, (const uint32_t *)pre, failed);
+      hipLaunchKernelGGL(k_check_scan, dim3(1), dim3(CHECK_THREADS), 0, s, (const uint32_t *)cnt, pre, nblocks, tot);
+      if (cap) hipLaunchKernelGGL(k_fr_copy_check<1>, dim3(nblocks), dim3(CHECK_THREADS), 0, s, cols, log_n, cells, images, len, lo, cap, cnt, (const uint32_t *)pre, failed);
+      sc.close();
+      if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_copy_check: kernel launch failed"); return; }
+    }
+    if (hipMemcpyAsync(n_failed_out, tot, 8, hipMemcpyDeviceToHost, s) != hipSuccess || (cap && hipMemcpyAsync(failed_t_out_host, failed, (uint64_t)cap * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_copy_check: stream synchronize failed"); return; }
   }();
   (void)mi355_buf_free(ws);
   if (rc != MI355_OK) return rc;

@@ -372,6 +372,44 @@ def permutation_sigma(n_cols: int, log_n: int, delta: np.ndarray, omega: np.ndar
     return out
 
 
+def nonzero_rows(vecs, cap: int = 16):
+    """MockProver::verify's gate check on device tensors (mi355_fr_nonzero_rows_dev): `vecs` is one tensor or a list of tensors of n 32-byte words each (a gate
+    evaluated on the Lagrange domain).  Returns (counts, rows): counts[v] = the rows of vector v whose word is not all-zero, rows[v] = the smallest `cap` of them,
+    ascending, unused slots 2^64 - 1 (numpy uint64, shapes [batch] and [batch, cap]).  A failing witness is not an error.  cap = 0: counts only."""
+    if not isinstance(vecs, (list, tuple)):
+        vecs = [vecs]
+    n = vecs[0].numel() * vecs[0].element_size() // 32 if vecs else 0
+    for t in vecs:
+        assert t.numel() * t.element_size() == 32 * n, "nonzero_rows: the vectors differ in length"
+    arr = (C.c_void_p * max(1, len(vecs)))(*[t.data_ptr() for t in vecs])
+    counts = np.zeros(len(vecs), dtype=np.uint64)
+    rows = np.full((len(vecs), cap), (1 << 64) - 1, dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    check(lib().mi355_fr_nonzero_rows_dev(arr, len(vecs), n, cap, counts.ctypes.data_as(u64p), rows.ctypes.data_as(u64p) if cap else None))
+    return counts, rows
+
+
+def copy_check(cols, cells, images, cap: int = 16):
+    """MockProver::verify's permutation check on device tensors (mi355_fr_copy_check_dev): `cols` are the columns in permutation position order, 2^log_n words each;
+    (cells, images) is what PermutationAssembly.overrides() returns (cell = column * n + row).  Pair t fails when the two cells hold different words.  Returns
+    (n_failed, failed_t): the number of failing pairs and the smallest `cap` failing t, ascending, unused slots 2^64 - 1.  A list with a cell outside the columns raises
+    Mi355Error (EBADARG) naming the pair, before anything reaches the device."""
+    cells = np.ascontiguousarray(cells, dtype=np.uint64).reshape(-1)
+    images = np.ascontiguousarray(images, dtype=np.uint64).reshape(-1)
+    assert cells.size == images.size, "copy_check: cells and images differ in length"
+    n = cols[0].numel() * cols[0].element_size() // 32 if len(cols) else 1
+    log_n = max(0, n.bit_length() - 1)
+    for t in cols:
+        assert t.numel() * t.element_size() == 32 << log_n, "copy_check: a column is not 2^log_n words"
+    arr = (C.c_void_p * max(1, len(cols)))(*[t.data_ptr() for t in cols])
+    n_failed = C.c_uint64(0)
+    failed = np.full(cap, (1 << 64) - 1, dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    check(lib().mi355_fr_copy_check_dev(arr, len(cols), log_n, cells.ctypes.data_as(u64p), images.ctypes.data_as(u64p), cells.size, cap, C.byref(n_failed),
+                                        failed.ctypes.data_as(u64p) if cap else None))
+    return int(n_failed.value), failed
+
+
 # halo2curves bn256 G2 generator (x.c0, x.c1, y.c0, y.c1) [EXT-recalled src/bn256/curve.rs]; the same four words are the first pairing
 # input of the released verifier [REF release-v0.13.1/evm_verifier.yul:1230-1233] (tests/test_oracle_golden.py)
 G2_GENERATOR = (0x1800DEEF121F1E76426A00665E5C4479674322D4F75EDADD46DEBD5CD992F6ED, 0x198E9393920D483A7260BFB731FB5D25F1AA493335A9E71297E485B7AEF312C2,

@@ -135,3 +135,35 @@ def run_permutation_keygen(layer: int, k: int | None = None, out_dir: str | None
             with open(p, "rb") as f:
                 rec[name] = f.read()
     return rec
+
+
+def run_witness_check(layer: int, k: int | None = None, out_dir: str | None = None, args=(), env=None, timeout: int = 1800, protocol_file: str | None = None, **shape) -> dict:
+    """tests/cpp/test_witness_check.cpp: plonk::check_witness (MockProver::verify on the device) on the builder's instance of one layer, with the cells named by
+    "--corrupt advice:<col>:<row>" / "--corrupt instance:<i>" changed first.  Returns the program's record with `check` (check.json: check_ms and the failures) and, under
+    "--prove", `prove` (prove.json), `proof`, `proof_plain`, `vk` and `instances`; the dumped inputs are in `out_dir`.  args: "--builder-only" (no device), "--cap N"."""
+    from . import build
+    out_dir = out_dir or tempfile.mkdtemp(prefix=f"mi355_witness_check_l{layer}_")
+    os.makedirs(out_dir, exist_ok=True)
+    proto = write_protocol(layer, out_dir, k, protocol_file, **shape)
+    e = dict(os.environ)
+    e.update(env or {})
+    t0 = time.perf_counter()
+    out = subprocess.run([build.build_cpp("test_witness_check"), "--protocol", proto, "--out", out_dir] + list(args), capture_output=True, text=True, timeout=timeout, env=e)
+    line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
+    rec = {"layer": layer, "ok": False, "returncode": out.returncode, "out_dir": out_dir, "protocol_path": proto, "process_wall_s": time.perf_counter() - t0}
+    if out.returncode != 0 or line is None:
+        rec["error"] = (out.stdout + out.stderr)[-1200:]
+        return rec
+    rec.update(json.loads(line))
+    rec["ok"] = True
+    for name in ("check", "prove"):
+        p = os.path.join(out_dir, name + ".json")
+        if os.path.exists(p):
+            with open(p) as f:
+                rec[name] = json.load(f)
+    for name in ("proof", "proof_plain", "vk", "instances"):
+        p = os.path.join(out_dir, name + ".bin")
+        if os.path.exists(p):
+            with open(p, "rb") as f:
+                rec[name] = f.read()
+    return rec
