@@ -337,7 +337,8 @@ int mi355_g2_mul_host(const void *p_g2affine_host, const void *scalar_fr, void *
  * bases: n x 128-byte G2Affine as above (identity = all zero); scalars: n x 32-byte Fr, Montgomery form as for mi355_msm_g1_*; out: one
  * normalised G2Affine (identity = 128 zero bytes; n == 0 gives the identity).  Every base is checked to be on the twist in a device pass:
  * MI355_EBADARG, and mi355_last_error() names the first bad index, when one is not.  Bases are NOT checked for subgroup membership (a
- * point of the twist outside the r-torsion is summed like any other).  One device (the primary), no CPU fallback (MI355_ENODEVICE
+ * point of the twist outside the r-torsion is summed like any other: its scalar multiplies it as the canonical integer below r, exactly as
+ * mi355_g2_mul_host does).  One device (the primary), no CPU fallback (MI355_ENODEVICE
  * without a gfx950 device); same locking and stream order as the G1 entry points.  mi355_msm_last_plan reports the call's window
  * bits, windows and entries; mi355_msm_set_window_bits applies as for G1.  The kernels report under msm_g2_* in mi355_profile_get.
  *   _adhoc_host: bases and scalars in host memory.   _dev: both in device memory of the primary device (mi355_buf_alloc blocks or any

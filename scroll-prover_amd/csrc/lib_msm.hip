@@ -222,7 +222,10 @@ int msm_sort_stage(const PolyPtrs &inl, const fe_t *const *polys_dev, uint32_t M
   {
     Scope sc(g2 ? "msm_g2_digits" : "msm_digits", s);
     HIPCHK(hipMemsetAsync(coarse_hist, 0, ((size_t)S.regions + 1) * 4, s));
-    hipLaunchKernelGGL(k_msm_digits, dim3(grid_stream / M > 0 ? grid_stream / M : 1, M), dim3(256), (size_t)S.regions * 4, s, inl, polys_dev, enc, P, coarse_hist, S.fb, S.cb_bits, S.shared);
+    const dim3 dgrid(grid_stream / M > 0 ? grid_stream / M : 1, M);
+    // G1: k and r - k are the same term up to the sign of the point; a twist point need not have order r (k_msm_g2_validate checks the curve equation only)
+    if (g2) hipLaunchKernelGGL(k_msm_digits<false>, dgrid, dim3(256), (size_t)S.regions * 4, s, inl, polys_dev, enc, P, coarse_hist, S.fb, S.cb_bits, S.shared);
+    else hipLaunchKernelGGL(k_msm_digits<true>, dgrid, dim3(256), (size_t)S.regions * 4, s, inl, polys_dev, enc, P, coarse_hist, S.fb, S.cb_bits, S.shared);
   }
   {
     Scope sc(g2 ? "msm_g2_sort" : "msm_sort", s);

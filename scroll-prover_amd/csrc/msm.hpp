@@ -193,7 +193,11 @@ struct G1Ops {   // G1 on the 29-bit field: 144-byte XYZZ records, one-lane and 
 // ---- 1. digits.  Plane layout enc[w * n + i]: 0 for a zero digit, else |d| (1 .. 2^(c-1)) with bit 31 = sign.
 // up to 8 polynomial pointers travel as a kernel argument (copied at launch: no staging copy, nothing for an asynchronous caller to keep
 // alive); larger batches pass a device array
+// FOLD: take the smaller of k and r - k (below).  That is the same term only for a point that r annihilates: every point of G1 (cofactor 1), but not
+// every point of the twist, whose bases are validated against the curve equation alone -- the G2 MSM runs without it and multiplies by the integer k,
+// as k_g2_mul does.  W = ceil(255 / c) windows hold either form: k < r < 2^254 leaves the top digit at most 2^(c-1), so the recoding never carries out.
 struct PolyPtrs { const fe_t *p[8]; };
+template <bool FOLD>
 __global__ void __launch_bounds__(256) k_msm_digits(PolyPtrs inl, const fe_t *const *__restrict__ polys, uint32_t *__restrict__ enc, MsmPlan P,
                                                      uint32_t *__restrict__ coarse_hist, uint32_t fb, uint32_t cb_bits, uint32_t shared) {
   // the level-1 (coarse) histogram of the sorter is taken here, while the digits are in registers: LDS counters per block,
@@ -217,7 +221,7 @@ __global__ void __launch_bounds__(256) k_msm_digits(PolyPtrs inl, const fe_t *co
       for (int q = 0; q < 8; q++) { const uint64_t d = (uint64_t)FrP::mod(q) - k.l[q] - borrow; t.l[q] = (uint32_t)d; borrow = (uint32_t)(d >> 63); } }
     bool flip = false;
 #pragma unroll
-    for (int q = 7; q >= 0; q--) { if (t.l[q] != k.l[q]) { flip = t.l[q] < k.l[q]; break; } }
+    for (int q = 7; q >= 0; q--) { if (t.l[q] != k.l[q]) { flip = FOLD && t.l[q] < k.l[q]; break; } }
     const uint32_t sign_flip = flip ? 0x80000000u : 0u;
     uint32_t l0 = flip ? t.l[0] : k.l[0], l1 = flip ? t.l[1] : k.l[1], l2 = flip ? t.l[2] : k.l[2], l3 = flip ? t.l[3] : k.l[3];
     uint32_t l4 = flip ? t.l[4] : k.l[4], l5 = flip ? t.l[5] : k.l[5], l6 = flip ? t.l[6] : k.l[6], l7 = flip ? t.l[7] : k.l[7];

@@ -1,4 +1,6 @@
 """helpers shared by the -m gpu tests (TEST INFRASTRUCTURE)."""
+import functools
+
 import numpy as np
 
 from oracle import cref, pyref
@@ -128,3 +130,184 @@ FULL_RANGE_DRAWS = {
 def full_range(name, n):
     """the first n words of the named draw"""
     return rand_fr_full(np.random.default_rng(FULL_RANGE_DRAWS[name][0]), n)
+
+
+# ---- curve points whose coordinate WORDS are adversarial (tests/test_gpu_curve_adversarial.py and the host tests of the limb code).  Every other
+# point of the suite is a multiple of a generator: its words are uniform in [0, p), so nothing ever sits on an edge of the limb grids from_sat slices.
+P = pyref.P_MOD
+_RINV_P = pow(pyref.MONT_R, -1, P)
+_T9 = (P - 1) // 9                                        # p - 1 = 9 t with 3 not dividing t
+assert P % 4 == 3 and 9 * _T9 == P - 1 and _T9 % 3 != 0 and ALL_ONES_LIMBS < P <= ((0x30644E << 232) | ((1 << 232) - 1))
+_ZETA9 = next(pow(g, _T9, P) for g in range(2, 50) if pow(g, 3 * _T9, P) != 1)      # a primitive 9th root of unity
+FQ_BETA = pow(_ZETA9, 3, P)                               # a primitive cube root of unity: (x, y) -> (beta x, y) is the endomorphism lambda
+LIFT_MAX = 8                                              # a pool word lifts to a coordinate within this distance (tests/test_host_logic.py)
+
+
+def adversarial_fq_ints():
+    """adversarial_fr_ints with p in place of r: words of a base-field coordinate.  Fixed order, no duplicates, every word < p."""
+    mont = pyref.MONT_R % P
+    v = [0, 1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, mont, P - mont, ALL_ONES_LIMBS]
+    for i in range(1, 9):
+        v += [(1 << (29 * i)) - 1, 1 << (29 * i), (1 << (29 * i)) + 1]
+    for i in range(1, 8):
+        v += [(1 << (32 * i)) - 1, 1 << (32 * i)]
+    v += [(1 << 252) - 1, 1 << 252, 1 << 253]
+    v += [int("55" * 32, 16) % P, int("AA" * 32, 16) % P]
+    v += [c * mont % P for c in (0, 1, 2, P - 1)]
+    assert all(0 <= x < P for x in v)
+    return list(dict.fromkeys(v))
+
+
+def fq_sqrt(a):
+    """a square root of a modulo p (p = 3 mod 4), or None"""
+    y = pow(a, (P + 1) // 4, P)
+    return y if y * y % P == a % P else None
+
+
+def fq_cbrt(a):
+    """a cube root of a modulo p, or None: a^(1/3 mod t) is a root up to a 9th root of unity"""
+    a %= P
+    if a == 0:
+        return 0
+    if pow(a, (P - 1) // 3, P) != 1:
+        return None
+    c = pow(a, pow(3, -1, _T9), P)
+    for _ in range(9):
+        if pow(c, 3, P) == a:
+            return c
+        c = c * _ZETA9 % P
+    raise AssertionError("a cube without a cube root")
+
+
+def _nearest(w, lift):
+    """(value of lift, signed distance) at the nearest word w + d, w - d (d = 0, 1, ..; + before -) inside [0, p) at which lift gives something"""
+    for d in range(LIFT_MAX + 1):
+        for s in ((0,) if d == 0 else (d, -d)):
+            if 0 <= w + s < P:
+                got = lift(w + s)
+                if got is not None:
+                    return got, s
+    raise AssertionError("word %#x does not lift within %d" % (w, LIFT_MAX))
+
+
+@functools.lru_cache(maxsize=None)
+def _g1_pool(reading):
+    assert reading in ("mont", "canonical")
+    val = (lambda w: w * _RINV_P % P) if reading == "mont" else (lambda w: w)
+
+    def lift_x(w):
+        x = val(w)
+        y = fq_sqrt((x * x * x + 3) % P)
+        return None if y is None or x == 0 else [(x, y), (x, P - y)]
+
+    def lift_y(w):
+        y = val(w)
+        x = fq_cbrt((y * y - 3) % P)
+        return None if x is None or x == 0 else [(x, y), (FQ_BETA * x % P, y), (FQ_BETA * FQ_BETA * x % P, y)]
+
+    pts, words, dist, kind, index, triples = [], [], [], [], {}, []
+    for fam, lift in (("x", lift_x), ("y", lift_y)):
+        for w in adversarial_fq_ints():
+            got, d = _nearest(w, lift)
+            ids = []
+            for pt in got:
+                if pt not in index:
+                    index[pt] = len(pts); pts.append(pt); words.append(w); dist.append(d); kind.append(fam)
+                ids.append(index[pt])
+            if fam == "y" and ids not in triples:
+                triples.append(ids)
+    abi = np.array([pyref.mont_limbs(x, P) + pyref.mont_limbs(y, P) for x, y in pts], dtype=np.uint64)
+    for a in (abi,):
+        a.setflags(write=False)
+    return {"points": abi, "words": ints_to_words(words), "dist": np.array(dist, dtype=np.int64), "kind": kind, "py": pts, "triples": triples}
+
+
+def adversarial_g1_points(reading):
+    """G1 points with an adversarial coordinate word.  reading = "mont": the pool word is the Montgomery form of the coordinate (what the MSM, FFT and
+    normalise kernels slice); "canonical": it is the value (what the codec slices).  Every word of adversarial_fq_ints is taken once as an x (both
+    points (x, +-y) are kept) and once as a y (all three points (x, y), (beta x, y), (beta^2 x, y) are kept: P, lambda P, lambda^2 P, which sum to
+    the identity and have equal y and different x), each time at the nearest word w + d, w - d (smallest d, + first) for which the point exists.
+    -> (points [m,8] u64 ABI words (Montgomery), the pool word each was built for [m,4], the signed distance d [m]); fixed order, no duplicates."""
+    g = _g1_pool(reading)
+    return g["points"].copy(), g["words"].copy(), g["dist"].copy()
+
+
+def adversarial_g1_info(reading):
+    """of the same pool: (the points as pyref tuples, "x" / "y" per point: the coordinate the word was lifted as, the index triples of the y family)"""
+    g = _g1_pool(reading)
+    return list(g["py"]), list(g["kind"]), [list(t) for t in g["triples"]]
+
+
+def adversarial_fq_non_lifting(reading):
+    """the pool words that are no x coordinate as they stand (distance != 0 in the x family), in pool order"""
+    g = _g1_pool(reading)
+    seen = dict()
+    for w, d, k in zip(words_to_ints(g["words"]), g["dist"], g["kind"]):
+        if k == "x" and d != 0:
+            seen[w] = None
+    return list(seen)
+
+
+def g1_neg_words(pts):
+    """[n,8] ABI points -> their opposites (identity entries stay all-zero)"""
+    pts = np.asarray(pts, dtype=np.uint64).reshape(-1, 8)
+    out = pts.copy()
+    for i, y in enumerate(words_to_ints(pts[:, 4:])):
+        out[i, 4:] = pyref.to_limbs((P - y) % P)
+    return out
+
+
+def f2_sqrt(a):
+    """a square root in Fq2 = Fq[u]/(u^2 + 1) by the complex method, or None.  a = (a0, a1) canonical integers."""
+    a0, a1 = a[0] % P, a[1] % P
+    if a1 == 0:
+        s = fq_sqrt(a0)
+        if s is not None:
+            return (s, 0)
+        return (0, fq_sqrt(P - a0))                       # -1 is a non-residue: exactly one of a0, -a0 is a square
+    s = fq_sqrt((a0 * a0 + a1 * a1) % P)                  # the norm; a is a square of Fq2 iff its norm is one of Fq
+    if s is None:
+        return None
+    half = (P + 1) // 2
+    x0 = fq_sqrt((a0 + s) * half % P)
+    if x0 is None:
+        x0 = fq_sqrt((a0 - s) * half % P)
+    x1 = a1 * pow(2 * x0, -1, P) % P
+    assert pyref.f2_mul((x0, x1), (x0, x1)) == (a0, a1)
+    return (x0, x1)
+
+
+@functools.lru_cache(maxsize=None)
+def _g2_pool(reading):
+    assert reading in ("mont", "canonical")
+    val = (lambda w: w * _RINV_P % P) if reading == "mont" else (lambda w: w)
+    pool = adversarial_fq_ints()
+    m = len(pool)
+    pts, words, dist, index = [], [], [], {}
+    shapes = [(w, None) for w in pool] + [(None, w) for w in pool] + [(w, pool[(5 * i + 3) % m]) for i, w in enumerate(pool)]
+    for c0w, c1w in shapes:
+        c1 = 0 if c1w is None else val(c1w)
+
+        def lift(w):
+            x = (val(w), c1)
+            if x == (0, 0):
+                return None
+            y = f2_sqrt(pyref.f2_add(pyref.f2_mul(pyref.f2_mul(x, x), x), pyref.G2_B))
+            return None if y is None or y == (0, 0) else [(x, y), (x, ((-y[0]) % P, (-y[1]) % P))]
+
+        got, d = _nearest(0 if c0w is None else c0w, lift)
+        for pt in got:
+            if pt not in index:
+                index[pt] = len(pts); pts.append(pt); words.append((c0w or 0, c1w or 0)); dist.append(d)
+    abi = np.array([pyref.g2_to_limbs(q) for q in pts], dtype=np.uint64)
+    abi.setflags(write=False)
+    return {"points": abi, "words": words, "dist": np.array(dist, dtype=np.int64), "py": pts}
+
+
+def adversarial_g2_points(reading="mont"):
+    """points of the twist y^2 = x^3 + 3 / (9 + u) with x = (w, 0), (0, w) and (w, w') over the words of adversarial_fq_ints (w' = the word 5 i + 3 places
+    on, so every word is a c1 once), c0 moved to the nearest word at which x^3 + b' is a square of Fq2, both signs of y.  On the twist, NOT in the
+    subgroup of order r: a scalar multiple of such a point is the multiple by the INTEGER, never by its residue modulo r.
+    -> (points [m,16] u64 ABI words, the pyref tuples, the signed distances of c0 [m])"""
+    g = _g2_pool(reading)
+    return g["points"].copy(), list(g["py"]), g["dist"].copy()

@@ -202,3 +202,61 @@ def test_g2_decoded_points_satisfy_the_srs_pairing_equation(codec):
     assert pairing.pairing_product_is_one([(g1, g2d), (pyref.g1_neg(g0), sg2d)])       # e(g[1], g2) == e(g[0], s_g2)
     flipped = sg2w[:63] + bytes([sg2w[63] ^ 0x40])
     assert not pairing.pairing_product_is_one([(g1, g2d), (pyref.g1_neg(g0), to_py(g2_decode(codec, flipped)))])
+
+
+# ---- points and words from the adversarial pool (tests/gpu_common.py): x on the edges of the field and of the limb grids from_sat_plain slices
+def test_adversarial_points_round_trip(codec):
+    """the "canonical" pool (the canonical x, the word the codec slices, is the adversarial word) and the "mont" pool (the ABI word compress reads is)"""
+    from tests import gpu_common as gc
+    for reading in ("canonical", "mont"):
+        pts, _, _ = gc.adversarial_g1_points(reading)
+        py, _, _ = gc.adversarial_g1_info(reading)
+        words = [cref.g1_compress(p) for p in pts]
+        assert words == [pyref.g1_compress(q) for q in py]
+        assert {w[31] >> 6 & 1 for w in words} == {0, 1}
+        assert compress(codec, pts) == words
+        got, ok = decompress(codec, words)
+        assert ok.all() and (got == pts).all(), np.nonzero((got != pts).any(axis=1))[0][:8]
+        got, ok, _ = check_words(codec, words)
+        assert ok.all()
+
+
+def test_adversarial_words_that_are_no_x_coordinate(codec):
+    """the pool words that did not lift at distance 0 (0 among them), and every pool word's neighbours, as compressed x with either sign bit: accepted
+    exactly when pyref finds a root; the first flag that is down is the first word pyref rejects"""
+    from tests import gpu_common as gc
+    non = gc.adversarial_fq_non_lifting("canonical")
+    assert 0 in non and len(non) >= 10
+    words = [word_of(x, s) for x in non for s in (0, 1)]
+    _, ok, _ = check_words(codec, words)
+    assert list(ok) == [1] + [0] * (len(words) - 1), "only x = 0 with the sign bit clear (the identity) is accepted"
+    near = [word_of(w + d, s) for w in gc.adversarial_fq_ints() for d in range(-2, 3) if 0 <= w + d < P for s in (0, 1)]
+    _, ok, classes = check_words(codec, near)
+    assert classes == {True, False}
+    rejected = [i for i, w in enumerate(near) if cref.g1_decompress(w) is None]
+    assert int(np.argmin(ok)) == rejected[0]
+
+
+def test_g2_codec_on_adversarial_twist_points(codec):
+    from tests import gpu_common as gc
+    for reading in ("canonical", "mont"):
+        pts, py, _ = gc.adversarial_g2_points(reading)
+        for limbs, Q in zip(pts, py):
+            word = g2_encode(codec, limbs)
+            assert word == g2_word_expected(Q)
+            got = g2_decode(codec, word)
+            assert got is not None and (got == limbs).all(), Q
+    # x = (w, 0) and (0, w) for the pool words themselves: decoded exactly when x^3 + b' is a square of Fq2 (its norm a square of Fq)
+    seen = set()
+    for w in gc.adversarial_fq_ints():
+        for x in ((w, 0), (0, w)):
+            if x == (0, 0):
+                continue
+            rhs = pyref.f2_add(pyref.f2_mul(pyref.f2_mul(x, x), x), pyref.G2_B)
+            is_square = pow((rhs[0] * rhs[0] + rhs[1] * rhs[1]) % P, (P - 1) // 2, P) == 1
+            got = g2_decode(codec, x[0].to_bytes(32, "little") + x[1].to_bytes(32, "little"))
+            assert (got is not None) == is_square, x
+            seen.add(is_square)
+            if got is not None:
+                assert cref.g2_is_on_curve(got) and (got[:8] == np.array(pyref.mont_limbs(x[0], P) + pyref.mont_limbs(x[1], P), dtype=np.uint64)).all()
+    assert seen == {True, False}

@@ -124,3 +124,52 @@ def test_g2_bucket_msm_on_host(g2s, n, c):
         for b, k in zip(bases, ks):
             acc = pyref.g2_add(acc, to_py(cref.g2_mul(b, cref.fr_mont(k))))
         assert acc == want
+
+
+def test_g2_formulas_on_adversarial_twist_points(g2s):
+    """twist points whose x components are adversarial Montgomery words (tests/gpu_common.py::adversarial_g2_points: a component zero, on an edge of the
+    field or of a limb grid), outside the subgroup of order r: madd, add, dbl, normalise and the on-twist check against pyref"""
+    from tests import gpu_common as gc
+    limbs, pts, _ = gc.adversarial_g2_points()
+    m = len(pts)
+    rng = np.random.default_rng(84)
+    ref = rand_pts(rng, 3)
+    for i, Q in enumerate(pts):
+        assert g2s.g2s_on_curve(p_(limbs[i].copy())) == 1
+        off = limbs[i].copy(); off[4 * int(rng.integers(0, 4))] ^= np.uint64(1)
+        assert g2s.g2s_on_curve(p_(off)) == 0
+        Q2 = pts[(7 * i + 11) % m]
+        if Q2[0] == Q[0]:
+            Q2 = pts[(7 * i + 13) % m]
+        A = ref[i % 3]
+        assert X(g2s, Q).point() == Q                                    # first point, normalised back
+        a = X(g2s, A).madd(Q)                                            # onto a random accumulator
+        assert a.point() == pyref.g2_add(A, Q)
+        b = X(g2s, Q).madd(Q2)                                           # two pool points
+        assert b.point() == pyref.g2_add(Q, Q2)
+        assert X(g2s, Q).madd(Q).point() == pyref.g2_add(Q, Q)           # madd doubling branch
+        assert X(g2s, Q).madd(neg(Q)).point() is None                    # madd inverse branch
+        assert X(g2s, Q).dbl().point() == pyref.g2_add(Q, Q)
+        if i % 4 == 0:                                                   # full additions and a doubling of projective points
+            s = pyref.g2_add(pyref.g2_add(A, Q), pyref.g2_add(Q, Q2))
+            assert a.add(b).point() == s and a.dbl().point() == pyref.g2_add(s, s)
+            assert X(g2s, Q).madd(Q2).add(X(g2s, Q2).madd(Q)).point() == pyref.g2_mul(pyref.g2_add(Q, Q2), 2)
+            assert X(g2s, Q).madd(Q2).add(X(g2s, neg(Q2)).madd(neg(Q))).point() is None
+
+
+def test_g2_bucket_msm_on_adversarial_twist_points(g2s):
+    """the host-side bucket MSM over pool points: the scalars act as integers (the points are outside the subgroup of order r)"""
+    from tests import gpu_common as gc
+    limbs, pts, _ = gc.adversarial_g2_points()
+    rng = np.random.default_rng(85)
+    for lo, c in ((0, 4), (100, 5), (len(pts) - 24, 6)):
+        n = 24
+        ks = [int(rng.integers(0, 2**63)) ** 4 % R for _ in range(n)]
+        ks[0] = R - 1; ks[1] = pyref.FR_ZETA; ks[3] = ks[2]
+        can = np.array([pyref.to_limbs(k) for k in ks], dtype=np.uint64)
+        out = np.zeros(16, dtype=np.uint64)
+        g2s.g2s_bucket_msm(p_(out), p_(np.ascontiguousarray(limbs[lo:lo + n])), p_(can), C.c_uint64(n), C.c_uint32(c))
+        want = None
+        for Q, k in zip(pts[lo:lo + n], ks):
+            want = pyref.g2_add(want, pyref.g2_mul(Q, k))
+        assert to_py(out) == want

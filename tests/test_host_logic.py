@@ -236,3 +236,79 @@ def test_scan_oracle_agrees_with_integers_on_the_pool():
     for v in ints[1:]:
         want.append(acc); acc = acc * v * rinv % R
     assert gc.words_to_ints(z) == want and gc.words_to_ints(t)[0] == acc
+
+
+def test_adversarial_curve_point_pools():
+    """tests/gpu_common.py: every point of the adversarial G1 / G2 pools is on its curve, none is listed twice, none has the x word 0 (the device's
+    identity test reads x alone), every pool word lifted to a coordinate within LIFT_MAX = 8, and every y-triple (x, beta x, beta^2 x) sums to the identity.
+    Observed: 54 words; "mont": 189 G1 points (34 triples), x lifts within 3 (32 words at 0), y within 3 (12 at 0), 284 twist points within 4;
+    "canonical": 182 G1 points (34 triples), x within 3 (25 at 0), y within 4 (10 at 0), 288 twist points within 5."""
+    from tests import gpu_common as gc
+    P = pyref.P_MOD
+    ints = gc.adversarial_fq_ints()
+    assert len(set(ints)) == len(ints) >= 50 and all(0 <= v < P for v in ints)
+    mont = (1 << 256) % P
+    for v in [0, 1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, mont, P - mont, 2 * mont % P, gc.ALL_ONES_LIMBS, (1 << 252) - 1, 1 << 252, 1 << 253,
+              int("55" * 32, 16) % P, int("AA" * 32, 16) % P] + [(1 << (29 * i)) + d for i in range(1, 9) for d in (-1, 0, 1)] + [(1 << (32 * i)) - d for i in range(1, 8) for d in (1, 0)]:
+        assert v in ints, hex(v)
+    assert pow(gc.FQ_BETA, 3, P) == 1 and gc.FQ_BETA != 1 and gc.LIFT_MAX == 8
+    rinv = pow(1 << 256, -1, P)
+    for reading in ("mont", "canonical"):
+        pts, words, dist = gc.adversarial_g1_points(reading)
+        py, kind, triples = gc.adversarial_g1_info(reading)
+        m = pts.shape[0]
+        assert pts.shape == (m, 8) and pts.dtype == np.uint64 and words.shape == (m, 4) and dist.shape == (m,) and m >= 150
+        assert len({p.tobytes() for p in pts}) == m and len(set(py)) == m
+        assert int(np.abs(dist).max()) <= 8
+        assert pts[:, :4].any(axis=1).all(), "no point has the x word 0"
+        for i in range(m):
+            assert pyref.g1_is_on_curve(py[i]) and cref.g1_is_on_curve(pts[i])
+            assert pyref.g1_affine_from_limbs(pts[i, :4], pts[i, 4:]) == py[i]
+            coord = gc.words_to_ints(pts[i:i + 1, :4] if kind[i] == "x" else pts[i:i + 1, 4:])[0]      # the ABI word of the lifted coordinate
+            if reading == "canonical":
+                coord = coord * rinv % P
+            assert coord == gc.words_to_ints(words[i:i + 1])[0] + int(dist[i]), "the word the point was built for, at its distance"
+        for fam in "xy":                                                  # every pool word has a point of either family within reach (a point two words share is listed once)
+            have = [gc.words_to_ints(words[i:i + 1])[0] + int(dist[i]) for i in range(m) if kind[i] == fam]
+            assert all(min(abs(w - h) for h in have) <= 8 for w in ints), fam
+        assert len(triples) >= 30 and {i for t in triples for i in t} >= {i for i in range(m) if kind[i] == "y"}      # a member may have been listed as an x lift before
+        for t in triples:
+            a, b, c = (py[i] for i in t)
+            assert a[1] == b[1] == c[1] and len({a[0], b[0], c[0]}) == 3
+            assert pyref.g1_add(pyref.g1_add(a, b), c) is None
+            acc = np.zeros(12, dtype=np.uint64)
+            for i in t:
+                acc = cref.g1_add_affine(acc, pts[i])
+            assert not acc[8:].any(), "and the C oracle says so too"
+        for p, q in zip(gc.g1_neg_words(pts), py):
+            assert pyref.g1_affine_from_limbs(p[:4], p[4:]) == pyref.g1_neg(q)
+        non = gc.adversarial_fq_non_lifting(reading)
+        val = (lambda w: w * rinv % P) if reading == "mont" else (lambda w: w)
+        assert 0 in non and all(gc.fq_sqrt((val(w) ** 3 + 3) % P) is None or val(w) == 0 for w in non) and len(non) >= 10
+        g2, g2py, g2d = gc.adversarial_g2_points(reading)
+        assert g2.shape == (len(g2py), 16) and len(set(g2py)) == len(g2py) >= 250 and int(np.abs(g2d).max()) <= 8
+        for q, w in zip(g2py, g2):
+            assert pyref.g2_is_on_curve(q) and cref.g2_is_on_curve(w) and list(w) == pyref.g2_to_limbs(q)
+        assert any(q[0][1] == 0 for q in g2py) and any(q[0][0] < 8 and q[0][1] for q in g2py) if reading == "canonical" else True
+    assert not cref.g2_in_subgroup(gc.adversarial_g2_points()[0][0]), "twist points outside the subgroup of order r"
+
+
+def test_oracles_agree_on_the_adversarial_points():
+    """what the GPU tests lean on: the C oracle against Python integers ON these points -- an MSM over the G1 pool, and cref.g2_mul on twist points
+    outside the order-r subgroup (the scalar acts as an integer there)"""
+    from tests import gpu_common as gc
+    P, R = pyref.P_MOD, pyref.R_MOD
+    pts, _, _ = gc.adversarial_g1_points("mont")
+    py, _, _ = gc.adversarial_g1_info("mont")
+    sc = gc.full_range("msm", pts.shape[0])
+    can = gc.words_to_ints(cref.f_to_canonical_vec(cref.FR, sc))
+    for lo in (0, pts.shape[0] - 48):
+        want = pyref.msm(can[lo:lo + 48], py[lo:lo + 48])
+        got = cref.g1_to_affine(cref.best_multiexp(sc[lo:lo + 48], pts[lo:lo + 48]))
+        assert pyref.g1_affine_from_limbs(got[:4], got[4:]) == want
+    g2, g2py, _ = gc.adversarial_g2_points()
+    rinv = pow(1 << 256, -1, P)
+    for i in range(0, len(g2py), 9):
+        k = (R - 1, pyref.FR_ZETA, can[i % len(can)])[i % 3]
+        got = cref.g2_mul(g2[i], cref.fr_mont(k))
+        assert list(got) == pyref.g2_to_limbs(pyref.g2_mul(g2py[i], k)), i

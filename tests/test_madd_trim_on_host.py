@@ -209,3 +209,113 @@ def test_column_sum_bounds_of_the_lazy_operand():
     assert worst(rd, t, y1, ppp) < 1 << 63
     pd = [(1 << 30) + 7] * 8 + [top(160)]
     assert worst(pd, pd) < 1 << 64 and worst(pd, [M29] * 9) < 1 << 64
+
+
+# ---- addends whose coordinate WORDS are adversarial (tests/gpu_common.py::adversarial_g1_points): the edges of the field and of the 29-bit / 32-bit limb
+# grids as the Montgomery word of x or of y, where from_sat, fq29_neg_loaded and the first-point path reduce_small + normalise + sub4 can be wrong without
+# a random point noticing.  The pool above (4096 random points) supplies the accumulators.
+@pytest.fixture(scope="module")
+def adv():
+    from tests import gpu_common as gc
+    pts, _, _ = gc.adversarial_g1_points("mont")
+    _, _, triples = gc.adversarial_g1_info("mont")
+    return pts, triples
+
+
+def test_adversarial_addends_in_every_position(mt, pool, adv):
+    """each pool point, with both signs, as the first point of a bucket followed by two random points, and as the second and the third point onto
+    random accumulators"""
+    pts, _ = adv
+    rng = random.Random(51)
+    seqs = []
+    for q in pts:
+        for s in (0, 1):
+            a, b = rng.sample(range(len(pool)), 2)
+            ra, rb = (pool[a], rng.randrange(2)), (pool[b], rng.randrange(2))
+            seqs += [[(q, s), ra, rb], [ra, (q, s), rb], [ra, rb, (q, s)], [(q, s)]]
+    got, want = sums(mt, seqs)
+    assert (got == want).all(), np.nonzero((got != want).any(axis=1))[0][:8]
+
+
+def test_adversarial_addends_doubled_and_annihilated(mt, pool, adv):
+    pts, _ = adv
+    rng = random.Random(52)
+    seqs, zero = [], []
+    for q in pts:
+        for s in (0, 1):
+            r = (pool[rng.randrange(len(pool))], rng.randrange(2))
+            zero.append(len(seqs) + 1)
+            seqs += [[(q, s), (q, s)], [(q, s), (q, 1 - s)], [(q, s), (q, 1 - s), r], [(q, s), (q, s), r], [r, (q, s), (q, s)], [(q, s)] * 5]
+    got, want = sums(mt, seqs)
+    assert (got == want).all(), np.nonzero((got != want).any(axis=1))[0][:8]
+    assert not got[zero].any()
+
+
+def test_adversarial_y_triples_in_one_bucket(mt, adv):
+    """(x, y), (beta x, y), (beta^2 x, y) are P, lambda P, lambda^2 P: equal y words and different x, so no doubling test may take one for another.  All
+    three under one sign give the identity; two of the three give minus the third."""
+    pts, triples = adv
+    seqs, zero, minus = [], [], []
+    for t in triples:
+        for s in (0, 1):
+            for order in ((0, 1, 2), (2, 0, 1), (1, 2, 0)):
+                i, j, k = (t[o] for o in order)
+                zero.append(len(seqs)); seqs.append([(pts[i], s), (pts[j], s), (pts[k], s)])
+                minus.append((len(seqs), k, 1 - s)); seqs.append([(pts[i], s), (pts[j], s)])
+                minus.append((len(seqs), k, 1 - s)); seqs.append([(pts[j], s), (pts[i], s)])
+    got, want = sums(mt, seqs)
+    assert (got == want).all(), np.nonzero((got != want).any(axis=1))[0][:8]
+    assert not got[zero].any()
+    for at, k, s in minus:
+        assert (got[at] == (neg(pts[k]) if s else pts[k])).all(), at
+
+
+def test_adversarial_addends_pairwise(mt, pool, adv):
+    """400 ordered pairs of pool points (seeded sample) meeting in one bucket: alone, and on a random accumulator"""
+    pts, _ = adv
+    rng = random.Random(53)
+    seqs = []
+    for _ in range(400):
+        i, j = rng.sample(range(len(pts)), 2)
+        si, sj = rng.randrange(2), rng.randrange(2)
+        r = (pool[rng.randrange(len(pool))], rng.randrange(2))
+        seqs += [[(pts[i], si), (pts[j], sj)], [r, (pts[i], si), (pts[j], sj)]]
+    got, want = sums(mt, seqs)
+    assert (got == want).all(), np.nonzero((got != want).any(axis=1))[0][:8]
+
+
+def test_adversarial_y_words_as_not_normalised_representatives(mt, pool, adv):
+    """madd_core with normalise_y = 1 on the pool's y words: 64 p - y limb by limb (what a negative digit loads: the fat 64 p is rebuilt here from p
+    alone), and the residue raised by p's limbs.  The word whose eight low limbs are all 0x1FFFFFFF is the one this exists for: it is the extreme of
+    the column-sum argument for limbs < 2^29."""
+    from tests import gpu_common as gc
+    pts, _ = adv
+    ys = gc.words_to_ints(pts[:, 4:])
+    assert any(all((y >> (29 * i)) & M29 == M29 for i in range(8)) or all(((y + d) >> (29 * i)) & M29 == M29 for i in range(8)) for y in ys for d in range(-8, 9)), \
+        "a y word at (or within the lift distance of) all-ones low limbs is in the pool"
+    pl = _limbs(P)
+    fat64 = _limbs(64 * P)
+    for i in range(8):                                    # 2^29 lent to every limb below the top: limbs >= 2^29 - 1 wherever the limb above can lend
+        fat64[i] += 1 << 29; fat64[i + 1] -= 1
+    assert _val(fat64) == 64 * P and min(fat64[:8]) >= M29 and fat64[8] >= 1 << 27
+    rng = random.Random(54)
+    for n, q in enumerate(pts):
+        x2 = np.zeros(9, dtype=np.uint32); y2 = np.zeros(9, dtype=np.uint32)
+        mt.mt_from_sat(p_(x2), p_(q[:4].copy())); mt.mt_from_sat(p_(y2), p_(q[4:].copy()))
+        assert max(y2[:8]) <= M29 and _val(y2) < 1 << 259
+        yres = _val(y2) % P
+        a = pool[rng.randrange(len(pool))]
+        plus, minus = cref.g1_to_affine(oracle_sum([a, q], [0, 0])), cref.g1_to_affine(oracle_sum([a, q], [0, 1]))
+        reps = [([int(c) - int(v) for c, v in zip(fat64, y2)], minus), ([u + v for u, v in zip(_limbs(yres), pl)], plus),
+                ([u + v for u, v in zip(_limbs(P - yres), pl)], minus)]
+        for first in (False, True):
+            for limbs, want in reps:
+                assert 0 <= min(limbs) and max(limbs) < 1 << 30
+                acc = np.zeros(36, dtype=np.uint32)
+                if not first:
+                    assert mt.mt_madd_raw(p_(acc), p_(a), 0) == 0
+                assert mt.mt_madd_core_raw(p_(acc), p_(x2), p_(np.array(limbs, dtype=np.uint32)), 1) == 0
+                out = np.zeros(8, dtype=np.uint64); mt.mt_finish(p_(out), p_(acc))
+                if first:
+                    want = q if want is plus else neg(q)
+                assert (out == want).all(), (n, first, limbs)
