@@ -1,5 +1,5 @@
 # Plain-make entry points for a maintainer who integrates libmi355zk.so without the Python tooling.
-#   make lib        libmi355zk.so for gfx950: four translation units (csrc/lib_*.hip), `make -j4 lib` builds them in parallel (~1 min)
+#   make lib        libmi355zk.so for gfx950: five translation units (csrc/lib_*.hip), `make -j5 lib` builds them in parallel (~1 min)
 #   make oracle     the CPU oracle (test infrastructure only)
 #   make test-cpu   the GPU-less test suite          make test-gpu   the -m gpu suite (needs an MI355X)
 #   make bench      the headline measurement (one JSON line)
@@ -10,7 +10,7 @@ DEPS := $(wildcard $(CSRC)/*.hpp $(CSRC)/*.hpp $(CSRC)/*.inc) include/mi355zk.h
 
 .PHONY: lib oracle test-cpu test-gpu bench clean
 OBJDIR := scroll-prover_amd/build
-UNITS := lib_core lib_msm lib_ntt lib_aux
+UNITS := lib_core lib_msm lib_ntt lib_aux lib_pairing
 OBJS := $(UNITS:%=$(OBJDIR)/%.o)
 lib: $(LIB)
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(DEPS)

@@ -347,6 +347,23 @@ int mi355_msm_g2_adhoc_host(const void *bases_g2affine_host, const void *scalars
 int mi355_msm_g2_dev(const void *bases_g2affine_dev, const void *scalars_dev, uint64_t n, void *out_g2affine_host);
 int mi355_msm_g2_batch_dev(const void *bases_g2affine_dev, const void *const *scalars_dev, uint32_t batch, uint64_t n, void *out_g2affine_host);
 
+/* ---- the optimal ate pairing of BN254 on the device: products of pairings, one per group of consecutive pairs
+ *      out[g] = prod_{j < pairs_per_group} e(P[g * ppg + j], Q[g * ppg + j])   for g < groups
+ * P: 64-byte G1Affine, Q: 128-byte G2Affine (Montgomery limbs, identity = all zero; a pair with an identity contributes 1).
+ * gt_out (optional): groups x 384 B, halo2curves' Fq12 memory layout c0.c0.c0 | c0.c0.c1 | c0.c1.c0 | ... | c1.c2.c1 (Fq12 = c0 + c1 w,
+ * Fq6 = c0 + c1 v + c2 v^2, Fq2 = c0 + c1 u; 32-byte Montgomery words).  is_one_out (optional): groups x u32, 1 where the product is 1 --
+ * what the EVM precompile at address 8 answers for that group.
+ * Every P is checked to be on the curve and every Q on the twist in a device pass: MI355_EBADARG, and mi355_last_error() names the first
+ * bad pair, when one is not; nothing else is launched then.  Q is NOT checked for membership of the subgroup of order r: that stays the
+ * caller's responsibility, as for the bases of mi355_msm_g2_*.  For a Q outside the subgroup the result is unspecified (the call returns).
+ * The device is looked up first, as in every entry point: without a bound device every call, groups == 0 included, is MI355_ENODEVICE.  With one,
+ * groups == 0 is a no-op; pairs_per_group == 0, both outputs NULL, or more than 2^20 pairs in one call are MI355_EBADARG.  One Miller loop
+ * per pair (one lane each), a tree of pairwise products inside each group, one final exponentiation per group; the workspace (two
+ * 384-byte values per pair) is one pooled mi355_buf block, back in the pool on return.  Same device choice, lock and stream order as
+ * mi355_g2_mul_host; synchronous; no CPU fallback (MI355_ENODEVICE).  The kernels report under pairing_* in mi355_profile_get.            */
+int mi355_pairing_products_host(const void *p_g1affine_host, const void *q_g2affine_host, uint32_t groups, uint32_t pairs_per_group,
+                                void *gt_out_host, uint32_t *is_one_out_host);
+
 /* ---- best_fft::<Fr, G1> -- the same DFT over G1 points, a'[i] = sum_j omega^(ij) a[j] -- and its one caller, g_to_lagrange, which
  * ParamsKZG::downsize(k) [REF integration/tests/integration.rs:17-22] and ParamsKZG::setup run to rebuild g_lagrange from
  * g[..2^k]: g_lagrange = n^-1 * DFT_{omega^-1}(g) [EXT-recalled halo2_proofs src/arithmetic.rs g_to_lagrange].

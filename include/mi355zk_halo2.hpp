@@ -357,6 +357,17 @@ class ParamsKZG {
   // the bases as ParamsKZG::write serialises them (first n points)
   std::vector<G1Affine> get_g() const { std::vector<G1Affine> v(n); check(mi355_srs_read_host(g_, 0, n, v.data())); return v; }
   std::vector<G1Affine> get_g_lagrange() const { std::vector<G1Affine> v(n); check(mi355_srs_read_host(gl_, 0, n, v.data())); return v; }
+  // e(g[0], s_g2) e(-g[1], g2) == 1: s_g2 is [tau] g2 for the tau of the G1 basis, with G2 ordered and signed as the pairing reads it.  One pairing call
+  // (mi355_pairing_products_host) over two points read back from the device; nothing calls it by default.
+  bool check_g2() const {
+    if (n < 2) throw std::invalid_argument("check_g2 needs g[0] and g[1]");
+    G1Affine p[2]; check(mi355_srs_read_host(g_, 0, 2, p));
+    zk::fe_t y; std::memcpy(&y, &p[1][4], 32); y = zk::Fq::neg(y); std::memcpy(&p[1][4], &y, 32);   // neg(0) = 0 keeps the identity
+    uint8_t q[256]; std::memcpy(q, s_g2.data(), 128); std::memcpy(q + 128, g2.data(), 128);
+    uint32_t one = 0;
+    check(mi355_pairing_products_host(p, q, 1, 2, nullptr, &one));
+    return one == 1;
+  }
 
   // the per-column loop of create_proof (advice / lookup / permutation commitments of one phase) as one call: equal-length polynomials,
   // results in input order, identical to calling commit / commit_lagrange on each

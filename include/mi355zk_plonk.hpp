@@ -33,6 +33,7 @@
 
 #include "mi355zk_plonk_circuit.hpp"
 #include "mi355zk_transcript.hpp"
+#include "mi355zk_plonk_verify.hpp"   // plonk::verify_proof
 
 namespace mi355zk {
 namespace plonk {

@@ -175,6 +175,9 @@ struct Protocol {
   // the scalar a verifier of THIS protocol file absorbs first (snark-verifier's PlonkProtocol::transcript_initial_state = halo2's hash of the verifying key): the
   // reference's protocol files carry it [REF release-v0.13.1/chunk.protocol "transcript_initial_state"]; generated protocols do not (see vk_transcript_scalar)
   bool has_initial_state = false; Fr initial_state{};
+  // what a verifier built from the file alone needs besides: the preprocessed commitments (Montgomery limbs, as the reference's files carry them) and whether the first
+  // twelve instance values are a carried KZG accumulator (`accumulator_indices`: two G1 points, three 88-bit limbs per coordinate).  Generated protocols have neither.
+  std::vector<halo2::G1Affine> preprocessed; bool has_accumulator = false;
   Protocol() = default;
   Protocol(const Protocol &) = delete;               // `perm` / `lookups` / `gates` point into `numerator`
   Protocol &operator=(const Protocol &) = delete;
@@ -212,6 +215,8 @@ struct Protocol {
     if (const json::Value *ly = root.find("layer")) layer = (int)ly->i64();
     if (const json::Value *sc = root.find("source")) source = sc->s;
     if (const json::Value *is = root.find("transcript_initial_state")) if (is->type == json::Value::ARR) { initial_state = fr_from_json(*is); has_initial_state = true; }   // JSON null (Option::None) = absent
+    if (const json::Value *pp = root.find("preprocessed")) for (const auto &v : pp->arr) { const Fr x = fr_from_json(v.at("x")), y = fr_from_json(v.at("y")); preprocessed.push_back({{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]}}); }
+    if (const json::Value *ai = root.find("accumulator_indices")) has_accumulator = ai->type == json::Value::ARR && !ai->arr.empty();
     recognise();
   }
 

@@ -1,0 +1,243 @@
+// mi355zk_plonk_verify.hpp -- plonk::verify_proof: the verifier of a SHPLONK halo2 proof for any snark-verifier PlonkProtocol, a port of oracle/plonk.py verify()
+// [EXT-recalled snark-verifier verifier/plonk.rs, pcs/kzg/multiopen/bdfg21.rs].  Included from mi355zk_plonk.hpp.
+//   key         the .vkey bytes | the protocol file's own `preprocessed` and `transcript_initial_state` (the route of the released proofs) | an explicit list and state
+//   transcript  the read side of mi355zk_transcript.hpp; a non-canonical scalar, a word that is no curve point, leftover or missing bytes are NAMED failures
+//   points      the compressed layouts: ONE mi355_g1_decompress_host call over every point word of the proof (positions follow from the protocol) and of the .vkey;
+//               the Evm layout: uncompressed, checked on the curve by the transcript
+//   scalars     instance evaluations by Lagrange, the numerator tree at x, h(x) = numerator / (x^n - 1)
+//   SHPLONK     rotation sets by first appearance in `queries`, the i-th set at v^i, its j-th polynomial at y^j; everything collapses to ONE (scalars, points) list, summed by
+//               mi355_msm_g1_adhoc_host
+//   pairing     ONE mi355_pairing_products_host call: group 0 = e(lhs, g2) e(W', -s_g2); group 1 = the carried accumulator when the protocol has one
+// Failures of the INPUT (proof, key, instances, protocol) are statuses in VerifyResult::error; only a failing device call throws (halo2::Error, as everywhere in these headers).
+// VerifyOptions::host_only stops after the list is built (points decompressed on the host): the verifier's own logic runs without a device.
+#pragma once
+#include "mi355zk_plonk_protocol.hpp"
+#include "mi355zk_transcript.hpp"
+
+namespace mi355zk {
+namespace plonk {
+
+struct G2Pair {   // the two G2 points of the final check, as the pairing takes them: g2 and -[s]g2 (128-byte G2Affine)
+  std::array<uint8_t, 128> g2{}, neg_s_g2{};
+  static std::array<uint8_t, 128> negate(const std::array<uint8_t, 128> &q) {
+    std::array<uint8_t, 128> r = q; zk::fe_t y[2]; std::memcpy(y, q.data() + 64, 64);
+    for (auto &c : y) c = zk::Fq::neg(c);   // neg(0) = 0 keeps the identity
+    std::memcpy(r.data() + 64, y, 64); return r;
+  }
+  static G2Pair from_params(const std::array<uint8_t, 128> &g2, const std::array<uint8_t, 128> &s_g2) { G2Pair p; p.g2 = g2; p.neg_s_g2 = negate(s_g2); return p; }   // ParamsKZG's g2 / s_g2
+  static G2Pair from_negated(const std::array<uint8_t, 128> &g2, const std::array<uint8_t, 128> &neg_s_g2) { G2Pair p; p.g2 = g2; p.neg_s_g2 = neg_s_g2; return p; }
+};
+struct VerifyingKeyRef {   // vk_bytes when not empty; else `preprocessed` when not empty; else the protocol file's own.  initial_state overrides the transcript's first scalar
+  std::vector<uint8_t> vk_bytes; std::vector<halo2::G1Affine> preprocessed; bool has_initial_state = false; Fr initial_state{};
+};
+struct VerifyOptions { TranscriptKind transcript = TranscriptKind::ByLayer; bool check_accumulator = true; int accumulator = -1 /* -1: as the protocol says; 0 / 1: no / yes */; bool host_only = false; };
+struct VerifyResult {
+  bool ok = false; std::string error;                       // the name of the first failed check ("" when none); `detail` says more
+  std::string detail;
+  Fr theta{}, beta{}, gamma{}, y{}, x{}, shplonk_y{}, shplonk_v{}, shplonk_u{};
+  Fr numerator_at_x{};
+  std::vector<Fr> msm_scalars; std::vector<halo2::G1Affine> msm_points; halo2::G1Affine msm_result{}, w_prime{};
+  bool has_accumulator = false; halo2::G1Affine acc_lhs{}, acc_rhs{};
+  std::vector<uint32_t> pairing;                            // per group: 1 where the product is 1
+};
+
+namespace vdetail {
+inline bool fq_on_curve(const halo2::G1Affine &a) {
+  zk::fe_t x, y; std::memcpy(&x, a.data(), 32); std::memcpy(&y, a.data() + 4, 32);
+  zk::fe_t three = zk::Fq::zero(); three.l[0] = 3; three = zk::Fq::from_canonical(three);
+  return zk::Fq::eq(zk::Fq::sqr(y), zk::Fq::add(zk::Fq::mul(zk::Fq::sqr(x), x), three));
+}
+inline Fr eval_expr(const Expr &e, const std::map<PolyRot, Fr> &evals, const Fr *ch, const Fr &x, const std::map<int32_t, Fr> &lag) {
+  auto ev = [&](const Expr &k) { return eval_expr(k, evals, ch, x, lag); };
+  switch (e.kind) {
+    case Expr::CONSTANT: return e.c;
+    case Expr::IDENTITY: return x;
+    case Expr::LAGRANGE: return lag.at(e.i);
+    case Expr::POLY: { auto it = evals.find({(uint32_t)e.i, e.rot}); if (it == evals.end()) throw std::invalid_argument("verify: the numerator names an evaluation the proof does not carry"); return it->second; }
+    case Expr::CHALLENGE: return ch[e.i];
+    case Expr::NEG: return fr_neg(ev(e.kids[0]));
+    case Expr::SUM: return fr_add(ev(e.kids[0]), ev(e.kids[1]));
+    case Expr::PROD: return fr_mul(ev(e.kids[0]), ev(e.kids[1]));
+    case Expr::SCALED: return fr_mul(ev(e.kids[0]), e.c);
+    case Expr::DPOW: { const Fr b = ev(e.kids.back()); Fr acc = ev(e.kids[0]); for (size_t i = 1; i + 1 < e.kids.size(); i++) acc = fr_add(fr_mul(acc, b), ev(e.kids[i])); return acc; }   // Horner, the first expression at the highest power
+  }
+  throw std::invalid_argument("verify: unknown expression node");
+}
+inline Fr pow_rot(const Protocol &P, int32_t r) { return r >= 0 ? fr_pow(P.omega, (uint64_t)r) : fr_pow(P.omega_inv, (uint64_t)(-(int64_t)r)); }
+}  // namespace vdetail
+
+inline VerifyResult verify_proof(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const G2Pair &srs, const VerifyOptions &opt) {
+  using halo2::G1Affine;
+  VerifyResult res;
+  auto failed = [&](const char *name, const std::string &why) { res.ok = false; res.error = name; res.detail = why; return res; };
+  const TranscriptKind kind = opt.transcript == TranscriptKind::ByLayer ? (P.layer == 6 ? TranscriptKind::Evm : TranscriptKind::Poseidon) : opt.transcript;
+  Transcript T(kind);
+  const size_t nb = T.point_bytes();
+  uint32_t nw = 0; for (auto w : P.num_witness) nw += w;
+  const size_t n_com = nw + P.Q, n_ev = P.evaluations.size(), expect = (n_com + 2) * nb + n_ev * 32;
+  if (proof.size() != expect) return failed("proof_length", "proof has " + std::to_string(proof.size()) + " bytes, the protocol reads " + std::to_string(expect));
+
+  // ---- every compressed point word of the proof (and of the .vkey) through one decompression
+  const bool use_vk = !vk.vk_bytes.empty();
+  if (use_vk && vk.vk_bytes.size() != 8 + 32 * (size_t)P.num_pre) return failed("vk_length", "the .vkey has " + std::to_string(vk.vk_bytes.size()) + " bytes, the protocol has " + std::to_string(P.num_pre) + " preprocessed polynomials");
+  std::vector<halo2::G1Bytes> words;
+  if (kind != TranscriptKind::Evm) {
+    words.resize(n_com + 2);
+    for (size_t i = 0; i < n_com; i++) std::memcpy(words[i].data(), proof.data() + 32 * i, 32);
+    for (size_t i = 0; i < 2; i++) std::memcpy(words[n_com + i].data(), proof.data() + 32 * (n_com + n_ev) + (i ? 32 : 0), 32);
+  }
+  const size_t vk0 = words.size();
+  if (use_vk) { words.resize(vk0 + P.num_pre); for (uint32_t i = 0; i < P.num_pre; i++) std::memcpy(words[vk0 + i].data(), vk.vk_bytes.data() + 8 + 32 * i, 32); }
+  std::vector<G1Affine> decoded(words.size());
+  if (!words.empty()) {
+    if (opt.host_only) { for (size_t i = 0; i < words.size(); i++) if (!halo2::g1_from_bytes(words[i], decoded[i])) decoded[i].fill(0); }
+    else {
+      uint64_t bad = ~0ull; const int rc = mi355_g1_decompress_host(words.data(), decoded.data(), words.size(), &bad);
+      if (rc == MI355_EBADARG && bad != ~0ull) {   // a rejected word: name it below, where the transcript reaches it; the words behind it are decoded on the host
+        for (size_t i = 0; i < words.size(); i++) if (!halo2::g1_from_bytes(words[i], decoded[i])) decoded[i].fill(0);
+      } else halo2::check(rc);
+    }
+  }
+  std::vector<G1Affine> pre;
+  if (use_vk) { for (uint32_t i = 0; i < P.num_pre; i++) { pre.push_back(decoded[vk0 + i]); bool z = true; for (auto w : pre.back()) z = z && w == 0; if (z) return failed("invalid_point", ".vkey commitment " + std::to_string(i) + " is no curve point"); } }
+  else pre = vk.preprocessed.empty() ? P.preprocessed : vk.preprocessed;
+  if (pre.size() != P.num_pre) return failed("preprocessed", std::to_string(pre.size()) + " preprocessed commitments given, the protocol has " + std::to_string(P.num_pre));
+  for (size_t i = 0; i < pre.size(); i++) if (!vdetail::fq_on_curve(pre[i])) return failed("invalid_point", "preprocessed commitment " + std::to_string(i) + " is not on the curve");
+
+  // ---- transcript: key scalar, instances, commitments by phase with their challenges, quotient pieces, x, evaluations, y, v, H, u, W'
+  if (vk.has_initial_state) T.common_scalar(vk.initial_state);
+  else if (P.has_initial_state) T.common_scalar(P.initial_state);
+  else if (use_vk) T.common_scalar(vk_transcript_repr(vk.vk_bytes));
+  else return failed("initial_state", "no transcript initial state: give the .vkey, a protocol file that carries one, or an explicit value");
+  for (const Fr &v : instances) T.common_scalar(v);
+  size_t pos = 0, word = 0;
+  std::map<uint32_t, G1Affine> com; for (uint32_t i = 0; i < P.num_pre; i++) com[i] = pre[i];
+  auto read_point = [&](G1Affine &out, std::string &err) {
+    const Transcript::Read st = T.read_point(proof, pos, kind == TranscriptKind::Evm ? nullptr : &decoded[word], out);
+    if (st != Transcript::Read::Ok) err = "point " + std::to_string(word) + " of the proof (byte " + std::to_string(pos - nb) + ") is no curve point";
+    word++;
+    return st == Transcript::Read::Ok;
+  };
+  std::string err; Fr ch[4]; uint32_t idx = P.wit0, nch = 0;
+  for (size_t ph = 0; ph < P.num_witness.size(); ph++) {
+    for (uint32_t j = 0; j < P.num_witness[ph]; j++) if (!read_point(com[idx++], err)) return failed("invalid_point", err);
+    for (uint32_t j = 0; j < P.num_challenge[ph]; j++) ch[nch++] = T.squeeze_challenge();
+  }
+  std::vector<G1Affine> pieces(P.Q);
+  for (auto &pc : pieces) if (!read_point(pc, err)) return failed("invalid_point", err);
+  const Fr x = T.squeeze_challenge();
+  std::map<PolyRot, Fr> evals;
+  for (size_t i = 0; i < n_ev; i++) {
+    Fr v; const Transcript::Read st = T.read_scalar(proof, pos, v);
+    if (st == Transcript::Read::NonCanonical) return failed("non_canonical_scalar", "evaluation " + std::to_string(i) + " of the proof is not below r");
+    if (st != Transcript::Read::Ok) return failed("proof_length", "the proof ends inside evaluation " + std::to_string(i));
+    evals[P.evaluations[i]] = v;
+  }
+  const Fr ys = T.squeeze_challenge(), v = T.squeeze_challenge();
+  G1Affine c_h, c_w;
+  if (!read_point(c_h, err)) return failed("invalid_point", err);
+  const Fr uu = T.squeeze_challenge();
+  if (!read_point(c_w, err)) return failed("invalid_point", err);
+  if (pos != proof.size()) return failed("proof_length", "proof has " + std::to_string(proof.size()) + " bytes, the protocol reads " + std::to_string(pos));
+  res.theta = ch[0]; res.beta = ch[1]; res.gamma = ch[2]; res.y = ch[3]; res.x = x; res.shplonk_y = ys; res.shplonk_v = v; res.shplonk_u = uu; res.w_prime = c_w;
+
+  // ---- scalar side
+  const Fr one = fr_one();
+  Fr xn = x; for (uint32_t i = 0; i < P.k; i++) xn = fr_mul(xn, xn);
+  const Fr xn_minus_1 = fr_sub(xn, one);
+  if (fr_is_zero(xn_minus_1)) return failed("x_in_domain", "the evaluation point lies in the domain");
+  std::map<int32_t, Fr> lag;
+  auto lagrange_at = [&](int32_t i) {   // omega^i (x^n - 1) / (n (x - omega^i))
+    auto it = lag.find(i); if (it != lag.end()) return it->second;
+    const Fr wi = vdetail::pow_rot(P, i);
+    const Fr val = fr_mul(fr_mul(fr_mul(wi, xn_minus_1), P.n_inv), fr_inv(fr_sub(x, wi)));
+    lag[i] = val; return val;
+  };
+  { std::vector<int32_t> need; collect_lagrange(P.numerator, need); for (int32_t i : need) lagrange_at(i); }
+  { Fr acc = fr_zero(); for (size_t i = 0; i < instances.size(); i++) acc = fr_add(acc, fr_mul(instances[i], lagrange_at((int32_t)i))); for (size_t j = 0; j < P.num_instance.size(); j++) evals[{P.inst0 + (uint32_t)j, 0}] = acc; }
+  { std::vector<std::pair<int32_t, int32_t>> named; collect_polys(P.numerator, named);   // an inconsistent protocol is a named failure here as in the SHPLONK part, never an exception
+    for (const auto &pr : named) if (!evals.count({(uint32_t)pr.first, pr.second})) return failed("protocol", "the numerator names polynomial " + std::to_string(pr.first) + " at rotation " + std::to_string(pr.second) + ", which the proof carries no evaluation for"); }
+  const Fr numer = vdetail::eval_expr(P.numerator, evals, ch, x, lag);
+  res.numerator_at_x = numer;
+  evals[{P.quotient_poly, 0}] = fr_mul(numer, fr_inv(xn_minus_1));
+
+  // ---- SHPLONK: the (scalars, points) list
+  auto rot_pt = [&](int32_t r) { return fr_mul(x, vdetail::pow_rot(P, r)); };
+  const std::vector<RotationSet> sets = rotation_sets(P.queries);
+  std::vector<Fr> super_pts;
+  for (const auto &s : sets) for (int32_t r : s.rots) { const Fr pt = rot_pt(r); if (std::find(super_pts.begin(), super_pts.end(), pt) == super_pts.end()) super_pts.push_back(pt); }
+  Fr zt = one; for (const Fr &pt : super_pts) zt = fr_mul(zt, fr_sub(uu, pt));
+  std::vector<uint32_t> term_order; std::map<uint32_t, Fr> terms;
+  Fr r_acc = fr_zero(), zd0 = fr_zero(), vp = one; bool first = true;
+  for (const auto &s : sets) {
+    std::vector<Fr> points; for (int32_t r : s.rots) points.push_back(rot_pt(r));
+    Fr zd = one; for (const Fr &pt : super_pts) if (std::find(points.begin(), points.end(), pt) == points.end()) zd = fr_mul(zd, fr_sub(uu, pt));
+    if (first) { zd0 = zd; first = false; }
+    std::vector<Fr> basis(points.size());   // the Lagrange basis of the set's points at u: r_ij(u) = sum_k eval_k basis_k
+    for (size_t a = 0; a < points.size(); a++) { Fr num = one, den = one; for (size_t b = 0; b < points.size(); b++) if (b != a) { num = fr_mul(num, fr_sub(uu, points[b])); den = fr_mul(den, fr_sub(points[a], points[b])); } basis[a] = fr_mul(num, fr_inv(den)); }
+    const Fr w = fr_mul(vp, zd);
+    Fr inner_r = fr_zero(), yp = one;
+    for (uint32_t p : s.polys) {
+      Fr r_u = fr_zero();
+      for (size_t a = 0; a < points.size(); a++) { auto it = evals.find({p, s.rots[a]}); if (it == evals.end()) return failed("protocol", "polynomial " + std::to_string(p) + " is queried at a rotation the proof carries no evaluation for"); r_u = fr_add(r_u, fr_mul(it->second, basis[a])); }
+      inner_r = fr_add(inner_r, fr_mul(yp, r_u));
+      if (!terms.count(p)) { terms[p] = fr_zero(); term_order.push_back(p); }
+      terms[p] = fr_add(terms[p], fr_mul(w, yp));
+      yp = fr_mul(yp, ys);
+    }
+    r_acc = fr_add(r_acc, fr_mul(w, inner_r));
+    vp = fr_mul(vp, v);
+  }
+  if (fr_is_zero(zd0)) return failed("shplonk_degenerate", "u coincides with an opening point");
+  const Fr zi = fr_inv(zd0);
+  for (uint32_t p : term_order) {
+    const Fr c = fr_mul(terms[p], zi);
+    if (p == P.quotient_poly) { Fr f = one; for (const auto &pc : pieces) { res.msm_scalars.push_back(fr_mul(c, f)); res.msm_points.push_back(pc); f = fr_mul(f, xn); } }
+    else { auto it = com.find(p); if (it == com.end()) return failed("protocol", "no commitment for queried polynomial " + std::to_string(p)); res.msm_scalars.push_back(c); res.msm_points.push_back(it->second); }
+  }
+  G1Affine gen{}; { zk::fe_t c = zk::Fq::zero(); c.l[0] = 1; const zk::fe_t gx = zk::Fq::from_canonical(c); c.l[0] = 2; const zk::fe_t gy = zk::Fq::from_canonical(c); std::memcpy(gen.data(), &gx, 32); std::memcpy(gen.data() + 4, &gy, 32); }
+  res.msm_scalars.push_back(fr_neg(fr_mul(r_acc, zi))); res.msm_points.push_back(gen);
+  res.msm_scalars.push_back(fr_neg(fr_mul(zt, zi))); res.msm_points.push_back(c_h);
+  res.msm_scalars.push_back(uu); res.msm_points.push_back(c_w);
+
+  // ---- the carried accumulator: limbs of 88 bits, three per coordinate, (lhs.x, lhs.y, rhs.x, rhs.y) in the first twelve instances
+  res.has_accumulator = opt.check_accumulator && (opt.accumulator < 0 ? P.has_accumulator : opt.accumulator != 0);
+  if (res.has_accumulator) {
+    if (instances.size() < 12) return failed("accumulator_limb", "an accumulator needs twelve instance values");
+    uint32_t q[8]; for (int i = 0; i < 8; i++) q[i] = zk::FqP::mod(i);
+    zk::fe_t co[4];
+    for (int cidx = 0; cidx < 4; cidx++) {
+      uint64_t wds[5] = {0, 0, 0, 0, 0};
+      for (int l = 0; l < 3; l++) {
+        const Fr cv = fr_to_canonical(instances[3 * cidx + l]);
+        if (cv[2] || cv[3] || (cv[1] >> 24)) return failed("accumulator_limb", "instance " + std::to_string(3 * cidx + l) + " is an accumulator limb of 2^88 or more");
+        const int bit = 88 * l, wi = bit / 64, sh = bit % 64;
+        wds[wi] |= cv[0] << sh; if (sh) { wds[wi + 1] |= cv[0] >> (64 - sh); } wds[wi + 1] |= cv[1] << sh; if (sh && wi + 2 < 5) wds[wi + 2] |= cv[1] >> (64 - sh);
+      }
+      std::memcpy(&co[cidx], wds, 32);
+      if (wds[4] || zk::Fq::w_geq(co[cidx].l, q)) return failed("accumulator_point", "accumulator coordinate " + std::to_string(cidx) + " is not below q");
+      co[cidx] = zk::Fq::from_canonical(co[cidx]);
+    }
+    std::memcpy(res.acc_lhs.data(), &co[0], 32); std::memcpy(res.acc_lhs.data() + 4, &co[1], 32); std::memcpy(res.acc_rhs.data(), &co[2], 32); std::memcpy(res.acc_rhs.data() + 4, &co[3], 32);
+    if (!vdetail::fq_on_curve(res.acc_lhs) || !vdetail::fq_on_curve(res.acc_rhs)) return failed("accumulator_point", "a point of the carried accumulator is not on the curve");
+  }
+  if (opt.host_only) { res.ok = true; res.error = ""; res.detail = "host-only: stopped before the multi-scalar multiplication and the pairing"; return res; }
+
+  // ---- one MSM, one pairing call
+  halo2::G1 sum{};
+  halo2::check(mi355_msm_g1_adhoc_host(res.msm_points.data(), res.msm_scalars.data(), res.msm_scalars.size(), sum.data()));
+  std::memcpy(res.msm_result.data(), sum.data(), 64);
+  const uint32_t groups = res.has_accumulator ? 2 : 1;
+  std::vector<G1Affine> Pp = {res.msm_result, c_w}; if (groups == 2) { Pp.push_back(res.acc_lhs); Pp.push_back(res.acc_rhs); }
+  std::vector<uint8_t> Qq(256 * groups);
+  for (uint32_t g = 0; g < groups; g++) { std::memcpy(Qq.data() + 256 * g, srs.g2.data(), 128); std::memcpy(Qq.data() + 256 * g + 128, srs.neg_s_g2.data(), 128); }
+  res.pairing.assign(groups, 0);
+  halo2::check(mi355_pairing_products_host(Pp.data(), Qq.data(), groups, 2, nullptr, res.pairing.data()));
+  if (!res.pairing[0]) return failed("pairing", "e(lhs, g2) e(W', -s_g2) != 1");
+  if (groups == 2 && !res.pairing[1]) return failed("accumulator_pairing", "the carried accumulator does not satisfy e(lhs, g2) e(rhs, -s_g2) == 1");
+  res.ok = true;
+  return res;
+}
+
+}  // namespace plonk
+}  // namespace mi355zk

@@ -337,18 +337,13 @@ struct Transcript {
     if (kind == TranscriptKind::Evm) { uint8_t w[32]; be32(c, w); proof.insert(proof.end(), w, w + 32); return; }
     const uint8_t *p = reinterpret_cast<const uint8_t *>(&c); proof.insert(proof.end(), p, p + 32);
   }
-  // g: a commitment as the C-ABI returns it (normalised Jacobian: x, y, z = R; all-zero = identity)
-  void write_point(const halo2::G1 &g) {
-    halo2::G1Affine a; std::memcpy(a.data(), g.data(), 64);
-    bool ident = true; for (auto w : g) ident = ident && w == 0;
+  // absorb a point without writing it (the verifier's side of write_point; also the preprocessed commitments are NOT absorbed: the key's scalar stands for them)
+  void common_point(const halo2::G1Affine &a) {
+    bool ident = true; for (auto w : a) ident = ident && w == 0;
     if (ident) throw std::invalid_argument("transcript: the identity has no coordinates (halo2's common_point fails on it)");
     zk::fe_t x, y; std::memcpy(&x, a.data(), 32); std::memcpy(&y, a.data() + 4, 32);
     const zk::fe_t xc = zk::Fq::to_canonical(x), yc = zk::Fq::to_canonical(y);
-    if (kind == TranscriptKind::Evm) {
-      uint8_t w[64]; be32(xc, w); be32(yc, w + 32);
-      evm_buf.insert(evm_buf.end(), w, w + 64); proof.insert(proof.end(), w, w + 64);
-      return;
-    }
+    if (kind == TranscriptKind::Evm) { uint8_t w[64]; be32(xc, w); be32(yc, w + 32); evm_buf.insert(evm_buf.end(), w, w + 64); return; }
     if (kind == TranscriptKind::Poseidon) {
       auto base_to_scalar = [](zk::fe_t c) {   // a base-field coordinate as a scalar: its value mod r (q < 2 r: one subtraction at most)
         uint32_t m[8]; for (int i = 0; i < 8; i++) m[i] = zk::FrP::mod(i);
@@ -359,7 +354,59 @@ struct Transcript {
     } else {
       const uint8_t tag = 1; state.update(&tag, 1); state.update(&xc, 32); state.update(&yc, 32);
     }
+  }
+  // g: a commitment as the C-ABI returns it (normalised Jacobian: x, y, z = R; all-zero = identity)
+  void write_point(const halo2::G1 &g) {
+    halo2::G1Affine a; std::memcpy(a.data(), g.data(), 64);
+    bool ident = true; for (auto w : g) ident = ident && w == 0;
+    if (ident) throw std::invalid_argument("transcript: the identity has no coordinates (halo2's common_point fails on it)");
+    common_point(a);
+    if (kind == TranscriptKind::Evm) {
+      zk::fe_t x, y; std::memcpy(&x, a.data(), 32); std::memcpy(&y, a.data() + 4, 32);
+      uint8_t w[64]; be32(zk::Fq::to_canonical(x), w); be32(zk::Fq::to_canonical(y), w + 32);
+      proof.insert(proof.end(), w, w + 64);
+      return;
+    }
     const halo2::G1Bytes b = halo2::g1_to_bytes(a); proof.insert(proof.end(), b.begin(), b.end());
+  }
+
+  // ---- read side (the verifier): the proof is walked with a cursor; every way a word can be wrong is a status, not an exception
+  enum class Read { Ok, Short /* the proof ends inside the word */, NonCanonical /* a scalar word >= r */, InvalidPoint /* a word that is no curve point (or the identity) */ };
+  size_t point_bytes() const { return kind == TranscriptKind::Evm ? 64 : 32; }
+  Read read_scalar(const std::vector<uint8_t> &in, size_t &pos, halo2::Fr &out) {
+    if (pos + 32 > in.size()) return Read::Short;
+    zk::fe_t c; uint8_t *le = reinterpret_cast<uint8_t *>(&c);
+    if (kind == TranscriptKind::Evm) for (int i = 0; i < 32; i++) le[i] = in[pos + 31 - i]; else std::memcpy(le, in.data() + pos, 32);
+    pos += 32;
+    uint32_t m[8]; for (int i = 0; i < 8; i++) m[i] = zk::FrP::mod(i);
+    if (zk::Fr::w_geq(c.l, m)) return Read::NonCanonical;
+    out = halo2::detail::from_fe(zk::Fr::from_canonical(c));
+    common_scalar(out);
+    return Read::Ok;
+  }
+  // decoded: the point this word decompresses to, when the caller has decoded the proof's compressed words in one device call (all-zero: the word was rejected there);
+  // null: decode here (the uncompressed Evm layout, checked on the curve; or the host decompression of the host-only mode)
+  Read read_point(const std::vector<uint8_t> &in, size_t &pos, const halo2::G1Affine *decoded, halo2::G1Affine &out) {
+    const size_t nb = point_bytes();
+    if (pos + nb > in.size()) return Read::Short;
+    if (kind == TranscriptKind::Evm) {
+      zk::fe_t c[2]; uint32_t q[8]; for (int i = 0; i < 8; i++) q[i] = zk::FqP::mod(i);
+      for (int k = 0; k < 2; k++) { uint8_t *le = reinterpret_cast<uint8_t *>(&c[k]); for (int i = 0; i < 32; i++) le[i] = in[pos + 32 * k + 31 - i]; }
+      pos += nb;
+      if (zk::Fq::w_geq(c[0].l, q) || zk::Fq::w_geq(c[1].l, q)) return Read::InvalidPoint;
+      const zk::fe_t x = zk::Fq::from_canonical(c[0]), y = zk::Fq::from_canonical(c[1]);
+      zk::fe_t three = zk::Fq::zero(); three.l[0] = 3; three = zk::Fq::from_canonical(three);
+      if (!zk::Fq::eq(zk::Fq::sqr(y), zk::Fq::add(zk::Fq::mul(zk::Fq::sqr(x), x), three))) return Read::InvalidPoint;   // (0, 0) fails here too
+      std::memcpy(out.data(), &x, 32); std::memcpy(out.data() + 4, &y, 32);
+    } else {
+      if (decoded) out = *decoded;
+      else { halo2::G1Bytes b; std::memcpy(b.data(), in.data() + pos, 32); if (!halo2::g1_from_bytes(b, out)) out.fill(0); }
+      pos += nb;
+      bool ident = true; for (auto w : out) ident = ident && w == 0;
+      if (ident) return Read::InvalidPoint;
+    }
+    common_point(out);
+    return Read::Ok;
   }
 };
 

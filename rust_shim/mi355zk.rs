@@ -81,6 +81,8 @@ extern "C" {
     pub fn mi355_msm_g2_adhoc_host(bases_g2affine_host: *const c_void, scalars_host: *const c_void, n: u64, out_g2affine_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g2_dev(bases_g2affine_dev: *const c_void, scalars_dev: *const c_void, n: u64, out_g2affine_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g2_batch_dev(bases_g2affine_dev: *const c_void, scalars_dev: *const *const c_void, batch: u32, n: u64, out_g2affine_host: *mut c_void) -> c_int;
+    pub fn mi355_pairing_products_host(p_g1affine_host: *const c_void, q_g2affine_host: *const c_void, groups: u32, pairs_per_group: u32,
+                                       gt_out_host: *mut c_void, is_one_out_host: *mut u32) -> c_int;
     pub fn mi355_intt_fr_dev(data_dev: *mut c_void, log_n: u32, omega_inv: *const c_void, divisor: *const c_void) -> c_int;
     pub fn mi355_ntt_fr_batch_host(data_host: *const *mut c_void, batch: u32, log_n: u32, omega: *const c_void, divisor: *const c_void) -> c_int;
     pub fn mi355_ntt_fr_batch_dev(data_dev: *const *mut c_void, batch: u32, log_n: u32, omega: *const c_void, divisor: *const c_void) -> c_int;

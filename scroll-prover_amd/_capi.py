@@ -102,6 +102,7 @@ SIGNATURES = {
     "mi355_msm_g2_adhoc_host": (_int, [_vp, _vp, _u64, _vp]),
     "mi355_msm_g2_dev": (_int, [_vp, _vp, _u64, _vp]),
     "mi355_msm_g2_batch_dev": (_int, [_vp, C.POINTER(_vp), _u32, _u64, _vp]),
+    "mi355_pairing_products_host": (_int, [_vp, _vp, _u32, _u32, _vp, C.POINTER(_u32)]),
     "mi355_profile_enable": (_int, [_int]),
     "mi355_profile_get": (_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),
     "mi355_profile_reset": (_int, []),

@@ -1,6 +1,6 @@
 """build.py -- compiles libmi355zk.so for gfx950 with hipcc (in-tree, next to this file).
 
-The library is four translation units (csrc/lib_core|lib_msm|lib_ntt|lib_aux.hip) compiled in parallel and linked; a change to one
+The library is five translation units (csrc/lib_core|lib_msm|lib_ntt|lib_aux|lib_pairing.hip) compiled in parallel and linked; a change to one
 kernel family rebuilds one unit.  Staleness is decided by CONTENT (sha256 of every file a unit includes + the flags), not by mtimes, so a
 copied tree (the GPU box's snapshot) never rebuilds what was built here.
 """
@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libmi355zk.so")
-UNITS = ["lib_core", "lib_msm", "lib_ntt", "lib_aux"]
+UNITS = ["lib_core", "lib_msm", "lib_ntt", "lib_aux", "lib_pairing"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DNDEBUG", "-Wno-unused-result"]
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
@@ -98,7 +98,7 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
 
 
-CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check")
+CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check", "test_verify_proof")
 
 
 def build_cpp(name: str) -> str:

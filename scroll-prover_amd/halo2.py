@@ -16,6 +16,7 @@ The constants (omega, n^-1, ...) are computed with Python integers -- host set-u
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -461,6 +462,78 @@ def g2_msm_batch_dev(bases, scalars_list, n: int) -> np.ndarray:
     return out[:m]
 
 
+def pairing_products(P, Q, groups: int, pairs_per_group: int, want_gt: bool = True, want_is_one: bool = True):
+    """mi355_pairing_products_host: out[g] = prod_j e(P[g * ppg + j], Q[g * ppg + j]) on the device.  P: [groups * ppg, 8] u64 G1Affine, Q: [groups * ppg, 16] u64
+    G2Affine (Montgomery, identity = zeros: such a pair contributes 1) -> (gt [groups, 48] u64 in halo2curves' Fq12 layout, is_one [groups] u32: 1 where the product
+    is 1, the answer of the EVM precompile at address 8).  want_gt / want_is_one = False leaves that output out (None in its place).  Every point must lie on its
+    curve (Mi355Error EBADARG names the first pair that does not); Q is not checked for membership of the subgroup of order r."""
+    n = int(groups) * int(pairs_per_group)
+    P = np.ascontiguousarray(P, dtype=np.uint64).reshape(-1, 8)
+    Q = np.ascontiguousarray(Q, dtype=np.uint64).reshape(-1, 16)
+    assert P.shape[0] == n and Q.shape[0] == n, "pairing_products: groups * pairs_per_group points on each side"
+    gt = np.zeros((groups, 48), dtype=np.uint64) if want_gt else None
+    one = np.zeros(groups, dtype=np.uint32) if want_is_one else None
+    check(lib().mi355_pairing_products_host(ptr(P), ptr(Q), groups, pairs_per_group, ptr(gt), None if one is None else one.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return gt, one
+
+
+def verify_proof(protocol, instances, proof: bytes, transcript: str | None = None, vk_bytes: bytes | None = None, preprocessed=None, initial_state: int | None = None,
+                 g2=None, s_g2=None, neg_s_g2=None, check_accumulator: bool = True, accumulator: bool | None = None, host_only: bool = False, timeout: int = 600) -> dict:
+    """plonk::verify_proof (include/mi355zk_plonk_verify.hpp) through its compiled driver tests/cpp/test_verify_proof.cpp, run as a process the way replay.py runs the prover.
+    protocol: a path to a PlonkProtocol JSON or the dict itself; instances: integers; key: vk_bytes (.vkey) | preprocessed ([n, 8] u64 G1Affine) | the protocol file's own;
+    g2 + (s_g2 | neg_s_g2): 128-byte G2Affine values (bytes or 16 u64; default g2: the generator) -- s_g2 is negated on the host.  host_only=True stops after the
+    (scalars, points) list and needs no device.  Returns the driver's record: ok, error (the name of the first failed check), challenges, numerator_at_x, msm {scalars,
+    points, result, w_prime}, pairing (per-group flags); field elements and coordinates as integers."""
+    import json, subprocess, tempfile
+    from . import build
+    exe = build.build_cpp("test_verify_proof")
+    as_g2 = lambda q: q if isinstance(q, (bytes, bytearray)) else np.ascontiguousarray(q, dtype=np.uint64).tobytes()
+    with tempfile.TemporaryDirectory(prefix="mi355_verify_") as d:
+        def put(name, data):
+            path = os.path.join(d, name)
+            with open(path, "wb") as f:
+                f.write(data)
+            return path
+        if isinstance(protocol, dict):
+            path = os.path.join(d, "protocol.json")
+            with open(path, "w") as f:
+                json.dump(protocol, f, separators=(",", ":"))
+            protocol = path
+        args = [exe, "--protocol", protocol, "--proof", put("proof.bin", bytes(proof)), "--instances", put("instances.bin", b"".join(int(v).to_bytes(32, "big") for v in instances))]
+        if transcript:
+            args += ["--transcript", transcript]
+        if vk_bytes is not None:
+            args += ["--vk", put("vk.bin", bytes(vk_bytes))]
+        if preprocessed is not None:
+            args += ["--preprocessed", put("pre.bin", np.ascontiguousarray(preprocessed, dtype=np.uint64).tobytes())]
+        if initial_state is not None:
+            args += ["--initial-state", "%x" % initial_state]
+        if not host_only:
+            args += ["--g2", put("g2.bin", as_g2(g2 if g2 is not None else g2_generator()))]
+            assert (s_g2 is None) != (neg_s_g2 is None), "verify_proof: give s_g2 or neg_s_g2"
+            args += ["--s-g2", put("sg2.bin", as_g2(s_g2))] if s_g2 is not None else ["--neg-s-g2", put("nsg2.bin", as_g2(neg_s_g2))]
+        if not check_accumulator:
+            args.append("--no-accumulator")
+        if accumulator:
+            args.append("--accumulator")
+        if host_only:
+            args.append("--host-only")
+        out = subprocess.run(args, capture_output=True, text=True, timeout=timeout)
+    line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
+    if out.returncode != 0 or line is None:
+        raise Mi355Error(_capi.EBADARG, "verify_proof driver failed: " + (out.stdout + out.stderr)[-800:])
+    rec = json.loads(line)
+    h = lambda s: int(s, 16)
+    rec["challenges"] = {k: h(v) for k, v in rec["challenges"].items()}
+    rec["numerator_at_x"] = h(rec["numerator_at_x"])
+    m = rec["msm"]
+    m["scalars"] = [h(v) for v in m["scalars"]]
+    for key in ("result", "w_prime"):
+        m[key] = (h(m[key][0]), h(m[key][1]))
+    m["points"] = [(h(a), h(b)) for a, b in m["points"]]
+    return rec
+
+
 def g1_sum(points: np.ndarray) -> np.ndarray:
     """fold of per-GPU partial results: results.iter().fold(identity, |a, b| a + b)."""
     points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
@@ -672,6 +745,20 @@ class ParamsKZG:
         check(lib().mi355_srs_release(self._gl))
         self._gl = h.value
         self.k, self.n = k, 1 << k
+
+    def check_g2(self) -> bool:
+        """e(g[0], s_g2) * e(-g[1], g2) == 1: the file's (or setup's) s_g2 is [tau] g2 for the tau of the G1 basis, with G2 ordered and signed as the pairing
+        reads it.  One pairing call over two points read back from the device; nothing calls it by default."""
+        assert self.n >= 2, "check_g2 needs g[0] and g[1]"
+        g01 = np.zeros((2, 8), dtype=np.uint64)
+        check(lib().mi355_srs_read_host(self._g, 0, 2, ptr(g01)))
+        y = sum(int(v) << (64 * i) for i, v in enumerate(g01[1, 4:]))
+        if g01[1].any():
+            y = (P_MOD - y) % P_MOD
+            g01[1, 4:] = [(y >> (64 * i)) & _M64 for i in range(4)]
+        Q = np.stack([np.frombuffer(self.s_g2, dtype=np.uint64), np.frombuffer(self.g2, dtype=np.uint64)])
+        _, one = pairing_products(g01, Q, 1, 2, want_gt=False)
+        return bool(one[0])
 
     def read_g(self, lagrange: bool = False) -> np.ndarray:
         """the first n points of g (or g_lagrange) back on the host: [n, 8] (what ParamsKZG::write serialises)."""
