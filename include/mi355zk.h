@@ -166,6 +166,14 @@ int mi355_msm_g1_batch_dev(uint64_t srs_handle, uint64_t base_offset, const void
 int mi355_msm_g1_batch_host(uint64_t srs_handle, uint64_t base_offset, const void *const *scalars_host, uint32_t batch, uint64_t n, void *out_g1_host);
 /* ad-hoc bases (best_multiexp with bases that are not a registered SRS)                                        */
 int mi355_msm_g1_adhoc_host(const void *bases_affine_host, const void *scalars_host, uint64_t n, void *out_g1_host);
+/* MANY SHORT MSMs in one launch: the final MSM of a verifier (19-24 terms), once per proof of a batch.  Serves the aggregator's native succinct verification of
+ * every chunk / layer snark behind gen_batch_proof [REF integration/src/prove.rs:67] (extract_accumulators_and_proof [EXT-recalled]) and plonk::verify_proofs / plonk::aggregate.
+ * out[s] = sum_{offsets[s] <= i < offsets[s+1]} scalars[i] * bases[i], s < segments.  bases: G1Affine 64 B (identity (0,0) allowed), scalars: Fr 32 B Montgomery,
+ * offsets: segments + 1 values, offsets[0] = 0, non-decreasing; out: segments x G1Affine (identity = all zero), the form mi355_pairing_products_host takes.
+ * One wavefront per segment, one double-and-add per term: any length is correct, a long one is slow -- use mi355_msm_g1_adhoc_host for those.
+ * MI355_EBADARG (before the device is looked at): null pointers, offsets[0] != 0, decreasing offsets, segments > 2^20, more than 2^24 terms.  segments == 0 touches nothing.
+ * Bases are not validated (the contract of mi355_msm_g1_adhoc_host).                                                                                                  */
+int mi355_msm_g1_segmented_host(const void *bases_affine_host, const void *scalars_host, const uint64_t *offsets_host, uint32_t segments, void *out_g1affine_host);
 /* sum of `n` G1 (Jacobian, any representative) points: the fold `results.iter().fold(identity, |a, b| a + b)` of
  * best_multiexp, used to combine per-GPU partial sums after the RCCL all-gather.                  */
 int mi355_g1_sum_host(const void *g1_points_host, uint64_t n, void *out_g1_host);

@@ -74,6 +74,15 @@ inline G1 best_multiexp(const std::vector<Fr> &coeffs, const std::vector<G1Affin
   check(mi355_msm_g1_adhoc_host(bases.data(), coeffs.data(), coeffs.size(), out.data()));
   return out;
 }
+// many short best_multiexp calls in one launch (mi355_msm_g1_segmented_host): out[s] = sum over [offsets[s], offsets[s + 1]) of coeffs[i] * bases[i], affine (identity = zeros);
+// offsets has one entry more than there are segments and ends at coeffs.len().  The final MSMs of a batch of verifiers; a long segment belongs to best_multiexp.
+inline std::vector<G1Affine> msm_g1_segmented(const std::vector<Fr> &coeffs, const std::vector<G1Affine> &bases, const std::vector<uint64_t> &offsets) {
+  if (coeffs.size() != bases.size()) throw std::invalid_argument("msm_g1_segmented: coeffs.len() != bases.len()");
+  if (offsets.empty() || offsets.back() != coeffs.size()) throw std::invalid_argument("msm_g1_segmented: offsets must end at coeffs.len()");
+  std::vector<G1Affine> out(offsets.size() - 1);
+  check(mi355_msm_g1_segmented_host(bases.data(), coeffs.data(), offsets.data(), (uint32_t)(offsets.size() - 1), out.data()));
+  return out;
+}
 inline void best_fft(std::vector<Fr> &a, const Fr &omega, uint32_t log_n) {
   if (a.size() != (size_t(1) << log_n)) throw std::invalid_argument("best_fft: a.len() != 1 << log_n");
   check(mi355_ntt_fr_host(a.data(), log_n, omega.data()));

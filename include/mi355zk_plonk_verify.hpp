@@ -10,6 +10,8 @@
 //   pairing     ONE mi355_pairing_products_host call: group 0 = e(lhs, g2) e(W', -s_g2); group 1 = the carried accumulator when the protocol has one
 // Failures of the INPUT (proof, key, instances, protocol) are statuses in VerifyResult::error; only a failing device call throws (halo2::Error, as everywhere in these headers).
 // VerifyOptions::host_only stops after the list is built (points decompressed on the host): the verifier's own logic runs without a device.
+// plonk::verify_proofs runs the same host part for N proofs and ONE decompression, ONE segmented MSM and ONE pairing call for all of them; plonk::aggregate folds their
+// KZG accumulators into the one the next layer's first twelve instances carry (KzgAs).  Both stand further down, behind verify_proof.
 #pragma once
 #include "mi355zk_plonk_protocol.hpp"
 #include "mi355zk_transcript.hpp"
@@ -64,40 +66,56 @@ inline Fr eval_expr(const Expr &e, const std::map<PolyRot, Fr> &evals, const Fr 
   throw std::invalid_argument("verify: unknown expression node");
 }
 inline Fr pow_rot(const Protocol &P, int32_t r) { return r >= 0 ? fr_pow(P.omega, (uint64_t)r) : fr_pow(P.omega_inv, (uint64_t)(-(int64_t)r)); }
-}  // namespace vdetail
 
-inline VerifyResult verify_proof(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const G2Pair &srs, const VerifyOptions &opt) {
-  using halo2::G1Affine;
-  VerifyResult res;
-  auto failed = [&](const char *name, const std::string &why) { res.ok = false; res.error = name; res.detail = why; return res; };
-  const TranscriptKind kind = opt.transcript == TranscriptKind::ByLayer ? (P.layer == 6 ? TranscriptKind::Evm : TranscriptKind::Poseidon) : opt.transcript;
-  Transcript T(kind);
-  const size_t nb = T.point_bytes();
+// ---- the HOST PART of one verification, in three steps that plonk::verify_proof runs for one proof and plonk::verify_proofs / plonk::aggregate for many:
+//   layout_of     what the proof's length and the key decide before any point is looked at: the transcript, the word counts, every compressed point word
+//   decode_words  the words -> affine points (all-zero for a rejected word): one mi355_g1_decompress_host call, or the host decoder
+//   host_part     the transcript, the scalar side, the SHPLONK list and the carried accumulator; what VerifyOptions::host_only stops after
+// Each returns false after it has written the named failure into `res`.
+inline bool failed(VerifyResult &res, const char *name, const std::string &why) { res.ok = false; res.error = name; res.detail = why; return false; }
+inline uint64_t &device_calls() { static uint64_t n = 0; return n; }   // how many C-ABI calls that need a device the verifiers of this header have made (the drivers print it)
+struct Layout { TranscriptKind kind = TranscriptKind::Poseidon; size_t nb = 32, n_com = 0, n_ev = 0, vk0 = 0; bool use_vk = false; std::vector<halo2::G1Bytes> words; };
+inline bool layout_of(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<uint8_t> &proof, const VerifyOptions &opt, Layout &L, VerifyResult &res) {
+  L.kind = opt.transcript == TranscriptKind::ByLayer ? (P.layer == 6 ? TranscriptKind::Evm : TranscriptKind::Poseidon) : opt.transcript;
+  L.nb = Transcript(L.kind).point_bytes();
   uint32_t nw = 0; for (auto w : P.num_witness) nw += w;
-  const size_t n_com = nw + P.Q, n_ev = P.evaluations.size(), expect = (n_com + 2) * nb + n_ev * 32;
-  if (proof.size() != expect) return failed("proof_length", "proof has " + std::to_string(proof.size()) + " bytes, the protocol reads " + std::to_string(expect));
+  L.n_com = nw + P.Q; L.n_ev = P.evaluations.size();
+  const size_t expect = (L.n_com + 2) * L.nb + L.n_ev * 32;
+  if (proof.size() != expect) return failed(res, "proof_length", "proof has " + std::to_string(proof.size()) + " bytes, the protocol reads " + std::to_string(expect));
 
   // ---- every compressed point word of the proof (and of the .vkey) through one decompression
-  const bool use_vk = !vk.vk_bytes.empty();
-  if (use_vk && vk.vk_bytes.size() != 8 + 32 * (size_t)P.num_pre) return failed("vk_length", "the .vkey has " + std::to_string(vk.vk_bytes.size()) + " bytes, the protocol has " + std::to_string(P.num_pre) + " preprocessed polynomials");
-  std::vector<halo2::G1Bytes> words;
-  if (kind != TranscriptKind::Evm) {
-    words.resize(n_com + 2);
-    for (size_t i = 0; i < n_com; i++) std::memcpy(words[i].data(), proof.data() + 32 * i, 32);
-    for (size_t i = 0; i < 2; i++) std::memcpy(words[n_com + i].data(), proof.data() + 32 * (n_com + n_ev) + (i ? 32 : 0), 32);
+  L.use_vk = !vk.vk_bytes.empty();
+  if (L.use_vk && vk.vk_bytes.size() != 8 + 32 * (size_t)P.num_pre) return failed(res, "vk_length", "the .vkey has " + std::to_string(vk.vk_bytes.size()) + " bytes, the protocol has " + std::to_string(P.num_pre) + " preprocessed polynomials");
+  std::vector<halo2::G1Bytes> &words = L.words;
+  if (L.kind != TranscriptKind::Evm) {
+    words.resize(L.n_com + 2);
+    for (size_t i = 0; i < L.n_com; i++) std::memcpy(words[i].data(), proof.data() + 32 * i, 32);
+    for (size_t i = 0; i < 2; i++) std::memcpy(words[L.n_com + i].data(), proof.data() + 32 * (L.n_com + L.n_ev) + (i ? 32 : 0), 32);
   }
-  const size_t vk0 = words.size();
-  if (use_vk) { words.resize(vk0 + P.num_pre); for (uint32_t i = 0; i < P.num_pre; i++) std::memcpy(words[vk0 + i].data(), vk.vk_bytes.data() + 8 + 32 * i, 32); }
-  std::vector<G1Affine> decoded(words.size());
+  L.vk0 = words.size();
+  if (L.use_vk) { words.resize(L.vk0 + P.num_pre); for (uint32_t i = 0; i < P.num_pre; i++) std::memcpy(words[L.vk0 + i].data(), vk.vk_bytes.data() + 8 + 32 * i, 32); }
+  return true;
+}
+inline void decode_words(const std::vector<halo2::G1Bytes> &words, std::vector<halo2::G1Affine> &decoded, bool on_host) {
+  using halo2::G1Affine;
+  decoded.assign(words.size(), G1Affine{});
   if (!words.empty()) {
-    if (opt.host_only) { for (size_t i = 0; i < words.size(); i++) if (!halo2::g1_from_bytes(words[i], decoded[i])) decoded[i].fill(0); }
+    if (on_host) { for (size_t i = 0; i < words.size(); i++) if (!halo2::g1_from_bytes(words[i], decoded[i])) decoded[i].fill(0); }
     else {
-      uint64_t bad = ~0ull; const int rc = mi355_g1_decompress_host(words.data(), decoded.data(), words.size(), &bad);
+      uint64_t bad = ~0ull; device_calls()++; const int rc = mi355_g1_decompress_host(words.data(), decoded.data(), words.size(), &bad);
       if (rc == MI355_EBADARG && bad != ~0ull) {   // a rejected word: name it below, where the transcript reaches it; the words behind it are decoded on the host
         for (size_t i = 0; i < words.size(); i++) if (!halo2::g1_from_bytes(words[i], decoded[i])) decoded[i].fill(0);
       } else halo2::check(rc);
     }
   }
+}
+// decoded: the L.words.size() points of THIS proof (its slice of a batch's decompression)
+inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const VerifyOptions &opt, const Layout &L,
+                      const halo2::G1Affine *decoded, VerifyResult &res) {
+  using halo2::G1Affine;
+  auto failed = [&](const char *name, const std::string &why) { return vdetail::failed(res, name, why); };
+  const TranscriptKind kind = L.kind; const bool use_vk = L.use_vk; const size_t nb = L.nb, n_ev = L.n_ev, vk0 = L.vk0;
+  Transcript T(kind);
   std::vector<G1Affine> pre;
   if (use_vk) { for (uint32_t i = 0; i < P.num_pre; i++) { pre.push_back(decoded[vk0 + i]); bool z = true; for (auto w : pre.back()) z = z && w == 0; if (z) return failed("invalid_point", ".vkey commitment " + std::to_string(i) + " is no curve point"); } }
   else pre = vk.preprocessed.empty() ? P.preprocessed : vk.preprocessed;
@@ -221,23 +239,163 @@ inline VerifyResult verify_proof(const Protocol &P, const VerifyingKeyRef &vk, c
     std::memcpy(res.acc_lhs.data(), &co[0], 32); std::memcpy(res.acc_lhs.data() + 4, &co[1], 32); std::memcpy(res.acc_rhs.data(), &co[2], 32); std::memcpy(res.acc_rhs.data() + 4, &co[3], 32);
     if (!vdetail::fq_on_curve(res.acc_lhs) || !vdetail::fq_on_curve(res.acc_rhs)) return failed("accumulator_point", "a point of the carried accumulator is not on the curve");
   }
-  if (opt.host_only) { res.ok = true; res.error = ""; res.detail = "host-only: stopped before the multi-scalar multiplication and the pairing"; return res; }
+  return true;
+}
+inline void host_only_done(VerifyResult &res) { res.ok = true; res.error = ""; res.detail = "host-only: stopped before the multi-scalar multiplication and the pairing"; }
+// the verdict over a proof's one or two pairing groups (res.pairing filled)
+inline void judge(VerifyResult &res) {
+  if (!res.pairing[0]) { failed(res, "pairing", "e(lhs, g2) e(W', -s_g2) != 1"); return; }
+  if (res.pairing.size() == 2 && !res.pairing[1]) { failed(res, "accumulator_pairing", "the carried accumulator does not satisfy e(lhs, g2) e(rhs, -s_g2) == 1"); return; }
+  res.ok = true;
+}
+// `groups` pairing groups of (P[2 g], g2) (P[2 g + 1], -s_g2): one mi355_pairing_products_host call
+inline std::vector<uint32_t> pairing_groups(const std::vector<halo2::G1Affine> &Pp, const G2Pair &srs) {
+  const uint32_t groups = (uint32_t)(Pp.size() / 2);
+  std::vector<uint8_t> Qq(256 * (size_t)groups);
+  for (uint32_t g = 0; g < groups; g++) { std::memcpy(Qq.data() + 256 * (size_t)g, srs.g2.data(), 128); std::memcpy(Qq.data() + 256 * (size_t)g + 128, srs.neg_s_g2.data(), 128); }
+  std::vector<uint32_t> flags(groups, 0);
+  device_calls()++; halo2::check(mi355_pairing_products_host(Pp.data(), Qq.data(), groups, 2, nullptr, flags.data()));
+  return flags;
+}
+}  // namespace vdetail
+
+inline VerifyResult verify_proof(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const G2Pair &srs, const VerifyOptions &opt) {
+  using halo2::G1Affine;
+  VerifyResult res; vdetail::Layout L;
+  if (!vdetail::layout_of(P, vk, proof, opt, L, res)) return res;
+  std::vector<G1Affine> decoded; vdetail::decode_words(L.words, decoded, opt.host_only);
+  if (!vdetail::host_part(P, vk, instances, proof, opt, L, decoded.data(), res)) return res;
+  if (opt.host_only) { vdetail::host_only_done(res); return res; }
 
   // ---- one MSM, one pairing call
   halo2::G1 sum{};
-  halo2::check(mi355_msm_g1_adhoc_host(res.msm_points.data(), res.msm_scalars.data(), res.msm_scalars.size(), sum.data()));
+  vdetail::device_calls()++; halo2::check(mi355_msm_g1_adhoc_host(res.msm_points.data(), res.msm_scalars.data(), res.msm_scalars.size(), sum.data()));
   std::memcpy(res.msm_result.data(), sum.data(), 64);
-  const uint32_t groups = res.has_accumulator ? 2 : 1;
-  std::vector<G1Affine> Pp = {res.msm_result, c_w}; if (groups == 2) { Pp.push_back(res.acc_lhs); Pp.push_back(res.acc_rhs); }
-  std::vector<uint8_t> Qq(256 * groups);
-  for (uint32_t g = 0; g < groups; g++) { std::memcpy(Qq.data() + 256 * g, srs.g2.data(), 128); std::memcpy(Qq.data() + 256 * g + 128, srs.neg_s_g2.data(), 128); }
-  res.pairing.assign(groups, 0);
-  halo2::check(mi355_pairing_products_host(Pp.data(), Qq.data(), groups, 2, nullptr, res.pairing.data()));
-  if (!res.pairing[0]) return failed("pairing", "e(lhs, g2) e(W', -s_g2) != 1");
-  if (groups == 2 && !res.pairing[1]) return failed("accumulator_pairing", "the carried accumulator does not satisfy e(lhs, g2) e(rhs, -s_g2) == 1");
-  res.ok = true;
+  std::vector<G1Affine> Pp = {res.msm_result, res.w_prime}; if (res.has_accumulator) { Pp.push_back(res.acc_lhs); Pp.push_back(res.acc_rhs); }
+  res.pairing = vdetail::pairing_groups(Pp, srs);
+  vdetail::judge(res);
   return res;
 }
 
+// ------------------------------------------------------------------------------------------------ many proofs in one pass
+// plonk::verify_proofs: N proofs, ONE decompression, ONE segmented MSM (mi355_msm_g1_segmented_host), ONE pairing call -- a pairing call costs one lane's latency whether it
+// judges one group or hundreds (profiles/pairing.md).  Protocols, keys and transcripts may differ inside a batch.  A proof that fails its host part keeps its named failure and
+// leaves the batch; when nothing survives no device call is made.  Every VerifyResult equals verify_proof's for that proof alone.  A proof with VerifyOptions::host_only decodes
+// its points on the host and stops after its list, as in verify_proof.
+struct ProofInput { const Protocol *protocol = nullptr; const VerifyingKeyRef *vk = nullptr; std::vector<Fr> instances; std::vector<uint8_t> proof; VerifyOptions opt; };
+
+namespace vdetail {
+// passed[i]: proof i reached the end of its host part (its list and, when it carries one, its accumulator are in res[i])
+inline void host_parts(const std::vector<ProofInput> &in, std::vector<VerifyResult> &res, std::vector<char> &passed) {
+  using halo2::G1Affine;
+  const size_t N = in.size();
+  res.assign(N, VerifyResult{}); passed.assign(N, 0);
+  std::vector<Layout> L(N); std::vector<size_t> at(N, 0); std::vector<halo2::G1Bytes> words;
+  for (size_t i = 0; i < N; i++) {
+    if (!in[i].protocol || !in[i].vk) throw std::invalid_argument("verify_proofs: proof " + std::to_string(i) + " has no protocol or no key");
+    passed[i] = layout_of(*in[i].protocol, *in[i].vk, in[i].proof, in[i].opt, L[i], res[i]) ? 1 : 0;
+    if (passed[i] && !in[i].opt.host_only) { at[i] = words.size(); words.insert(words.end(), L[i].words.begin(), L[i].words.end()); }
+  }
+  std::vector<G1Affine> decoded; decode_words(words, decoded, false);
+  for (size_t i = 0; i < N; i++) {
+    if (!passed[i]) continue;
+    std::vector<G1Affine> own; if (in[i].opt.host_only) decode_words(L[i].words, own, true);
+    passed[i] = host_part(*in[i].protocol, *in[i].vk, in[i].instances, in[i].proof, in[i].opt, L[i], in[i].opt.host_only ? own.data() : decoded.data() + at[i], res[i]) ? 1 : 0;
+  }
+}
+// the lists of the proofs `idx` names, concatenated: one segmented MSM, the sums into msm_result
+inline void msm_of_lists(std::vector<VerifyResult> &res, const std::vector<size_t> &idx) {
+  std::vector<Fr> sc; std::vector<halo2::G1Affine> pt; std::vector<uint64_t> off = {0};
+  for (size_t i : idx) { sc.insert(sc.end(), res[i].msm_scalars.begin(), res[i].msm_scalars.end()); pt.insert(pt.end(), res[i].msm_points.begin(), res[i].msm_points.end()); off.push_back(sc.size()); }
+  device_calls()++; const std::vector<halo2::G1Affine> sums = halo2::msm_g1_segmented(sc, pt, off);
+  for (size_t j = 0; j < idx.size(); j++) res[idx[j]].msm_result = sums[j];
+}
+}  // namespace vdetail
+
+inline std::vector<VerifyResult> verify_proofs(const std::vector<ProofInput> &in, const G2Pair &srs) {
+  std::vector<VerifyResult> res; std::vector<char> passed;
+  vdetail::host_parts(in, res, passed);
+  std::vector<size_t> idx;
+  for (size_t i = 0; i < in.size(); i++) if (passed[i]) { if (in[i].opt.host_only) vdetail::host_only_done(res[i]); else idx.push_back(i); }
+  if (idx.empty()) return res;
+  vdetail::msm_of_lists(res, idx);
+  std::vector<halo2::G1Affine> Pp;   // one group per surviving proof plus one per carried accumulator
+  for (size_t i : idx) { Pp.push_back(res[i].msm_result); Pp.push_back(res[i].w_prime); if (res[i].has_accumulator) { Pp.push_back(res[i].acc_lhs); Pp.push_back(res[i].acc_rhs); } }
+  const std::vector<uint32_t> flags = vdetail::pairing_groups(Pp, srs);
+  size_t g = 0;
+  for (size_t i : idx) { const size_t n = res[i].has_accumulator ? 2 : 1; res[i].pairing.assign(flags.begin() + g, flags.begin() + g + n); g += n; vdetail::judge(res[i]); }
+  return res;
+}
+
+// ------------------------------------------------------------------------------------------------ the accumulator the next layer's instances carry
+// plonk::aggregate restates PlonkSuccinctVerifier::verify + KzgAs::create_proof [EXT-recalled snark-verifier verifier/plonk.rs, pcs/kzg/accumulation.rs]: what the aggregator does
+// natively with the snarks of layer n before it proves layer n + 1.
+//   1  host parts and ONE segmented MSM as in verify_proofs; proof i yields (msm_result_i, W'_i), and a proof that carries an accumulator yields (acc_lhs, acc_rhs) AFTER it
+//   2  a fresh Poseidon transcript (no initial scalar; Poseidon also when a proof was read with the EVM transcript) absorbs lhs, rhs of every accumulator in list order; r = its challenge
+//   3  lhs = sum r^j lhs_j, rhs = sum r^j rhs_j (r^0 = 1): a second segmented MSM with two segments
+//   4  limbs: three 88-bit limbs per canonical coordinate, lhs.x, lhs.y, rhs.x, rhs.y -- the first twelve instances of the next layer, what host_part's decoder reads back
+//   5  with an SRS: one pairing group e(lhs, g2) e(rhs, -s_g2); failure "aggregate_pairing".  The proofs are judged TOGETHER here: proofs[i].pairing stays empty.
+// A proof that fails its host part fails the aggregation with that proof's error and its index in `detail` (the reference panics there); no device call is made then.
+// The order of the accumulators and the transcript of step 2 are recalled, not pinned by a fixture; the algebra is what the tests verify.
+struct AggregateResult {
+  bool ok = false; std::string error, detail; std::vector<VerifyResult> proofs; std::vector<std::pair<halo2::G1Affine, halo2::G1Affine>> accumulators;
+  Fr r{}; halo2::G1Affine lhs{}, rhs{}; std::array<Fr, 12> limbs{}; uint32_t pairing = 0;
+};
+namespace vdetail {
+inline bool g1_is_identity(const halo2::G1Affine &a) { bool z = true; for (auto w : a) z = z && w == 0; return z; }
+// step 1's list from results whose msm_result is filled
+inline std::vector<std::pair<halo2::G1Affine, halo2::G1Affine>> accumulators_of(const std::vector<VerifyResult> &proofs) {
+  std::vector<std::pair<halo2::G1Affine, halo2::G1Affine>> out;
+  for (const auto &p : proofs) { out.push_back({p.msm_result, p.w_prime}); if (p.has_accumulator) out.push_back({p.acc_lhs, p.acc_rhs}); }
+  return out;
+}
+// step 2; false with the named failure accumulator_identity in `out` (the transcript refuses the identity)
+inline bool aggregate_challenge(AggregateResult &out) {
+  Transcript T(TranscriptKind::Poseidon);
+  for (size_t j = 0; j < out.accumulators.size(); j++) {
+    const auto &a = out.accumulators[j];
+    if (g1_is_identity(a.first) || g1_is_identity(a.second)) { out.ok = false; out.error = "accumulator_identity"; out.detail = "accumulator " + std::to_string(j) + " holds the identity, which the transcript refuses"; return false; }
+    T.common_point(a.first); T.common_point(a.second);
+  }
+  out.r = T.squeeze_challenge();
+  return true;
+}
+// step 4: the inverse of host_part's limb decoder
+inline void accumulator_limbs(const halo2::G1Affine &lhs, const halo2::G1Affine &rhs, std::array<Fr, 12> &limbs) {
+  const halo2::G1Affine *pts[2] = {&lhs, &rhs};
+  for (int cidx = 0; cidx < 4; cidx++) {
+    zk::fe_t m; std::memcpy(&m, pts[cidx / 2]->data() + 4 * (cidx & 1), 32);
+    const zk::fe_t c = zk::Fq::to_canonical(m); uint64_t w[4]; std::memcpy(w, &c, 32);
+    const uint64_t lo[3] = {w[0], (w[1] >> 24) | (w[2] << 40), (w[2] >> 48) | (w[3] << 16)}, hi[3] = {w[1] & 0xffffffull, (w[2] >> 24) & 0xffffffull, w[3] >> 48};
+    for (int l = 0; l < 3; l++) { zk::fe_t v = zk::Fr::zero(); const uint64_t two[2] = {lo[l], hi[l]}; std::memcpy(&v, two, 16); limbs[3 * cidx + l] = h2d::from_fe(zk::Fr::from_canonical(v)); }
+  }
+}
+}  // namespace vdetail
+
+inline AggregateResult aggregate(const std::vector<ProofInput> &in, const G2Pair *srs /* nullptr: fold only, no pairing */) {
+  using halo2::G1Affine;
+  AggregateResult out;
+  if (in.empty()) { out.error = "no_proofs"; out.detail = "nothing to aggregate"; return out; }
+  std::vector<char> passed;
+  vdetail::host_parts(in, out.proofs, passed);
+  for (size_t i = 0; i < in.size(); i++) if (!passed[i]) { out.error = out.proofs[i].error; out.detail = "proof " + std::to_string(i) + ": " + out.proofs[i].detail; return out; }
+  std::vector<size_t> idx(in.size()); for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+  vdetail::msm_of_lists(out.proofs, idx);
+  for (auto &p : out.proofs) { p.ok = true; p.error = ""; p.detail = "aggregated: judged by the aggregate's pairing"; }
+  out.accumulators = vdetail::accumulators_of(out.proofs);
+  if (!vdetail::aggregate_challenge(out)) return out;
+  const size_t m = out.accumulators.size();
+  std::vector<Fr> sc(2 * m); std::vector<G1Affine> pt(2 * m);
+  Fr pw = fr_one();
+  for (size_t j = 0; j < m; j++) { sc[j] = sc[m + j] = pw; pt[j] = out.accumulators[j].first; pt[m + j] = out.accumulators[j].second; pw = fr_mul(pw, out.r); }
+  vdetail::device_calls()++; const std::vector<G1Affine> folded = halo2::msm_g1_segmented(sc, pt, {0, m, 2 * m});
+  out.lhs = folded[0]; out.rhs = folded[1];
+  vdetail::accumulator_limbs(out.lhs, out.rhs, out.limbs);
+  if (!srs) { out.ok = true; return out; }
+  out.pairing = vdetail::pairing_groups({out.lhs, out.rhs}, *srs)[0];
+  if (!out.pairing) { out.error = "aggregate_pairing"; out.detail = "the folded accumulator does not satisfy e(lhs, g2) e(rhs, -s_g2) == 1"; return out; }
+  out.ok = true;
+  return out;
+}
 }  // namespace plonk
 }  // namespace mi355zk

@@ -9,6 +9,7 @@
 #include "msm.hpp"
 #define ZK_G2_DEVICE_ONLY 1      // msm_g2.hpp needs the twist arithmetic of g2.hpp, not k_g2_mul (that kernel belongs to lib_aux.hip)
 #include "msm_g2.hpp"
+#include "msm_seg.hpp"           // after msm.hpp: the kernel loads its operands with load_affine
 #include "lib_common.hpp"
 
 namespace mi355 {
@@ -978,6 +979,44 @@ int mi355_msm_g1_adhoc_host(const void *bases_host, const void *scalars_host, ui
   g_last_devices = 1; g_last_exchange = "none";
   const fe_t *poly = sc;
   return msm_batch_impl(bs, &poly, 1, n, out_g1_host, nullptr);
+  });
+}
+// Many short MSMs in one launch (msm_seg.hpp: a wavefront per segment, no bucket pipeline).  The argument checks read host memory only and come before
+// the device is asked for; one upload per array, one launch, one download.
+int mi355_msm_g1_segmented_host(const void *bases_affine_host, const void *scalars_host, const uint64_t *offsets_host, uint32_t segments, void *out_g1affine_host) {
+  return guarded([&]() -> int {
+  if (segments > (1u << 20)) return fail(MI355_EBADARG, "msm_segmented: more than 2^20 segments");
+  uint64_t total = 0;
+  if (segments) {
+    if (!offsets_host || !out_g1affine_host) return fail(MI355_EBADARG, "msm_segmented: null pointer");
+    if (offsets_host[0] != 0) return fail(MI355_EBADARG, "msm_segmented: offsets[0] must be 0");
+    for (uint32_t s = 0; s < segments; s++) if (offsets_host[s + 1] < offsets_host[s]) return fail(MI355_EBADARG, "msm_segmented: offsets decrease at segment " + std::to_string(s));
+    total = offsets_host[segments];
+    if (total > (1ull << 24)) return fail(MI355_EBADARG, "msm_segmented: more than 2^24 terms (this entry point is for many SHORT segments)");
+    if (total && (!bases_affine_host || !scalars_host)) return fail(MI355_EBADARG, "msm_segmented: null pointer");
+  }
+  MsmGuard lk;
+  CHK(need_init());
+  if (segments == 0) return MI355_OK;
+  if (total == 0) { memset(out_g1affine_host, 0, (size_t)segments * sizeof(g1_affine_t)); return MI355_OK; }   // every segment empty: identities
+  CallTrace tr("msm_g1_segmented", total, 96.0);
+  hipStream_t s = g.stream;
+  fe_t *sc; g1_affine_t *bs, *out_dev; uint64_t *off;
+  CHK(ws_get("io.scalars", total * sizeof(fe_t), (void **)&sc)); CHK(ws_get("io.bases", total * sizeof(g1_affine_t), (void **)&bs));
+  CHK(ws_get("msmseg.offsets", ((size_t)segments + 1) * 8, (void **)&off)); CHK(ws_get("msmseg.out", (size_t)segments * sizeof(g1_affine_t), (void **)&out_dev));
+  HIPCHK(hipMemcpyAsync(sc, scalars_host, total * sizeof(fe_t), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(bs, bases_affine_host, total * sizeof(g1_affine_t), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(off, offsets_host, ((size_t)segments + 1) * 8, hipMemcpyHostToDevice, s));
+  {
+    Scope sp("msm_segmented", s);
+    hipLaunchKernelGGL(k_msm_g1_segmented, dim3(segments), dim3(SEGMSM_LANES), 0, s, (const g1_affine_t *)bs, (const fe_t *)sc, (const uint64_t *)off, out_dev);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(out_g1affine_host, out_dev, (size_t)segments * sizeof(g1_affine_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  resolve_spans();
+  { char buf[48]; snprintf(buf, sizeof buf, " segments=%u", segments); tr.done(buf); }
+  return MI355_OK;
   });
 }
 int mi355_g1_sum_host(const void *pts_host, uint64_t n, void *out_g1_host) {

@@ -522,7 +522,11 @@ def verify_proof(protocol, instances, proof: bytes, transcript: str | None = Non
     line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
     if out.returncode != 0 or line is None:
         raise Mi355Error(_capi.EBADARG, "verify_proof driver failed: " + (out.stdout + out.stderr)[-800:])
-    rec = json.loads(line)
+    return _verify_record(json.loads(line))
+
+
+def _verify_record(rec: dict) -> dict:
+    """a driver's VerifyResult line: hexadecimal field elements and coordinates -> integers"""
     h = lambda s: int(s, 16)
     rec["challenges"] = {k: h(v) for k, v in rec["challenges"].items()}
     rec["numerator_at_x"] = h(rec["numerator_at_x"])
@@ -532,6 +536,107 @@ def verify_proof(protocol, instances, proof: bytes, transcript: str | None = Non
         m[key] = (h(m[key][0]), h(m[key][1]))
     m["points"] = [(h(a), h(b)) for a, b in m["points"]]
     return rec
+
+
+def _run_verify_proofs(cases, mode, g2, s_g2, neg_s_g2, host_only, need_srs, timeout, extra=()):
+    """tests/cpp/test_verify_proofs over a manifest written from `cases` -> (per-proof records, the closing summary line)"""
+    import json, subprocess, tempfile
+    from . import build
+    exe = build.build_cpp("test_verify_proofs")
+    as_g2 = lambda q: q if isinstance(q, (bytes, bytearray)) else np.ascontiguousarray(q, dtype=np.uint64).tobytes()
+    with tempfile.TemporaryDirectory(prefix="mi355_verify_") as d:
+        def put(name, data):
+            path = os.path.join(d, name)
+            with open(path, "wb") as f:
+                f.write(data)
+            return path
+        man = {"proofs": []}
+        protocols = {}
+        for i, c in enumerate(cases):
+            c = dict(c)
+            protocol = c.pop("protocol")
+            if isinstance(protocol, dict):                       # one file per distinct dict: the driver parses each protocol file once
+                key = id(protocol)
+                if key not in protocols:
+                    protocols[key] = os.path.join(d, "protocol%d.json" % len(protocols))
+                    with open(protocols[key], "w") as f:
+                        json.dump(protocol, f, separators=(",", ":"))
+                protocol = protocols[key]
+            e = {"protocol": protocol, "proof": put("proof%d.bin" % i, bytes(c.pop("proof"))),
+                 "instances": put("instances%d.bin" % i, b"".join(int(v).to_bytes(32, "big") for v in c.pop("instances")))}
+            if c.get("transcript"):
+                e["transcript"] = c["transcript"]
+            if c.get("vk_bytes") is not None:
+                e["vk"] = put("vk%d.bin" % i, bytes(c["vk_bytes"]))
+            if c.get("preprocessed") is not None:
+                e["preprocessed"] = put("pre%d.bin" % i, np.ascontiguousarray(c["preprocessed"], dtype=np.uint64).tobytes())
+            if c.get("initial_state") is not None:
+                e["initial_state"] = "%x" % c["initial_state"]
+            if not c.get("check_accumulator", True):
+                e["no_accumulator"] = True
+            if c.get("accumulator"):
+                e["accumulator"] = True
+            unknown = set(c) - {"transcript", "vk_bytes", "preprocessed", "initial_state", "check_accumulator", "accumulator"}
+            assert not unknown, "verify_proofs: unknown keys %s in case %d" % (sorted(unknown), i)
+            man["proofs"].append(e)
+        if need_srs:
+            man["g2"] = put("g2.bin", as_g2(g2 if g2 is not None else g2_generator()))
+            assert (s_g2 is None) != (neg_s_g2 is None), "give s_g2 or neg_s_g2"
+            if s_g2 is not None:
+                man["s_g2"] = put("sg2.bin", as_g2(s_g2))
+            else:
+                man["neg_s_g2"] = put("nsg2.bin", as_g2(neg_s_g2))
+        path = os.path.join(d, "manifest.json")
+        with open(path, "w") as f:
+            json.dump(man, f)
+        args = [exe, "--manifest", path] + list(mode) + (["--host-only"] if host_only else []) + list(extra)
+        out = subprocess.run(args, capture_output=True, text=True, timeout=timeout)
+    lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    if out.returncode != 0 or not lines:
+        raise Mi355Error(_capi.EBADARG, "verify_proofs driver failed: " + (out.stdout + out.stderr)[-800:])
+    return [_verify_record(r) for r in lines[:-1]], lines[-1]
+
+
+def verify_proofs(cases, g2=None, s_g2=None, neg_s_g2=None, host_only: bool = False, one_by_one: bool = False, timeout: int = 600) -> list:
+    """plonk::verify_proofs (include/mi355zk_plonk_verify.hpp) through its compiled driver tests/cpp/test_verify_proofs.cpp: N proofs, ONE point decompression, ONE segmented
+    MSM, ONE pairing call.  cases: dictionaries with protocol (path or dict), instances, proof and verify_proof's per-proof keywords (transcript, vk_bytes, preprocessed,
+    initial_state, check_accumulator, accumulator); protocols and transcripts may differ.  g2 / s_g2 / neg_s_g2 / host_only as in verify_proof.  Returns verify_proof's record
+    per proof, each equal to what verify_proof gives for that proof alone; the last one carries "device_calls" (how many device calls the batch made).
+    one_by_one=True runs the unchanged verify_proof in a loop inside the same process instead."""
+    recs, summary = _run_verify_proofs(cases, ["--one-by-one"] if one_by_one else [], g2, s_g2, neg_s_g2, host_only, not host_only, timeout)
+    assert len(recs) == len(cases)
+    for r in recs:
+        r["device_calls"] = summary["device_calls"]
+    return recs
+
+
+def aggregate(cases, g2=None, s_g2=None, neg_s_g2=None, pairing: bool = True, host_only: bool = False, timeout: int = 600) -> dict:
+    """plonk::aggregate through the same driver (--aggregate): the KZG accumulators of the proofs -- (msm_result, W') of each, its carried accumulator after it -- folded with the
+    powers of a Poseidon transcript challenge into the accumulator the next layer's first twelve instances carry.  Returns ok, error, detail, proofs (records), accumulators
+    [((x, y), (x, y)), ...], r, lhs, rhs, limbs (12 integers below 2^88), pairing, device_calls.  pairing=False: fold only, no SRS.  host_only=True: no device; the lists'
+    sums come from the oracle and the result stops after r (lhs, rhs and limbs are zero)."""
+    recs, a = _run_verify_proofs(cases, ["--aggregate"], g2, s_g2, neg_s_g2, host_only, pairing and not host_only, timeout, extra=[] if pairing or host_only else ["--no-pairing"])
+    h = lambda s: int(s, 16)
+    pt = lambda p: (h(p[0]), h(p[1]))
+    a["proofs"] = recs
+    a["accumulators"] = [(pt(l), pt(r)) for l, r in a["accumulators"]]
+    a["r"] = h(a["r"]); a["lhs"] = pt(a["lhs"]); a["rhs"] = pt(a["rhs"]); a["limbs"] = [h(v) for v in a["limbs"]]
+    return a
+
+
+def msm_g1_segmented(bases, scalars, offsets) -> np.ndarray:
+    """mi355_msm_g1_segmented_host: out[s] = sum over [offsets[s], offsets[s + 1]) of scalars[i] * bases[i] -- MANY SHORT multi-scalar multiplications in one launch (a wavefront
+    per segment; the final MSMs of a batch of verifiers).  bases [n, 8] u64 G1Affine, scalars [n, 4] u64 Fr (Montgomery), offsets [segments + 1] (first 0, non-decreasing, last n)
+    -> [segments, 8] u64 G1Affine, identity = zeros.  A long segment is correct and slow: best_multiexp is the tool for those."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    assert offsets.shape[0] >= 1, "msm_g1_segmented: offsets holds segments + 1 values"
+    bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 8)
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    assert bases.shape[0] == scalars.shape[0] == int(offsets[-1]), "msm_g1_segmented: offsets[-1] != scalars.len() or bases.len()"
+    segments = offsets.shape[0] - 1
+    out = np.zeros((segments, 8), dtype=np.uint64)
+    check(lib().mi355_msm_g1_segmented_host(ptr(bases), ptr(scalars), ptr(offsets), segments, ptr(out)))
+    return out
 
 
 def g1_sum(points: np.ndarray) -> np.ndarray:
