@@ -320,6 +320,28 @@ int mi355_fr_nonzero_rows_dev(const void *const *vecs_dev, uint32_t batch, uint6
 int mi355_fr_copy_check_dev(const void *const *cols_dev, uint32_t n_cols, uint32_t log_n, const uint64_t *cells_host, const uint64_t *images_host, uint64_t count,
                             uint32_t cap, uint64_t *n_failed_out, uint64_t *failed_t_out_host);
 
+/* ---- the prover's randomness, drawn where the polynomials live (csrc/frrand.hpp): uniform field elements from ChaCha20 (RFC 8439 block function, 20 rounds).  One
+ * 64-byte block per element: state words 4..11 = key32 as eight little-endian words, words 12..13 = the 64-bit block counter, words 14..15 = the 64-bit stream
+ * identifier (with stream = 0 and a counter below 2^32: RFC 8439 with a zero nonce) [EXT-recalled: also the state layout of rand_chacha's ChaCha20Rng, whose block
+ * is the eight next_u64 words halo2curves' Fr::random consumes].  The block, read as a 512-bit little-endian integer, is reduced mod r
+ * [EXT-recalled halo2curves Fr::from_u512: d0 R^2 + d1 R^3 by two Montgomery products]; the word written is fully reduced, Montgomery form.  Every element is a pure
+ * function of (key, stream, counter): the result does not depend on the grid, on the device or on how a vector is cut into calls, and a caller can recompute it on
+ * the CPU (halo2::fr_random_reference).  Asynchronous on the library stream of the device that owns the destination; n == 0 / n_cols == 0 / rows == 0: MI355_OK, no
+ * launch.  MI355_EBADARG: a draw whose counters counter0 .. counter0 + count would wrap 2^64 (checked first: a stream must never repeat a block), a null or misaligned
+ * pointer, a range that leaves its mi355_buf block, columns on different devices.  No CPU path (MI355_ENODEVICE).  The key is passed to the kernel and nowhere else: it
+ * never appears in mi355_last_error(), in MI355_TRACE output or in a range name.  Choosing the key (an operating-system source in production) and never reusing a
+ * (key, stream, counter) triple across proofs is the caller's business.
+ *
+ * dst[i] = element(key32, stream, counter0 + i), i < n.                                                                                                              */
+int mi355_fr_random_dev(void *dst, uint64_t n, const uint8_t *key32, uint64_t stream, uint64_t counter0);
+/* cols: host array of n_cols device pointers; rows [row0, row0 + rows) of column c = element(key32, stream, counter0 + c * rows + j), j < rows: the blinding rows of a
+ * batch of columns in one launch.  Rows outside the range are not touched.  The call does not mark the columns' blocks as in use: a mi355_buf_upload into OTHER rows of a
+ * column is not ordered against it (and keeps its overlap with the compute stream); an upload into the SAME rows must wait for mi355_synchronize.                                                                                           */
+int mi355_fr_random_rows_dev(void *const *cols, uint32_t n_cols, uint64_t row0, uint32_t rows, const uint8_t *key32, uint64_t stream, uint64_t counter0);
+/* halo2curves' Fr::from_uniform_bytes over an array: src = n 64-byte little-endian integers, dst = n words, their residues mod r (Montgomery, fully reduced).  src and
+ * dst must not overlap.                                                                                                                                              */
+int mi355_fr_from_u512_dev(void *dst, const void *src, uint64_t n);
+
 /* ---- halo2_proofs::arithmetic::eval_polynomial(poly, point) = sum_i poly[i] * point^i  (the evaluations written to the
  *      transcript in step 9 of create_proof); out_fr_host receives 32 B.  First widening into SURVEY 8f-3.   */
 int mi355_eval_polynomial_dev(const void *poly_dev, uint64_t n, const void *point, void *out_fr_host);

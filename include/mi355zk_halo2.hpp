@@ -28,6 +28,7 @@
 
 #include "mi355zk.h"
 #include "../scroll-prover_amd/csrc/fp.hpp"
+#include "../scroll-prover_amd/csrc/frrand.hpp"   // the ChaCha20 block of the device randomness, compiled for the host (fr_random_reference)
 
 namespace mi355zk {
 namespace halo2 {
@@ -171,6 +172,7 @@ enum class SerdeFormat { RawBytes, Processed };
 // block back to the library's pool (no hipFree, no device synchronisation; work already queued on it stays valid).  `slot` picks the device of an
 // mi355_init_multi process.  create_proof uploads each witness column ONCE (from_host: the DMA overlaps whatever the device computes for other
 // threads) and then works on it through the `*_dev` entry points; host memory sees the 96-byte commitments and 32-byte evaluations only.
+using RngKey = std::array<uint8_t, 32>;   // a ChaCha20 key of the device randomness (mi355_fr_random_dev)
 struct DevicePoly {
   void *p = nullptr; uint64_t n = 0; int slot = 0;
   DevicePoly() = default;
@@ -186,7 +188,40 @@ struct DevicePoly {
   // element offset into the block: a device pointer like any other
   void *at(uint64_t i) const { return static_cast<char *>(p) + i * 32; }
   Fr eval(const Fr &point) const { Fr out; check(mi355_eval_polynomial_dev(p, n, point.data(), out.data())); return out; }
+  // fill with uniform field elements drawn on the device (mi355_fr_random_dev): element i = fr_random_reference(key, stream, counter0 + i).  What a loop of
+  // Fr::random over the caller's rng fills on CPU threads and uploads; asynchronous on the owner's stream.  Never reuse a (key, stream, counter) triple.
+  void random(const RngKey &key, uint64_t stream, uint64_t counter0 = 0) { check(mi355_fr_random_dev(p, n, key.data(), stream, counter0)); }
 };
+
+// ------------------------------------------------------------------------------------------------ ff::Field::random / Fr::from_uniform_bytes
+// rows [row0, row0 + rows) of every column drawn in ONE launch (mi355_fr_random_rows_dev): column c, row row0 + j = element counter0 + c * rows + j of the stream.
+// The columns live on one device; rows outside the range are not touched (the blinding rows of a batch of witness columns).
+inline void fr_random_rows(const std::vector<void *> &cols_dev, uint64_t row0, uint32_t rows, const RngKey &key, uint64_t stream, uint64_t counter0 = 0) {
+  check(mi355_fr_random_rows_dev(cols_dev.data(), (uint32_t)cols_dev.size(), row0, rows, key.data(), stream, counter0));
+}
+// Fr::from_uniform_bytes over an array on the device: src_dev = n 64-byte little-endian integers, dst_dev = n words (Montgomery, fully reduced)
+inline void fr_from_uniform_bytes_dev(void *dst_dev, const void *src_dev, uint64_t n) { check(mi355_fr_from_u512_dev(dst_dev, src_dev, n)); }
+// Fr::from_uniform_bytes on the host: 512-bit little-endian integer mod r, returned in Montgomery form (the transcripts' challenges; reduce-first, then REDUCED operands
+// into the multiplier -- deliberately not the device's two-product form)
+inline Fr fr_from_uniform_bytes(const std::array<uint8_t, 64> &b) {
+  auto reduce256 = [](const uint8_t *p) {
+    zk::fe_t a; std::memcpy(&a, p, 32);
+    uint32_t m[8]; for (int i = 0; i < 8; i++) m[i] = zk::FrP::mod(i);
+    while (zk::Fr::w_geq(a.l, m)) zk::Fr::w_sub(a.l, m);      // 2^256 < 6 r
+    return zk::Fr::from_canonical(a);
+  };
+  const zk::fe_t lo = reduce256(b.data()), hi = reduce256(b.data() + 32);
+  zk::fe_t r2; for (int i = 0; i < 8; i++) r2.l[i] = zk::FrP::r2(i);   // R^2 mod r as a Montgomery-form value IS (R mod r) = 2^256 mod r
+  return detail::from_fe(zk::Fr::add(lo, zk::Fr::mul(hi, r2)));
+}
+// the word the device writes for (key, stream, counter), computed on the host: the ChaCha20 block of csrc/frrand.hpp through fr_from_uniform_bytes.  For a caller's
+// checks and tests; NOT a fallback -- nothing in the library or in create_proof calls it.
+inline Fr fr_random_reference(const RngKey &key, uint64_t stream, uint64_t counter) {
+  zk::frrand_key_t k; std::memcpy(k.w, key.data(), 32);
+  uint32_t w[16]; zk::frrand_block(k, stream, counter, w);
+  std::array<uint8_t, 64> b; std::memcpy(b.data(), w, 64);
+  return fr_from_uniform_bytes(b);
+}
 
 
 // A host column whose storage is either ordinary memory or page-locked memory of the library (mi355_host_alloc): the choice is the caller's, per column

@@ -26,10 +26,12 @@
 // set; everything proportional to 2^k runs on the device.
 #pragma once
 #include <atomic>
+#include <cerrno>
 #include <cstdlib>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
+#include <sys/random.h>   // getrandom(2): ProofOptions::rng_key_from_os
 
 #include "mi355zk_plonk_circuit.hpp"
 #include "mi355zk_transcript.hpp"
@@ -567,6 +569,10 @@ struct ProofOptions { int devices = 1; int threads = 8; uint32_t commit_batch = 
                       bool multiplicity_rule_last = false /* with device_multiplicities: a repeated table value's count goes to its LAST usable row (default: the first) */;
                       bool check_witness = false /* run plonk::check_witness on the witness first and throw WitnessError (the failures, the first one named in the message) before anything is written to the
                                                     transcript.  The check does its own upload, so the witness crosses the link twice; sharing the prover's uploads is not done */;
+                      bool device_randomness = false /* the prover's randomness is drawn on the device from rng_key (mi355_fr_random_dev / _rows_dev, the stream table below): the random
+                                                        polynomial is not uploaded and Circuit::random_poly, m_blind, z_blind, phi_blind and the blinding rows of Circuit::advice / m are not read */;
+                      uint8_t rng_key[32] = {0} /* the ChaCha20 key of this proof's draws.  One key per proof: a (key, stream, counter) triple must never serve two proofs */;
+                      bool rng_key_from_os = false /* with device_randomness: the key is filled from getrandom(2) inside create_proof (rng_key is not read); a failure throws */;
                       TranscriptKind transcript = TranscriptKind::ByLayer /* the reference's choice for the protocol's layer (reference_transcript below): Poseidon for 0-5, Evm for 6; or name one */; };
 // the transcript the reference proves a layer with: Poseidon for every proof the next layer verifies in-circuit (layers 0-5, [REF integration/src/prove.rs:30-43,67,95-97] -> snark-verifier-sdk
 // gen_snark_shplonk), Keccak in the EVM layout for layer 6 (gen_evm_proof_shplonk: what the released verifier contract reads).  Files without a layer number are the reference's fixtures (layers 2, 4).
@@ -577,11 +583,21 @@ inline TranscriptKind reference_transcript(const Protocol &P) { return P.layer =
 // pinned key, which does not exist outside Rust): for those keys the scalar is a convention of this repository, the Blake2b hash of the .vkey bytes (vk_transcript_repr).
 inline Fr vk_transcript_scalar(const Protocol &P, const std::vector<uint8_t> &vk_bytes) { return P.has_initial_state ? P.initial_state : vk_transcript_repr(vk_bytes); }
 inline const char *transcript_name(TranscriptKind k) { return k == TranscriptKind::Poseidon ? "poseidon" : k == TranscriptKind::Evm ? "evm" : "blake2b"; }
+// The streams ProofOptions::device_randomness draws from.  Element (stream, block index) = halo2::fr_random_reference(rng_key, stream, block index); blind = Protocol::blind,
+// the rows u + 1 .. n - 1 of a column (j = row - u - 1).  A caller -- and every test -- can recompute each value on the CPU from the key alone.
+//   stream                     what                                                    block index
+//   RNG_STREAM_RANDOM_POLY  0  random polynomial of step 5, coefficient i              i
+//   RNG_STREAM_ADVICE_BLIND 1  advice column a (protocol order), blinding row j        a * blind + j
+//   RNG_STREAM_M_BLIND      2  multiplicity column of lookup l, blinding row j         l * blind + j
+//   RNG_STREAM_Z_BLIND      3  permutation product z of chunk c, blinding value j      c * blind + j
+//   RNG_STREAM_PHI_BLIND    4  lookup sum phi of lookup l, blinding value j            l * blind + j
+constexpr uint64_t RNG_STREAM_RANDOM_POLY = 0, RNG_STREAM_ADVICE_BLIND = 1, RNG_STREAM_M_BLIND = 2, RNG_STREAM_Z_BLIND = 3, RNG_STREAM_PHI_BLIND = 4;
 struct ProofResult {
   std::vector<uint8_t> proof;
   double step_ms[11] = {0}; double total_ms = 0;
   uint64_t peak_hbm_bytes = 0, hbm_total_bytes = 0;
   uint64_t sparse_columns = 0, packed_columns = 0, witness_link_bytes = 0;
+  double random_ms = 0;         // device_randomness: the random polynomial's block, its draw and the wait for it (an upper bound of the draw's device time), plus the host time of the blinding-row launches
   double multiplicity_ms = 0;   // device_multiplicities: compression, counting and blinding rows of every lookup (host wall time, the commitments excluded)
   uint32_t msm = 0, intt = 0, coset_ntt = 0, gate_launches = 0, evals = 0, plan_launches = 0, plan_terms = 0, plan_tmps = 0, plan_constraints = 0, plan_prefix_groups = 0, rotation_sets = 0;
 };
@@ -639,10 +655,24 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
   std::vector<std::pair<uint32_t, const Column *>> uploads;
   for (uint32_t i = 0; i < A; i++) uploads.push_back({P.phase0[0] + i, &wit.advice[i]});
   const bool dev_m = opt.device_multiplicities && NL > 0;
-  if (dev_m && wit.m_blind.size() != NL) throw std::invalid_argument("create_proof: device_multiplicities needs the blinding values of every multiplicity column (Circuit::m_blind)");
+  const bool dev_rng = opt.device_randomness;
+  halo2::RngKey rng_key; std::memcpy(rng_key.data(), opt.rng_key, 32);
+  if (dev_rng && opt.rng_key_from_os) {
+    for (size_t got = 0; got < 32;) { const ssize_t r = getrandom(rng_key.data() + got, 32 - got, 0); if (r < 0) { if (errno == EINTR) continue; throw Error(MI355_EHIP, "create_proof: getrandom failed (errno " + std::to_string(errno) + "): no key for the device randomness"); } got += (size_t)r; }
+  }
+  // rows [u + 1, n) of a group of resident columns (all on one device) in ONE launch; column i of the group draws the blocks (first + i) * blind + j of `stream`
+  auto draw_blinding = [&](const std::vector<void *> &cols, uint64_t stream, uint64_t first) {
+    if (!P.blind || cols.empty()) return;
+    const auto t0 = Clock::now();
+    halo2::fr_random_rows(cols, u + 1, P.blind, rng_key, stream, first * P.blind);
+    R.random_ms += ms_since(t0);
+  };
+  if (dev_rng) for (uint32_t i = 0; i < A; i++) if (wit.advice.at(i).size() < u + 1) throw std::invalid_argument("create_proof: advice column " + std::to_string(i) + " has fewer than the usable rows + 1");
+  if (dev_m && !dev_rng && wit.m_blind.size() != NL) throw std::invalid_argument("create_proof: device_multiplicities needs the blinding values of every multiplicity column (Circuit::m_blind)");
   if (!dev_m) for (uint32_t l = 0; l < NL; l++) uploads.push_back({P.phase0[1] + l, &wit.m[l]});
-  uploads.push_back({P.random_poly, &wit.random_poly});                                   // step 5's polynomial (coefficients): needed last, crosses last
+  if (!dev_rng) uploads.push_back({P.random_poly, &wit.random_poly});                     // step 5's polynomial (coefficients): needed last, crosses last
   for (const auto &up : uploads) poly[up.first];
+  poly[P.random_poly];
   poly[P.inst0];
   for (uint32_t l = 0; l < NL; l++) poly[P.phase0[1] + l];
   for (const auto &c : P.perm) poly[c.z];                                                 // every entry exists before the uploaders start: the map's structure does not change under them
@@ -654,8 +684,10 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
     try {
       std::vector<uint32_t> sidx; std::vector<Fr> svals;   // this worker's scratch for the sparse form
       for (size_t i = first; i < uploads.size(); i += UT) {
-        const uint64_t len = uploads[i].second->size();
-        DevicePoly d(len, 0);
+        // device_randomness: the block exists already and its rows [u + 1, n) are being drawn; rows [0, u + 1) cross the link.  The two regions are disjoint
+        const uint64_t len = dev_rng ? u + 1 : uploads[i].second->size();
+        if (uploads[i].second->size() < len) throw std::invalid_argument("create_proof: a witness column has fewer than the usable rows + 1");
+        DevicePoly d = dev_rng ? std::move(poly.at(uploads[i].first)) : DevicePoly(len, 0);
         uint64_t nz = len;
         if (opt.sparse_uploads && len >= (1u << 12) && uploads[i].first != P.random_poly) {
           sidx.resize(len); svals.resize(len);
@@ -665,8 +697,8 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
         if (opt.packed_multiplicities && is_m && wit.m_counts.size() == NL) {
           // a column whose KIND bounds its cells: counts below 2^32 on the rows up to l_last, then the prover's blinding values
           check(mi355_buf_upload_packed(d.p, wit.m_counts[uploads[i].first - P.phase0[1]].data(), len, 4));
-          if (P.blind) check(mi355_buf_upload(d.at(u + 1), uploads[i].second->data() + (u + 1), P.blind * 32));
-          packed_cols++; link_bytes += len * 4 + P.blind * 32;
+          if (P.blind && !dev_rng) check(mi355_buf_upload(d.at(u + 1), uploads[i].second->data() + (u + 1), P.blind * 32));
+          packed_cols++; link_bytes += len * 4 + (dev_rng ? 0 : P.blind * 32);
         }
         else if (2 * nz <= len) { check(mi355_buf_upload_sparse(d.p, len, sidx.data(), svals.data(), nz)); sparse_cols++; link_bytes += nz * 36; }
         else { check(mi355_buf_upload(d.p, uploads[i].second->data(), len * 32)); link_bytes += len * 32; }
@@ -682,6 +714,11 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
     DevicePoly inst(n, 0); check(mi355_buf_zero(inst.p, n * 32));
     if (!wit.instances.empty()) check(mi355_buf_upload(inst.p, wit.instances.data(), wit.instances.size() * 32));
     poly.at(P.inst0) = std::move(inst);
+  }
+  if (dev_rng) {                                                                        // the blocks of every uploaded column, their blinding rows drawn: one launch per kind of column
+    std::vector<void *> adv, ms;
+    for (size_t i = 0; i < uploads.size(); i++) { DevicePoly d(n, 0); (i < A ? adv : ms).push_back(d.p); poly.at(uploads[i].first) = std::move(d); }
+    draw_blinding(adv, RNG_STREAM_ADVICE_BLIND, 0); draw_blinding(ms, RNG_STREAM_M_BLIND, 0);
   }
   struct Joiner { std::vector<std::thread> th; void join() { for (auto &t : th) if (t.joinable()) t.join(); } ~Joiner() { join(); } } uploaders;
   for (size_t w = 0; w < UT; w++) uploaders.th.emplace_back(upload_worker, w);
@@ -734,10 +771,11 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
       const int rc = mi355_fr_lookup_multiplicities_dev(m.p, n, tmp_at(0).p, u, inputs, 1, u, opt.multiplicity_rule_last ? 1u : 0u, &missing);
       if (rc == MI355_EBADARG && missing != ~0ull) throw Error(MI355_EBADARG, "lookup " + std::to_string(l) + ": input row " + std::to_string(missing & ((uint64_t(1) << 40) - 1)) + " is not in the table");
       check(rc);
-      if (P.blind) check(mi355_buf_upload(m.at(u + 1), wit.m_blind[l].data(), P.blind * 32));
+      if (P.blind && !dev_rng) check(mi355_buf_upload(m.at(u + 1), wit.m_blind[l].data(), P.blind * 32));
       { std::lock_guard<std::mutex> lk_(mu); poly.at(P.phase0[1] + l) = std::move(m); }
       made.push_back(P.phase0[1] + l);
     }
+    if (dev_rng) { std::vector<void *> ms; for (uint32_t r : made) ms.push_back(poly.at(r).p); draw_blinding(ms, RNG_STREAM_M_BLIND, 0); }
     tmp.clear();
     R.multiplicity_ms = ms_since(t_m);
     std::vector<uint32_t> pending;
@@ -785,9 +823,10 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
       check(mi355_fr_prefix_product_dev(z.p, tmp_at(0).p, n, nullptr));                  // z[0] = 1, z[i + 1] = z[i] prod u / prod v
       if (c > 0) check(mi355_fr_vec_axpy_dev(z.p, nullptr, z.p, carry.data(), n));       // chunk c starts where chunk c - 1 ended: z_c(1) = z_(c-1)(w^last)
       if (c + 1 < NZ) check(mi355_buf_download(carry.data(), z.at(u), 32));
-      if (P.blind) check(mi355_buf_upload(z.at(u + 1), wit.z_blind.at(c).data(), P.blind * 32));
+      if (P.blind && !dev_rng) check(mi355_buf_upload(z.at(u + 1), wit.z_blind.at(c).data(), P.blind * 32));
       poly.at(chunk.z) = std::move(z);
     }
+    if (dev_rng) { std::vector<void *> zs; for (uint32_t c = 0; c < NZ; c++) zs.push_back(poly.at(P.perm[c].z).p); draw_blinding(zs, RNG_STREAM_Z_BLIND, 0); }
     for (uint32_t l = 0; l < NL; l++) {                                                 // phi[i + 1] = phi[i] + 1 / (I + beta) - m / (T + beta)
       const Lookup &lk = P.lookups[l];
       cmp.tmp_base = 4; cmp.tmp_next = 0;
@@ -802,9 +841,10 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
       check(mi355_fr_vec_op_dev(2, tmp_at(3).p, tmp_at(3).p, tmp_at(2).p, n));
       DevicePoly phi(n, 0);
       check(mi355_fr_prefix_sum_dev(phi.p, tmp_at(3).p, n, nullptr));
-      if (P.blind) check(mi355_buf_upload(phi.at(u + 1), wit.phi_blind.at(l).data(), P.blind * 32));
+      if (P.blind && !dev_rng) check(mi355_buf_upload(phi.at(u + 1), wit.phi_blind.at(l).data(), P.blind * 32));
       poly.at(lk.phi) = std::move(phi);
     }
+    if (dev_rng) { std::vector<void *> phis; for (uint32_t l = 0; l < NL; l++) phis.push_back(poly.at(P.lookups[l].phi).p); draw_blinding(phis, RNG_STREAM_PHI_BLIND, 0); }
     std::vector<uint32_t> made; for (uint32_t c = 0; c < NZ; c++) made.push_back(P.perm[c].z); for (uint32_t l = 0; l < NL; l++) made.push_back(P.lookups[l].phi);
     // small domains: one pass whatever the count (round 6: one reduction tail per batch); big ones keep one commitment per pass -- a batch of two at 2^24 doubles the sorter's
     // workspace (8.8 GB) for no gain, and a multi-layer prover process has no HBM to spare
@@ -813,8 +853,14 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
   }
   lap(4);
   // ---- step 5: the random polynomial of the vanishing argument: one commitment on the coefficient basis, one evaluation later, no transform
-  wait_for(uploads.size() - 1);
+  if (!uploads.empty()) wait_for(uploads.size() - 1);
   uploaders.join();
+  if (dev_rng) {                                                                        // drawn where it lives: nothing crosses the link.  Waited for, so that random_ms holds the draw
+    const auto t0 = Clock::now();                                                         // (with the block's allocation and whatever the stream still held; the commitment below waits anyway)
+    DevicePoly rp(n, 0); rp.random(rng_key, RNG_STREAM_RANDOM_POLY, 0); check(mi355_synchronize());
+    poly.at(P.random_poly) = std::move(rp);
+    R.random_ms += ms_since(t0);
+  }
   commit_one(h_g, poly.at(P.random_poly).p);
   for (uint32_t i = 0; i < P.num_challenge[2]; i++) ch.push_back(T.squeeze_challenge()); // y
   lap(5);

@@ -116,7 +116,11 @@ struct CircuitOptions { uint64_t seed = 1; int threads = 8; bool pinned = false;
                         // the PROVER's randomness, separable from the witness (in halo2 it comes from the rng handed to create_proof): blind_seed != 0 draws the blinding rows, the z / phi
                         // blinding values and the random polynomial from their own stream (same witness, other proof bytes); zero_blinding leaves the blinding rows and values zero -- a proof
                         // the verifier still accepts (it cannot see the choice; zero knowledge is what is lost).  tests/test_plonk_protocol.py::test_gpu_prover_invisible_choices
-                        uint64_t blind_seed = 0; bool zero_blinding = false; };
+                        uint64_t blind_seed = 0; bool zero_blinding = false;
+                        // the key a later create_proof with ProofOptions::device_randomness will draw from: the blinding rows of the advice columns are then the values the device
+                        // will write there (halo2::fr_random_reference, stream 1, block a * blind + j), so that an assigned gate whose P reads an earlier column across the
+                        // wrap-around is assigned against the rows the proof will hold.  Only the synthetic inner circuit has such gates; every other witness value is unchanged
+                        const uint8_t *device_rng_key = nullptr; };
 
 inline std::unique_ptr<Circuit> build_circuit(const Protocol &P, const CircuitOptions &opt) {
   using namespace detail;
@@ -257,6 +261,7 @@ inline std::unique_ptr<Circuit> build_circuit(const Protocol &P, const CircuitOp
   Rng blind_top(opt.blind_seed * 0xD1B54A32D192ED03ull + 777);
   auto blind_stream = [&]() { const uint64_t own = top.next(), other = blind_top.next(); return opt.blind_seed ? other : own; };   // `top` advances either way: the witness does not depend on blind_seed
   for (uint32_t a = 0; a < A; a++) { Rng g(blind_stream()); for (uint64_t r = u + 1; r < n; r++) C->advice[a][r] = opt.zero_blinding ? fr_zero() : g.uniform(); }
+  if (opt.device_rng_key) { halo2::RngKey key; std::memcpy(key.data(), opt.device_rng_key, 32); for (uint32_t a = 0; a < A; a++) for (uint64_t r = u + 1; r < n; r++) C->advice[a][r] = halo2::fr_random_reference(key, 1, (uint64_t)a * P.blind + (r - u - 1)); }
   std::set<uint32_t> assign_selectors;
   for (uint32_t a = 0; a < A; a++) if (role[a].kind == ASSIGN) {
     const Gate &g = *role[a].gate;

@@ -75,18 +75,8 @@ struct Blake2b {
   }
 };
 
-// Fr::from_uniform_bytes: 512-bit little-endian integer mod r, returned in Montgomery form
-inline halo2::Fr fr_from_uniform_bytes(const std::array<uint8_t, 64> &b) {
-  auto reduce256 = [](const uint8_t *p) {
-    zk::fe_t a; std::memcpy(&a, p, 32);
-    uint32_t m[8]; for (int i = 0; i < 8; i++) m[i] = zk::FrP::mod(i);
-    while (zk::Fr::w_geq(a.l, m)) zk::Fr::w_sub(a.l, m);      // 2^256 < 6 r
-    return zk::Fr::from_canonical(a);
-  };
-  const zk::fe_t lo = reduce256(b.data()), hi = reduce256(b.data() + 32);
-  zk::fe_t r2; for (int i = 0; i < 8; i++) r2.l[i] = zk::FrP::r2(i);   // R^2 mod r as a Montgomery-form value IS (R mod r) = 2^256 mod r
-  return halo2::detail::from_fe(zk::Fr::add(lo, zk::Fr::mul(hi, r2)));
-}
+// Fr::from_uniform_bytes (512-bit little-endian integer mod r, Montgomery form) lives in mi355zk_halo2.hpp
+using halo2::fr_from_uniform_bytes;
 
 // ---- Poseidon: parameters from the Grain LFSR (80-bit state: field type 1 (2 bits) | s-box 0 (4) | field bits 254 (12) | t (12) | R_F (10) | R_P (10) | thirty 1s; 160 warm-up
 // clocks; self-shrinking output), round constants by rejection sampling of 254-bit draws, the Cauchy matrix 1 / (x_i + y_j) from 2 t draws reduced mod r

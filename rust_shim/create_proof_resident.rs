@@ -115,6 +115,11 @@ pub fn lookup_running_sum(launches: &[Launch], operand: &dyn Fn(Atom) -> *const 
 /// on the coefficient basis, one evaluation in step 9, no transform.
 pub fn commit_random(g: &Arc<GpuBasis>, random_coeffs: &[Fr]) -> Option<(DevicePoly, G1)> { let d = DevicePoly::from_slice(random_coeffs, 0)?; let c = g.multiexp_dev(&d)?; Some((d, c)) }
 
+/// The same step with the coefficients drawn on the device (hpp: ProofOptions::device_randomness, stream RNG_STREAM_RANDOM_POLY): nothing crosses the link and no
+/// CPU thread calls `Fr::random`.  This is where the caller's `rng` seeds the device: `let mut key = [0u8; 32]; rng.fill_bytes(&mut key);` once per proof -- the
+/// blinding rows and blinding values of that proof draw from the other streams of the same key (stream table in mi355zk_plonk.hpp).
+pub fn commit_random_on_device(g: &Arc<GpuBasis>, n: usize, key: &[u8; 32]) -> Option<(DevicePoly, G1)> { let d = DevicePoly::random(n, 0, key, 0, 0)?; let c = g.multiexp_dev(&d)?; Some((d, c)) }
+
 /// R5 (hpp: step 6): every witness polynomial to coefficients in one batched call.
 pub fn all_to_coeff(polys: &mut [&mut DevicePoly], d: &Domain) -> bool { mi355zk::fft_many_dev(polys, d.k, &d.omega_inv, Some(&d.ifft_divisor)) }
 

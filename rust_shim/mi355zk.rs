@@ -104,6 +104,9 @@ extern "C" {
     pub fn mi355_fr_nonzero_rows_dev(vecs_dev: *const *const c_void, batch: u32, n: u64, cap: u32, counts_out_host: *mut u64, rows_out_host: *mut u64) -> c_int;
     pub fn mi355_fr_copy_check_dev(cols_dev: *const *const c_void, n_cols: u32, log_n: u32, cells_host: *const u64, images_host: *const u64, count: u64, cap: u32,
                                    n_failed_out: *mut u64, failed_t_out_host: *mut u64) -> c_int;
+    pub fn mi355_fr_random_dev(dst: *mut c_void, n: u64, key32: *const u8, stream: u64, counter0: u64) -> c_int;
+    pub fn mi355_fr_random_rows_dev(cols: *const *mut c_void, n_cols: u32, row0: u64, rows: u32, key32: *const u8, stream: u64, counter0: u64) -> c_int;
+    pub fn mi355_fr_from_u512_dev(dst: *mut c_void, src: *const c_void, n: u64) -> c_int;
     pub fn mi355_fr_kate_division_dev(dst_dev: *mut c_void, poly_dev: *const c_void, n: u64, z: *const c_void) -> c_int;
     pub fn mi355_eval_polynomial_batch_dev(polys_dev: *const *const c_void, batch: u32, n: u64, points: *const c_void, out_fr_host: *mut c_void) -> c_int;
     pub fn mi355_eval_polynomial_dev(poly_dev: *const c_void, n: u64, point: *const c_void, out_fr_host: *mut c_void) -> c_int;
@@ -246,6 +249,17 @@ impl DevicePoly {
         if unsafe { mi355_buf_alloc((n * 32) as u64, slot, &mut p) } != MI355_OK { return None; }
         let d = DevicePoly { ptr: p, len: n, slot };
         if unsafe { mi355_buf_upload_packed(d.ptr, values_le.as_ptr() as *const c_void, n as u64, width) } != MI355_OK { return None; }
+        Some(d)
+    }
+    /// `len` uniform field elements drawn on the device: element i = from_u512(ChaCha20 block (key, stream, counter0 + i)) -- what a loop of `Fr::random(&mut rng)`
+    /// over a `ChaCha20Rng` fills on CPU threads and then uploads (the random polynomial of create_proof's step 5; `plonk::RNG_STREAM_*` in mi355zk_plonk.hpp names
+    /// the streams the device prover draws from).  The caller owns the key: seed it from its own `rng` once per proof and never reuse a (key, stream, counter) triple.
+    pub fn random(len: usize, slot: c_int, key: &[u8; 32], stream: u64, counter0: u64) -> Option<DevicePoly> {
+        if !available() || len == 0 { return None; }
+        let mut p: *mut c_void = std::ptr::null_mut();
+        if unsafe { mi355_buf_alloc((len * 32) as u64, slot, &mut p) } != MI355_OK { return None; }
+        let d = DevicePoly { ptr: p, len, slot };
+        if unsafe { mi355_fr_random_dev(d.ptr, len as u64, key.as_ptr(), stream, counter0) } != MI355_OK { return None; }
         Some(d)
     }
     pub fn len(&self) -> usize { self.len }

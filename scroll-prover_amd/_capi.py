@@ -94,6 +94,9 @@ SIGNATURES = {
     "mi355_fr_permutation_sigma_dev": (_int, [C.POINTER(_vp), _u32, _u32, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64), _u64, _u32]),
     "mi355_fr_nonzero_rows_dev": (_int, [C.POINTER(_vp), _u32, _u64, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "mi355_fr_copy_check_dev": (_int, [C.POINTER(_vp), _u32, _u32, C.POINTER(_u64), C.POINTER(_u64), _u64, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
+    "mi355_fr_random_dev": (_int, [_vp, _u64, _vp, _u64, _u64]),
+    "mi355_fr_random_rows_dev": (_int, [C.POINTER(_vp), _u32, _u64, _u32, _vp, _u64, _u64]),
+    "mi355_fr_from_u512_dev": (_int, [_vp, _vp, _u64]),
     "mi355_eval_polynomial_dev": (_int, [_vp, _u64, _vp, _vp]),
     "mi355_eval_polynomial_batch_dev": (_int, [C.POINTER(_vp), _u32, _u64, _vp, _vp]),
     "mi355_eval_polynomial_host": (_int, [_vp, _u64, _vp, _vp]),

@@ -1,8 +1,8 @@
 // lib_aux.hip -- libmi355zk.so, the translation unit of the kernels either side of MSM / NTT: the DFT over G1 points
 // (g1fft.hpp: g_to_lagrange, ParamsKZG::downsize), the multiplicative scans of the permutation / lookup arguments and kate_division
 // (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), the multiplicities of the mv-lookup argument
-// (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), the compressed-point codec of G1 (g1codec.hpp), and the two reductions of the witness
-// check (check.hpp).  Host logic only.
+// (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), the compressed-point codec of G1 (g1codec.hpp), the two reductions of the witness
+// check (check.hpp), and the prover's randomness (frrand.hpp).  Host logic only.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #include "g1fft.hpp"
 #include "frscan.hpp"
@@ -11,6 +11,7 @@
 #include "perm.hpp"
 #include "g1codec.hpp"
 #include "check.hpp"
+#include "frrand.hpp"
 #include "lib_common.hpp"
 #include <thread>
 
@@ -648,6 +649,91 @@ int mi355_fr_copy_check_dev(const void *const *cols_dev, uint32_t n_cols, uint32
   }();
   (void)mi355_buf_free(ws);
   if (rc != MI355_OK) return rc;
+  return finish_async();
+  });
+}
+
+// ---- the prover's randomness (frrand.hpp): ChaCha20 blocks reduced to Fr.  Asynchronous on the library stream of the device that owns the destination.  The key is a
+// kernel argument and nothing else: it is never copied into an error text, a trace line or a range name.  A draw whose block counters would wrap 2^64 is refused before
+// the device is looked at: a (key, stream) pair must never repeat a block.  Grid: grid-stride over at most 8 workgroups per CU; MI355_FR_RANDOM_BLOCKS overrides the
+// workgroup count (tests make every lane loop; the result must not depend on it).
+static uint32_t frrand_grid(uint64_t n) {
+  uint64_t blocks = std::min<uint64_t>(ceil_div(n, FRRAND_THREADS), (uint64_t)g.prop.multiProcessorCount * 8);
+  if (const char *e = getenv("MI355_FR_RANDOM_BLOCKS")) { const long v = atol(e); if (v > 0) blocks = std::min<uint64_t>((uint64_t)v, 65535u * 4); }
+  return (uint32_t)std::max<uint64_t>(1, blocks);
+}
+static frrand_key_t frrand_key(const uint8_t *key32) { frrand_key_t k; memcpy(k.w, key32, 32); return k; }   // little-endian host: bytes -> words
+int mi355_fr_random_dev(void *dst, uint64_t n, const uint8_t *key32, uint64_t stream, uint64_t counter0) {
+  return guarded([&]() -> int {
+  if (counter0 + n < counter0) return fail(MI355_EBADARG, "fr_random: counter0 + n wraps 2^64 (a stream must never repeat a block)");
+  int slot; CHK(common_slot({dst}, &slot, "fr_random")); DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (n == 0) return MI355_OK;
+  if (!dst || !key32) return fail(MI355_EBADARG, "fr_random: null pointer");
+  if (n >= (1ull << 40)) return fail(MI355_EBADARG, "fr_random: n too large");
+  if ((uintptr_t)dst & 15) return fail(MI355_EBADARG, "fr_random: device pointers must be 16-byte aligned");
+  CHK(buf_check_range(dst, n * sizeof(fe_t), "fr_random"));
+  Scope sc("fr_random");
+  hipLaunchKernelGGL(k_fr_random, dim3(frrand_grid(n)), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *)dst, n, frrand_key(key32), stream, counter0);
+  sc.close();
+  HIPCHK(hipGetLastError());
+  return finish_async();
+  });
+}
+int mi355_fr_random_rows_dev(void *const *cols, uint32_t n_cols, uint64_t row0, uint32_t rows, const uint8_t *key32, uint64_t stream, uint64_t counter0) {
+  return guarded([&]() -> int {
+  const uint64_t total = (uint64_t)n_cols * rows;
+  if (counter0 + total < counter0) return fail(MI355_EBADARG, "fr_random_rows: counter0 + n_cols * rows wraps 2^64 (a stream must never repeat a block)");
+  // the columns are looked up WITHOUT marking their blocks as in use: a witness upload into the other rows of a column (create_proof: rows [0, u + 1) cross the link while
+  // rows [u + 1, n) are drawn) then keeps its fresh-block ordering instead of waiting for everything queued on the compute stream.  Disjoint rows need no order; calls
+  // queued afterwards on the compute stream see both.
+  int slot = -1;
+  for (uint32_t c = 0; cols && c < n_cols; c++) {
+    if (!cols[c]) continue;
+    const int s2 = slot_of(cols[c], false);
+    if (slot < 0) slot = s2;
+    else if (s2 != slot && g_ctx[s2].device != g_ctx[slot].device) return fail(MI355_EBADARG, "fr_random_rows: the columns live on different devices");
+  }
+  if (slot < 0) slot = 0;
+  DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (total == 0) return MI355_OK;
+  if (!cols || !key32) return fail(MI355_EBADARG, "fr_random_rows: null pointer");
+  if (row0 >= (1ull << 40)) return fail(MI355_EBADARG, "fr_random_rows: row0 too large");
+  for (uint32_t c = 0; c < n_cols; c++) {
+    if (!cols[c]) return fail(MI355_EBADARG, "fr_random_rows: null column " + std::to_string(c));
+    if ((uintptr_t)cols[c] & 15) return fail(MI355_EBADARG, "fr_random_rows: device pointers must be 16-byte aligned");
+    CHK(buf_check_range(cols[c], (row0 + rows) * sizeof(fe_t), "fr_random_rows"));
+  }
+  void *ws = nullptr; CHK(mi355_buf_alloc(stage_class((uint64_t)n_cols * 8), slot, &ws));
+  int rc = mi355_buf_upload(ws, cols, (uint64_t)n_cols * 8);
+  if (rc == MI355_OK) rc = need_init(slot);
+  if (rc == MI355_OK) {
+    Scope sc("fr_random");
+    hipLaunchKernelGGL(k_fr_random_rows, dim3(frrand_grid(total)), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *const *)ws, n_cols, row0, rows, frrand_key(key32), stream, counter0);
+    sc.close();
+    if (hipGetLastError() != hipSuccess) rc = fail(MI355_EHIP, "fr_random_rows: kernel launch failed");
+  }
+  (void)mi355_buf_free(ws);   // back to the pool; its reuse waits for the kernel queued above
+  if (rc != MI355_OK) return rc;
+  return finish_async();
+  });
+}
+// Fr::from_uniform_bytes over an array: src 64-byte little-endian integers, dst their residues mod r as Montgomery words
+int mi355_fr_from_u512_dev(void *dst, const void *src, uint64_t n) {
+  return guarded([&]() -> int {
+  int slot; CHK(common_slot({dst, src}, &slot, "fr_from_u512")); DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (n == 0) return MI355_OK;
+  if (!dst || !src) return fail(MI355_EBADARG, "fr_from_u512: null pointer");
+  if (n >= (1ull << 40)) return fail(MI355_EBADARG, "fr_from_u512: n too large");
+  if (((uintptr_t)dst | (uintptr_t)src) & 15) return fail(MI355_EBADARG, "fr_from_u512: device pointers must be 16-byte aligned");
+  if (ranges_overlap(src, n * 64, dst, n * sizeof(fe_t))) return fail(MI355_EBADARG, "fr_from_u512: input and output must not overlap");
+  CHK(buf_check_range(dst, n * sizeof(fe_t), "fr_from_u512"));
+  Scope sc("fr_from_u512");
+  hipLaunchKernelGGL(k_fr_from_u512, dim3(frrand_grid(n)), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *)dst, (const uint4 *)src, n);
+  sc.close();
+  HIPCHK(hipGetLastError());
   return finish_async();
   });
 }

@@ -411,6 +411,46 @@ def copy_check(cols, cells, images, cap: int = 16):
     return int(n_failed.value), failed
 
 
+def _key_buf(key: bytes):
+    assert isinstance(key, (bytes, bytearray)) and len(key) == 32, "a ChaCha20 key is 32 bytes"
+    return (C.c_uint8 * 32).from_buffer_copy(bytes(key))
+
+
+def fr_random(dst, key: bytes, stream: int, counter0: int = 0, n: int | None = None):
+    """uniform field elements drawn on the device (mi355_fr_random_dev): word i of the device tensor `dst` (n words; default: all of it) = from_u512 of the ChaCha20
+    block (key, stream, counter0 + i).  A pure function of its arguments: the same words whatever the grid, the device, or how a vector is cut into calls.
+    Asynchronous on the library stream.  A draw that would wrap the 64-bit block counter raises Mi355Error (EBADARG)."""
+    if n is None:
+        n = dst.numel() * dst.element_size() // 32
+    assert n * 32 <= dst.numel() * dst.element_size(), "fr_random: more words than the tensor holds"
+    check(lib().mi355_fr_random_dev(ptr(dst), n, _key_buf(key), stream, counter0))
+    return dst
+
+
+def fr_random_rows(cols, row0: int, rows: int, key: bytes, stream: int, counter0: int = 0):
+    """rows [row0, row0 + rows) of every device tensor of `cols` in one launch (mi355_fr_random_rows_dev): column c, row row0 + j = element counter0 + c * rows + j
+    of the stream.  The other rows are not touched (the blinding rows of a batch of witness columns)."""
+    cols = list(cols)
+    for t in cols:
+        assert (row0 + rows) * 32 <= t.numel() * t.element_size(), "fr_random_rows: the rows leave a column"
+    arr = (C.c_void_p * max(1, len(cols)))(*[t.data_ptr() for t in cols])
+    check(lib().mi355_fr_random_rows_dev(arr, len(cols), row0, rows, _key_buf(key), stream, counter0))
+    return cols
+
+
+def fr_from_u512(src, dst=None):
+    """halo2curves' Fr::from_uniform_bytes over an array on the device (mi355_fr_from_u512_dev): `src` is a device tensor of n 64-byte little-endian integers;
+    returns (or fills `dst` with) their residues mod r as n Montgomery words [n, 4] int64."""
+    n = src.numel() * src.element_size() // 64
+    assert n * 64 == src.numel() * src.element_size(), "fr_from_u512: the input is not a whole number of 64-byte words"
+    if dst is None:
+        import torch
+        dst = torch.empty((n, 4), dtype=torch.int64, device=src.device)
+    assert dst.numel() * dst.element_size() == 32 * n, "fr_from_u512: the output is not n words"
+    check(lib().mi355_fr_from_u512_dev(ptr(dst), ptr(src), n))
+    return dst
+
+
 # halo2curves bn256 G2 generator (x.c0, x.c1, y.c0, y.c1) [EXT-recalled src/bn256/curve.rs]; the same four words are the first pairing
 # input of the released verifier [REF release-v0.13.1/evm_verifier.yul:1230-1233] (tests/test_oracle_golden.py)
 G2_GENERATOR = (0x1800DEEF121F1E76426A00665E5C4479674322D4F75EDADD46DEBD5CD992F6ED, 0x198E9393920D483A7260BFB731FB5D25F1AA493335A9E71297E485B7AEF312C2,

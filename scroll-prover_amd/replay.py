@@ -167,3 +167,31 @@ def run_witness_check(layer: int, k: int | None = None, out_dir: str | None = No
             with open(p, "rb") as f:
                 rec[name] = f.read()
     return rec
+
+
+def run_device_randomness(layer: int, key: bytes, k: int | None = None, out_dir: str | None = None, args=(), env=None, timeout: int = 1800, protocol_file: str | None = None, **shape) -> dict:
+    """tests/cpp/test_device_randomness.cpp: one layer proven by the default route and, the witness's random fields emptied, with ProofOptions::device_randomness under
+    `key` (32 bytes).  Returns the program's record with `proof`, `proof_again` (the same key once more), `proof_off` (default route), `vk`, `instances` and, when asked
+    for, `proof_key2` ("--key2 HEX") and `proof_os1` / `proof_os2` ("--os-key"); the dumped inputs are in `out_dir`.  args: "--device-multiplicities", "--sparse-uploads",
+    "--check-witness", "--devices D", "--proofs N", "--builder-key"."""
+    from . import build
+    assert len(key) == 32
+    out_dir = out_dir or tempfile.mkdtemp(prefix=f"mi355_device_randomness_l{layer}_")
+    os.makedirs(out_dir, exist_ok=True)
+    proto = write_protocol(layer, out_dir, k, protocol_file, **shape)
+    e = dict(os.environ)
+    e.update(env or {})
+    t0 = time.perf_counter()
+    out = subprocess.run([build.build_cpp("test_device_randomness"), "--protocol", proto, "--out", out_dir, "--key", key.hex()] + list(args), capture_output=True, text=True, timeout=timeout, env=e)
+    line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
+    rec = {"layer": layer, "ok": False, "returncode": out.returncode, "out_dir": out_dir, "protocol_path": proto, "process_wall_s": time.perf_counter() - t0}
+    if out.returncode != 0 or line is None:
+        rec["error"] = (out.stdout + out.stderr)[-1200:]
+        return rec
+    rec.update(json.loads(line))
+    for name in ("proof", "proof_again", "proof_off", "proof_key2", "proof_os1", "proof_os2", "vk", "instances"):
+        p = os.path.join(out_dir, name + ".bin")
+        if os.path.exists(p):
+            with open(p, "rb") as f:
+                rec[name] = f.read()
+    return rec
