@@ -174,6 +174,20 @@ int mi355_msm_g1_adhoc_host(const void *bases_affine_host, const void *scalars_h
  * MI355_EBADARG (before the device is looked at): null pointers, offsets[0] != 0, decreasing offsets, segments > 2^20, more than 2^24 terms.  segments == 0 touches nothing.
  * Bases are not validated (the contract of mi355_msm_g1_adhoc_host).                                                                                                  */
 int mi355_msm_g1_segmented_host(const void *bases_affine_host, const void *scalars_host, const uint64_t *offsets_host, uint32_t segments, void *out_g1affine_host);
+/* MANY POSEIDON TRANSCRIPTS in one launch: the sponge of snark-verifier's PoseidonTranscript<NativeLoader> (T = 5, RATE = 4, R_F = 8, R_P = 60, x^5, Grain LFSR constants,
+ * initial state (2^64, 0, 0, 0, 0)) for every proof of a batch.  Serves gen_batch_proof [REF integration/src/prove.rs:67]: the aggregator's native succinct verifier reads every
+ * chunk snark through that transcript; on the verifier's side every absorbed word is known before the first squeeze and the squeeze positions are fixed by the protocol, so
+ * N proofs are N independent sponges with a known script (plonk::verify_proofs / plonk::aggregate with VerifyOptions::device_transcript).
+ * Job j is one fresh sponge: its words are words[word_offsets[j] .. word_offsets[j+1]) (Fr, 32 B Montgomery, fully reduced), its squeeze positions
+ * squeeze_at[squeeze_offsets[j] .. squeeze_offsets[j+1]) (non-decreasing, relative to the job's first word, each <= the job's length), and its challenges land at
+ * challenges_out[squeeze_offsets[j] ..), 32 B each, Montgomery.  Challenge k of a job = squeeze() after update(words[.. squeeze_at[k]) not yet absorbed); words behind the last
+ * squeeze are not hashed; a job without squeezes writes nothing.  The constants are the library's own (generated and checked once per process); the caller passes none.
+ * One lane per job: the call costs one sponge's latency whatever `jobs` is.  Kernel time reports as "poseidon_transcripts" in mi355_profile_get.
+ * MI355_EBADARG (before the device is looked at, each with its own message): a null pointer; an offsets array that does not start at 0 or decreases; a squeeze position that
+ * decreases within a job or exceeds the job's length; more than 2^20 jobs, 2^24 words or 2^24 squeezes; a word that is not below r (the first such index is named).
+ * jobs == 0 launches nothing.  No CPU fallback (MI355_ENODEVICE).                                                                                                    */
+int mi355_poseidon_transcripts_host(const void *words_host, const uint64_t *word_offsets_host, const uint32_t *squeeze_at_host, const uint64_t *squeeze_offsets_host,
+                                    uint32_t jobs, void *challenges_out_host);
 /* sum of `n` G1 (Jacobian, any representative) points: the fold `results.iter().fold(identity, |a, b| a + b)` of
  * best_multiexp, used to combine per-GPU partial sums after the RCCL all-gather.                  */
 int mi355_g1_sum_host(const void *g1_points_host, uint64_t n, void *out_g1_host);

@@ -84,6 +84,17 @@ inline std::vector<G1Affine> msm_g1_segmented(const std::vector<Fr> &coeffs, con
   check(mi355_msm_g1_segmented_host(bases.data(), coeffs.data(), offsets.data(), (uint32_t)(offsets.size() - 1), out.data()));
   return out;
 }
+// many Poseidon transcripts in one launch (mi355_poseidon_transcripts_host): job j hashes words[word_offsets[j] .. word_offsets[j + 1]) and squeezes at the positions
+// squeeze_at[squeeze_offsets[j] .. squeeze_offsets[j + 1]) (relative to its first word); the challenges come back in the order of squeeze_at.  Both offset vectors have one
+// entry more than there are jobs.  The transcripts of a batch of verifiers (plonk::verify_proofs with VerifyOptions::device_transcript).
+inline std::vector<Fr> poseidon_transcripts(const std::vector<Fr> &words, const std::vector<uint64_t> &word_offsets, const std::vector<uint32_t> &squeeze_at,
+                                            const std::vector<uint64_t> &squeeze_offsets) {
+  if (word_offsets.empty() || word_offsets.size() != squeeze_offsets.size()) throw std::invalid_argument("poseidon_transcripts: both offset vectors hold jobs + 1 values");
+  if (word_offsets.back() != words.size() || squeeze_offsets.back() != squeeze_at.size()) throw std::invalid_argument("poseidon_transcripts: the offsets must end at words.len() and squeeze_at.len()");
+  std::vector<Fr> out(squeeze_at.size());
+  check(mi355_poseidon_transcripts_host(words.data(), word_offsets.data(), squeeze_at.data(), squeeze_offsets.data(), (uint32_t)(word_offsets.size() - 1), out.data()));
+  return out;
+}
 inline void best_fft(std::vector<Fr> &a, const Fr &omega, uint32_t log_n) {
   if (a.size() != (size_t(1) << log_n)) throw std::invalid_argument("best_fft: a.len() != 1 << log_n");
   check(mi355_ntt_fr_host(a.data(), log_n, omega.data()));

@@ -12,7 +12,10 @@
 // VerifyOptions::host_only stops after the list is built (points decompressed on the host): the verifier's own logic runs without a device.
 // plonk::verify_proofs runs the same host part for N proofs and ONE decompression, ONE segmented MSM and ONE pairing call for all of them; plonk::aggregate folds their
 // KZG accumulators into the one the next layer's first twelve instances carry (KzgAs).  Both stand further down, behind verify_proof.
+// VerifyOptions::device_transcript (off by default) moves the Poseidon transcripts of such a batch onto the device: the transcript section of every Poseidon proof is RECORDED
+// (its words and squeeze positions, nothing hashed), ONE mi355_poseidon_transcripts_host call hashes all of them, and the rest of the host part REPLAYS the challenges.
 #pragma once
+#include <chrono>
 #include "mi355zk_plonk_protocol.hpp"
 #include "mi355zk_transcript.hpp"
 
@@ -32,7 +35,13 @@ struct G2Pair {   // the two G2 points of the final check, as the pairing takes 
 struct VerifyingKeyRef {   // vk_bytes when not empty; else `preprocessed` when not empty; else the protocol file's own.  initial_state overrides the transcript's first scalar
   std::vector<uint8_t> vk_bytes; std::vector<halo2::G1Affine> preprocessed; bool has_initial_state = false; Fr initial_state{};
 };
-struct VerifyOptions { TranscriptKind transcript = TranscriptKind::ByLayer; bool check_accumulator = true; int accumulator = -1 /* -1: as the protocol says; 0 / 1: no / yes */; bool host_only = false; };
+struct VerifyOptions {
+  TranscriptKind transcript = TranscriptKind::ByLayer; bool check_accumulator = true; int accumulator = -1 /* -1: as the protocol says; 0 / 1: no / yes */; bool host_only = false;
+  // verify_proofs / aggregate: hash this proof's Poseidon transcript on the device, together with every other proof of the batch that asks for it (one more device call per
+  // batch).  Proofs read with the EVM or Blake2b transcript, and host_only ones, take the host path inside the same batch.  Every VerifyResult equals the one with the option off.
+  // verify_proof (one proof) IGNORES it: one sponge is a serial chain, and the host is the faster place for it.
+  bool device_transcript = false;
+};
 struct VerifyResult {
   bool ok = false; std::string error;                       // the name of the first failed check ("" when none); `detail` says more
   std::string detail;
@@ -74,6 +83,16 @@ inline Fr pow_rot(const Protocol &P, int32_t r) { return r >= 0 ? fr_pow(P.omega
 // Each returns false after it has written the named failure into `res`.
 inline bool failed(VerifyResult &res, const char *name, const std::string &why) { res.ok = false; res.error = name; res.detail = why; return false; }
 inline uint64_t &device_calls() { static uint64_t n = 0; return n; }   // how many C-ABI calls that need a device the verifiers of this header have made (the drivers print it)
+// where the wall time of verify_proofs / aggregate went, in milliseconds, summed over the calls since the caller last cleared it (the drivers' --bench prints it):
+// decode = layouts + the decompression call; record = the recording pass of device_transcript; transcript_call = mi355_poseidon_transcripts_host; host_part = the pass over
+// host_part (the scalar side, the SHPLONK list, the accumulator; with the transcript on the host its hashing as well); msm and pairing = those calls with their packing
+struct PhaseTimes { double decode = 0, record = 0, transcript_call = 0, host_part = 0, msm = 0, pairing = 0; };
+inline PhaseTimes &phase_times() { static PhaseTimes t; return t; }
+struct PhaseClock {
+  double &into; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  explicit PhaseClock(double &d) : into(d) {}
+  ~PhaseClock() { into += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
 struct Layout { TranscriptKind kind = TranscriptKind::Poseidon; size_t nb = 32, n_com = 0, n_ev = 0, vk0 = 0; bool use_vk = false; std::vector<halo2::G1Bytes> words; };
 inline bool layout_of(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<uint8_t> &proof, const VerifyOptions &opt, Layout &L, VerifyResult &res) {
   L.kind = opt.transcript == TranscriptKind::ByLayer ? (P.layer == 6 ? TranscriptKind::Evm : TranscriptKind::Poseidon) : opt.transcript;
@@ -110,12 +129,17 @@ inline void decode_words(const std::vector<halo2::G1Bytes> &words, std::vector<h
   }
 }
 // decoded: the L.words.size() points of THIS proof (its slice of a batch's decompression)
+// tape (Poseidon only): null = the transcript hashes on the host.  Otherwise pass = HostPass::Record runs the transcript section alone -- every absorbed word and every squeeze
+// position goes onto the tape, nothing is hashed, the section's named failures are reported as always -- and stops; pass = HostPass::Replay runs everything with the tape's
+// challenges in place of the sponge's.
+enum class HostPass { Whole, Record, Replay };
 inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const VerifyOptions &opt, const Layout &L,
-                      const halo2::G1Affine *decoded, VerifyResult &res) {
+                      const halo2::G1Affine *decoded, VerifyResult &res, TranscriptTape *tape = nullptr, HostPass pass = HostPass::Whole) {
   using halo2::G1Affine;
   auto failed = [&](const char *name, const std::string &why) { return vdetail::failed(res, name, why); };
   const TranscriptKind kind = L.kind; const bool use_vk = L.use_vk; const size_t nb = L.nb, n_ev = L.n_ev, vk0 = L.vk0;
   Transcript T(kind);
+  if (pass != HostPass::Whole) T.use_tape(pass == HostPass::Record ? Transcript::Mode::Record : Transcript::Mode::Replay, tape);
   std::vector<G1Affine> pre;
   if (use_vk) { for (uint32_t i = 0; i < P.num_pre; i++) { pre.push_back(decoded[vk0 + i]); bool z = true; for (auto w : pre.back()) z = z && w == 0; if (z) return failed("invalid_point", ".vkey commitment " + std::to_string(i) + " is no curve point"); } }
   else pre = vk.preprocessed.empty() ? P.preprocessed : vk.preprocessed;
@@ -158,6 +182,7 @@ inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::v
   if (!read_point(c_w, err)) return failed("invalid_point", err);
   if (pos != proof.size()) return failed("proof_length", "proof has " + std::to_string(proof.size()) + " bytes, the protocol reads " + std::to_string(pos));
   res.theta = ch[0]; res.beta = ch[1]; res.gamma = ch[2]; res.y = ch[3]; res.x = x; res.shplonk_y = ys; res.shplonk_v = v; res.shplonk_u = uu; res.w_prime = c_w;
+  if (pass == HostPass::Record) return true;   // the script is on the tape; the challenges above are placeholders until the replay
 
   // ---- scalar side
   const Fr one = fr_one();
@@ -250,6 +275,7 @@ inline void judge(VerifyResult &res) {
 }
 // `groups` pairing groups of (P[2 g], g2) (P[2 g + 1], -s_g2): one mi355_pairing_products_host call
 inline std::vector<uint32_t> pairing_groups(const std::vector<halo2::G1Affine> &Pp, const G2Pair &srs) {
+  PhaseClock pc(phase_times().pairing);
   const uint32_t groups = (uint32_t)(Pp.size() / 2);
   std::vector<uint8_t> Qq(256 * (size_t)groups);
   for (uint32_t g = 0; g < groups; g++) { std::memcpy(Qq.data() + 256 * (size_t)g, srs.g2.data(), 128); std::memcpy(Qq.data() + 256 * (size_t)g + 128, srs.neg_s_g2.data(), 128); }
@@ -259,6 +285,7 @@ inline std::vector<uint32_t> pairing_groups(const std::vector<halo2::G1Affine> &
 }
 }  // namespace vdetail
 
+// one proof: VerifyOptions::device_transcript is ignored here (one sponge is a serial chain; the host runs it faster than one lane does)
 inline VerifyResult verify_proof(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const G2Pair &srs, const VerifyOptions &opt) {
   using halo2::G1Affine;
   VerifyResult res; vdetail::Layout L;
@@ -291,20 +318,46 @@ inline void host_parts(const std::vector<ProofInput> &in, std::vector<VerifyResu
   const size_t N = in.size();
   res.assign(N, VerifyResult{}); passed.assign(N, 0);
   std::vector<Layout> L(N); std::vector<size_t> at(N, 0); std::vector<halo2::G1Bytes> words;
-  for (size_t i = 0; i < N; i++) {
-    if (!in[i].protocol || !in[i].vk) throw std::invalid_argument("verify_proofs: proof " + std::to_string(i) + " has no protocol or no key");
-    passed[i] = layout_of(*in[i].protocol, *in[i].vk, in[i].proof, in[i].opt, L[i], res[i]) ? 1 : 0;
-    if (passed[i] && !in[i].opt.host_only) { at[i] = words.size(); words.insert(words.end(), L[i].words.begin(), L[i].words.end()); }
+  std::vector<G1Affine> decoded;
+  {
+    PhaseClock pc(phase_times().decode);
+    for (size_t i = 0; i < N; i++) {
+      if (!in[i].protocol || !in[i].vk) throw std::invalid_argument("verify_proofs: proof " + std::to_string(i) + " has no protocol or no key");
+      passed[i] = layout_of(*in[i].protocol, *in[i].vk, in[i].proof, in[i].opt, L[i], res[i]) ? 1 : 0;
+      if (passed[i] && !in[i].opt.host_only) { at[i] = words.size(); words.insert(words.end(), L[i].words.begin(), L[i].words.end()); }
+    }
+    decode_words(words, decoded, false);
   }
-  std::vector<G1Affine> decoded; decode_words(words, decoded, false);
+  // device_transcript: record the script of every Poseidon proof that asks for it (a proof that fails here keeps its named failure and leaves the batch), hash all of them
+  // in ONE call, hand each tape its challenges.  No Poseidon proof left: no call.
+  std::vector<TranscriptTape> tapes(N); std::vector<size_t> dev;
+  {
+    PhaseClock pc(phase_times().record);
+    for (size_t i = 0; i < N; i++) {
+      if (!passed[i] || !in[i].opt.device_transcript || in[i].opt.host_only || L[i].kind != TranscriptKind::Poseidon) continue;
+      passed[i] = host_part(*in[i].protocol, *in[i].vk, in[i].instances, in[i].proof, in[i].opt, L[i], decoded.data() + at[i], res[i], &tapes[i], HostPass::Record) ? 1 : 0;
+      if (passed[i]) dev.push_back(i);
+    }
+  }
+  if (!dev.empty()) {
+    PhaseClock pc(phase_times().transcript_call);
+    std::vector<Fr> w; std::vector<uint32_t> sq; std::vector<uint64_t> woff = {0}, soff = {0};
+    for (size_t i : dev) { w.insert(w.end(), tapes[i].words.begin(), tapes[i].words.end()); sq.insert(sq.end(), tapes[i].squeeze_at.begin(), tapes[i].squeeze_at.end()); woff.push_back(w.size()); soff.push_back(sq.size()); }
+    device_calls()++; const std::vector<Fr> ch = halo2::poseidon_transcripts(w, woff, sq, soff);
+    for (size_t j = 0; j < dev.size(); j++) tapes[dev[j]].challenges.assign(ch.begin() + soff[j], ch.begin() + soff[j + 1]);
+  }
+  PhaseClock pc(phase_times().host_part);
   for (size_t i = 0; i < N; i++) {
     if (!passed[i]) continue;
     std::vector<G1Affine> own; if (in[i].opt.host_only) decode_words(L[i].words, own, true);
-    passed[i] = host_part(*in[i].protocol, *in[i].vk, in[i].instances, in[i].proof, in[i].opt, L[i], in[i].opt.host_only ? own.data() : decoded.data() + at[i], res[i]) ? 1 : 0;
+    const bool replay = std::find(dev.begin(), dev.end(), i) != dev.end();
+    passed[i] = host_part(*in[i].protocol, *in[i].vk, in[i].instances, in[i].proof, in[i].opt, L[i], in[i].opt.host_only ? own.data() : decoded.data() + at[i], res[i],
+                          replay ? &tapes[i] : nullptr, replay ? HostPass::Replay : HostPass::Whole) ? 1 : 0;
   }
 }
 // the lists of the proofs `idx` names, concatenated: one segmented MSM, the sums into msm_result
 inline void msm_of_lists(std::vector<VerifyResult> &res, const std::vector<size_t> &idx) {
+  PhaseClock pc(phase_times().msm);
   std::vector<Fr> sc; std::vector<halo2::G1Affine> pt; std::vector<uint64_t> off = {0};
   for (size_t i : idx) { sc.insert(sc.end(), res[i].msm_scalars.begin(), res[i].msm_scalars.end()); pt.insert(pt.end(), res[i].msm_points.begin(), res[i].msm_points.end()); off.push_back(sc.size()); }
   device_calls()++; const std::vector<halo2::G1Affine> sums = halo2::msm_g1_segmented(sc, pt, off);
@@ -332,6 +385,7 @@ inline std::vector<VerifyResult> verify_proofs(const std::vector<ProofInput> &in
 // natively with the snarks of layer n before it proves layer n + 1.
 //   1  host parts and ONE segmented MSM as in verify_proofs; proof i yields (msm_result_i, W'_i), and a proof that carries an accumulator yields (acc_lhs, acc_rhs) AFTER it
 //   2  a fresh Poseidon transcript (no initial scalar; Poseidon also when a proof was read with the EVM transcript) absorbs lhs, rhs of every accumulator in list order; r = its challenge
+//      (ONE sponge: it stays on the host whatever VerifyOptions::device_transcript says -- that option moves the N transcripts of step 1)
 //   3  lhs = sum r^j lhs_j, rhs = sum r^j rhs_j (r^0 = 1): a second segmented MSM with two segments
 //   4  limbs: three 88-bit limbs per canonical coordinate, lhs.x, lhs.y, rhs.x, rhs.y -- the first twelve instances of the next layer, what host_part's decoder reads back
 //   5  with an SRS: one pairing group e(lhs, g2) e(rhs, -s_g2); failure "aggregate_pairing".  The proofs are judged TOGETHER here: proofs[i].pairing stays empty.

@@ -15,6 +15,9 @@
 //            challenge = Keccak-256 of the buffer (plus one byte 0x01 when the buffer is exactly one word: a squeeze right after a squeeze) mod r; the hash is the new buffer.
 //            oracle/keccak.py + oracle/plonk.py EvmTranscript make the RELEASED BUNDLE PROOF verify (test_released_bundle_evm_proof_verifies); compared word for word as above.
 // All refuse the identity (halo2's common_point fails on it).
+// A Poseidon transcript on the verifier's side does not depend on its own challenges: every absorbed word is known before the first squeeze and the squeeze positions are fixed
+// by the protocol.  Transcript::Mode::Record therefore hashes nothing and writes the script of the sponge onto a TranscriptTape (the words, and the word count at each squeeze);
+// mi355_poseidon_transcripts_host runs the tapes of a whole batch in one launch; Mode::Replay hands the challenges back in order and absorbs nothing.
 // The GPU library sees none of this: 96-byte commitments and 32-byte evaluations arrive from the C-ABI and are hashed here, on the calling thread.
 #pragma once
 #include <cstring>
@@ -294,8 +297,20 @@ inline TranscriptKind transcript_kind_from_name(const std::string &s) {
   throw std::invalid_argument("transcript: blake2b, poseidon or evm expected, got " + s);
 }
 
+// the script of one Poseidon sponge and, once the device has run it, its answers: job j of mi355_poseidon_transcripts_host
+struct TranscriptTape { std::vector<halo2::Fr> words; std::vector<uint32_t> squeeze_at; std::vector<halo2::Fr> challenges; size_t next = 0; };
+
 struct Transcript {
   TranscriptKind kind;
+  enum class Mode { Hash /* the transcript itself */, Record /* Poseidon only: absorbed words and squeeze positions go onto the tape, challenges are zero */, Replay /* Poseidon only: challenges come from the tape */ };
+  Mode mode = Mode::Hash; TranscriptTape *tape = nullptr;
+  void use_tape(Mode m, TranscriptTape *t) {
+    if (kind != TranscriptKind::Poseidon || !t || m == Mode::Hash) throw std::invalid_argument("transcript: a tape records or replays a Poseidon transcript");
+    mode = m; tape = t;
+  }
+  void absorb(const halo2::Fr &w) {   // Poseidon
+    if (mode == Mode::Hash) sponge.update(w); else if (mode == Mode::Record) tape->words.push_back(w);
+  }
   Blake2b state{"Halo2-Transcript"};
   PoseidonSponge sponge;
   std::vector<uint8_t> evm_buf;                                 // Evm: the words waiting for the next Keccak
@@ -303,7 +318,11 @@ struct Transcript {
   explicit Transcript(TranscriptKind k = TranscriptKind::Blake2b) : kind(k) { if (k == TranscriptKind::ByLayer) throw std::invalid_argument("transcript: ByLayer must be resolved with reference_transcript(protocol) first"); }
   static void be32(const zk::fe_t &canonical, uint8_t out[32]) { const uint8_t *le = reinterpret_cast<const uint8_t *>(&canonical); for (int i = 0; i < 32; i++) out[i] = le[31 - i]; }
   halo2::Fr squeeze_challenge() {
-    if (kind == TranscriptKind::Poseidon) return sponge.squeeze();
+    if (kind == TranscriptKind::Poseidon) {
+      if (mode == Mode::Record) { tape->squeeze_at.push_back((uint32_t)tape->words.size()); return halo2::Fr{}; }
+      if (mode == Mode::Replay) { if (tape->next >= tape->challenges.size()) throw std::invalid_argument("transcript: the tape holds no challenge for this squeeze"); return tape->challenges[tape->next++]; }
+      return sponge.squeeze();
+    }
     if (kind == TranscriptKind::Evm) {
       if (evm_buf.size() == 32) evm_buf.push_back(1);
       const std::array<uint8_t, 32> h = keccak256(evm_buf);
@@ -316,7 +335,7 @@ struct Transcript {
     const uint8_t z = 0; state.update(&z, 1); return fr_from_uniform_bytes(state.digest());
   }
   void common_scalar(const halo2::Fr &s) {
-    if (kind == TranscriptKind::Poseidon) { sponge.update(s); return; }
+    if (kind == TranscriptKind::Poseidon) { absorb(s); return; }
     const zk::fe_t c = zk::Fr::to_canonical(halo2::detail::to_fe(s));
     if (kind == TranscriptKind::Evm) { uint8_t w[32]; be32(c, w); evm_buf.insert(evm_buf.end(), w, w + 32); return; }
     const uint8_t tag = 2; state.update(&tag, 1); state.update(&c, 32);
@@ -331,6 +350,7 @@ struct Transcript {
   void common_point(const halo2::G1Affine &a) {
     bool ident = true; for (auto w : a) ident = ident && w == 0;
     if (ident) throw std::invalid_argument("transcript: the identity has no coordinates (halo2's common_point fails on it)");
+    if (mode == Mode::Replay) return;   // the words were absorbed when the tape was recorded
     zk::fe_t x, y; std::memcpy(&x, a.data(), 32); std::memcpy(&y, a.data() + 4, 32);
     const zk::fe_t xc = zk::Fq::to_canonical(x), yc = zk::Fq::to_canonical(y);
     if (kind == TranscriptKind::Evm) { uint8_t w[64]; be32(xc, w); be32(yc, w + 32); evm_buf.insert(evm_buf.end(), w, w + 64); return; }
@@ -340,7 +360,7 @@ struct Transcript {
         while (zk::Fr::w_geq(c.l, m)) zk::Fr::w_sub(c.l, m);
         return halo2::detail::from_fe(zk::Fr::from_canonical(c));
       };
-      sponge.update(base_to_scalar(xc)); sponge.update(base_to_scalar(yc));
+      absorb(base_to_scalar(xc)); absorb(base_to_scalar(yc));
     } else {
       const uint8_t tag = 1; state.update(&tag, 1); state.update(&xc, 32); state.update(&yc, 32);
     }

@@ -51,6 +51,7 @@ extern "C" {
     pub fn mi355_msm_g1_batch_host(srs: u64, base_offset: u64, scalars_host: *const *const c_void, batch: u32, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g1_adhoc_host(bases: *const c_void, scalars: *const c_void, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g1_segmented_host(bases: *const c_void, scalars: *const c_void, offsets: *const u64, segments: u32, out_g1affine_host: *mut c_void) -> c_int;
+    pub fn mi355_poseidon_transcripts_host(words: *const c_void, word_offsets: *const u64, squeeze_at: *const u32, squeeze_offsets: *const u64, jobs: u32, challenges_out_host: *mut c_void) -> c_int;
     pub fn mi355_g1_batch_normalize_host(g1_points_host: *const c_void, affine_out_host: *mut c_void, n: u64) -> c_int;
     pub fn mi355_g1_decompress_dev(bytes_dev: *const c_void, affine_out_dev: *mut c_void, n: u64, first_bad_out: *mut u64) -> c_int;
     pub fn mi355_g1_decompress_host(bytes_host: *const c_void, affine_out_host: *mut c_void, n: u64, first_bad_out: *mut u64) -> c_int;

@@ -98,7 +98,7 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
 
 
-CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check", "test_verify_proof", "test_verify_proofs", "test_device_randomness")
+CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check", "test_verify_proof", "test_verify_proofs", "test_device_randomness", "test_device_transcripts")
 
 
 def build_cpp(name: str) -> str:

@@ -2,7 +2,7 @@
 // (g1fft.hpp: g_to_lagrange, ParamsKZG::downsize), the multiplicative scans of the permutation / lookup arguments and kate_division
 // (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), the multiplicities of the mv-lookup argument
 // (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), the compressed-point codec of G1 (g1codec.hpp), the two reductions of the witness
-// check (check.hpp), and the prover's randomness (frrand.hpp).  Host logic only.
+// check (check.hpp), the prover's randomness (frrand.hpp), and the Poseidon transcripts of a batch of verifiers (poseidon.hpp).  Host logic only.
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #include "g1fft.hpp"
 #include "frscan.hpp"
@@ -12,6 +12,7 @@
 #include "g1codec.hpp"
 #include "check.hpp"
 #include "frrand.hpp"
+#include "poseidon.hpp"
 #include "lib_common.hpp"
 #include <thread>
 
@@ -735,6 +736,71 @@ int mi355_fr_from_u512_dev(void *dst, const void *src, uint64_t n) {
   sc.close();
   HIPCHK(hipGetLastError());
   return finish_async();
+  });
+}
+
+// ---- many Poseidon transcripts in one launch (poseidon.hpp: one lane per job).  The argument checks read host memory only and come before the device is asked for; the
+// constants are the library's own (generated and checked once per process, uploaded once per device slot); one staging block, one launch, one download.
+int mi355_poseidon_transcripts_host(const void *words_host, const uint64_t *word_offsets_host, const uint32_t *squeeze_at_host, const uint64_t *squeeze_offsets_host,
+                                    uint32_t jobs, void *challenges_out_host) {
+  return guarded([&]() -> int {
+  if (jobs > (1u << 20)) return fail(MI355_EBADARG, "poseidon_transcripts: more than 2^20 jobs");
+  uint64_t n_words = 0, n_sq = 0;
+  if (jobs) {
+    if (!word_offsets_host || !squeeze_offsets_host) return fail(MI355_EBADARG, "poseidon_transcripts: null pointer");
+    if (word_offsets_host[0] != 0) return fail(MI355_EBADARG, "poseidon_transcripts: word_offsets[0] must be 0");
+    if (squeeze_offsets_host[0] != 0) return fail(MI355_EBADARG, "poseidon_transcripts: squeeze_offsets[0] must be 0");
+    for (uint32_t j = 0; j < jobs; j++) {
+      if (word_offsets_host[j + 1] < word_offsets_host[j]) return fail(MI355_EBADARG, "poseidon_transcripts: word_offsets decrease at job " + std::to_string(j));
+      if (squeeze_offsets_host[j + 1] < squeeze_offsets_host[j]) return fail(MI355_EBADARG, "poseidon_transcripts: squeeze_offsets decrease at job " + std::to_string(j));
+    }
+    n_words = word_offsets_host[jobs]; n_sq = squeeze_offsets_host[jobs];
+    if (n_words > (1ull << 24)) return fail(MI355_EBADARG, "poseidon_transcripts: more than 2^24 words");
+    if (n_sq > (1ull << 24)) return fail(MI355_EBADARG, "poseidon_transcripts: more than 2^24 squeezes");
+    if ((n_words && !words_host) || (n_sq && (!squeeze_at_host || !challenges_out_host))) return fail(MI355_EBADARG, "poseidon_transcripts: null pointer");
+    for (uint32_t j = 0; j < jobs; j++) {
+      const uint64_t len = word_offsets_host[j + 1] - word_offsets_host[j]; uint32_t prev = 0;
+      for (uint64_t q = squeeze_offsets_host[j]; q < squeeze_offsets_host[j + 1]; q++) {
+        const uint32_t p = squeeze_at_host[q];
+        if (p < prev) return fail(MI355_EBADARG, "poseidon_transcripts: squeeze positions decrease in job " + std::to_string(j) + " (squeeze " + std::to_string(q - squeeze_offsets_host[j]) + ")");
+        if (p > len) return fail(MI355_EBADARG, "poseidon_transcripts: squeeze position " + std::to_string(p) + " exceeds the " + std::to_string(len) + " words of job " + std::to_string(j));
+        prev = p;
+      }
+    }
+    uint32_t m[8]; for (int i = 0; i < 8; i++) m[i] = FrP::mod(i);
+    for (uint64_t i = 0; i < n_words; i++) if (Fr::w_geq(((const fe_t *)words_host)[i].l, m)) return fail(MI355_EBADARG, "poseidon_transcripts: word " + std::to_string(i) + " is not below r");
+  }
+  MsmGuard lk;
+  CHK(need_init());
+  if (jobs == 0 || n_sq == 0) return MI355_OK;   // nothing to squeeze: nothing is launched, nothing is written
+  CallTrace tr("poseidon_transcripts", n_words, 32.0);
+  hipStream_t s = g.stream;
+  bool fresh; { const auto it = g.ws.find("poseidon.tables"); fresh = it == g.ws.end() || !it->second.p; }   // shutdown clears the arena: the next call uploads again
+  fe_t *tab; CHK(ws_get("poseidon.tables", (size_t)POS_TABLE_WORDS * sizeof(fe_t), (void **)&tab));
+  if (fresh) {
+    const std::vector<fe_t> &t = poseidon_tables();
+    const hipError_t e = hipMemcpyAsync(tab, t.data(), t.size() * sizeof(fe_t), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { g.ws.erase("poseidon.tables"); (void)hipFree(tab); HIPCHK(e); }
+  }
+  auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
+  const uint64_t off_woff = al(n_words * sizeof(fe_t)), off_soff = off_woff + al(((uint64_t)jobs + 1) * 8), off_sq = off_soff + al(((uint64_t)jobs + 1) * 8),
+                 off_out = off_sq + al(n_sq * 4), bytes = off_out + al(n_sq * sizeof(fe_t));
+  char *dev; CHK(ws_get("io.poseidon", bytes, (void **)&dev));
+  if (n_words) HIPCHK(hipMemcpyAsync(dev, words_host, n_words * sizeof(fe_t), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dev + off_woff, word_offsets_host, ((size_t)jobs + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dev + off_soff, squeeze_offsets_host, ((size_t)jobs + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dev + off_sq, squeeze_at_host, n_sq * 4, hipMemcpyHostToDevice, s));
+  {
+    Scope sp("poseidon_transcripts", s);
+    hipLaunchKernelGGL(k_poseidon_transcripts, dim3(ceil_div(jobs, POS_LANES)), dim3(POS_LANES), 0, s, (const fe_t *)tab, (const fe_t *)dev, (const uint64_t *)(dev + off_woff),
+                       (const uint32_t *)(dev + off_sq), (const uint64_t *)(dev + off_soff), jobs, (fe_t *)(dev + off_out));
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(challenges_out_host, dev + off_out, n_sq * sizeof(fe_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  resolve_spans();
+  { char buf[64]; snprintf(buf, sizeof buf, " jobs=%u squeezes=%llu", jobs, (unsigned long long)n_sq); tr.done(buf); }
+  return MI355_OK;
   });
 }
 

@@ -578,11 +578,11 @@ def _verify_record(rec: dict) -> dict:
     return rec
 
 
-def _run_verify_proofs(cases, mode, g2, s_g2, neg_s_g2, host_only, need_srs, timeout, extra=()):
-    """tests/cpp/test_verify_proofs over a manifest written from `cases` -> (per-proof records, the closing summary line)"""
+def _run_verify_proofs(cases, mode, g2, s_g2, neg_s_g2, host_only, need_srs, timeout, extra=(), driver="test_verify_proofs", raw=False):
+    """tests/cpp/<driver> over a manifest written from `cases` -> (per-proof records, the closing summary line); raw: the records as the driver printed them"""
     import json, subprocess, tempfile
     from . import build
-    exe = build.build_cpp("test_verify_proofs")
+    exe = build.build_cpp(driver)
     as_g2 = lambda q: q if isinstance(q, (bytes, bytearray)) else np.ascontiguousarray(q, dtype=np.uint64).tobytes()
     with tempfile.TemporaryDirectory(prefix="mi355_verify_") as d:
         def put(name, data):
@@ -634,34 +634,56 @@ def _run_verify_proofs(cases, mode, g2, s_g2, neg_s_g2, host_only, need_srs, tim
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
     if out.returncode != 0 or not lines:
         raise Mi355Error(_capi.EBADARG, "verify_proofs driver failed: " + (out.stdout + out.stderr)[-800:])
-    return [_verify_record(r) for r in lines[:-1]], lines[-1]
+    return lines[:-1] if raw else [_verify_record(r) for r in lines[:-1]], lines[-1]
 
 
-def verify_proofs(cases, g2=None, s_g2=None, neg_s_g2=None, host_only: bool = False, one_by_one: bool = False, timeout: int = 600) -> list:
+def verify_proofs(cases, g2=None, s_g2=None, neg_s_g2=None, host_only: bool = False, one_by_one: bool = False, timeout: int = 600, device_transcript: bool = False,
+                  tile: int = 0) -> list:
     """plonk::verify_proofs (include/mi355zk_plonk_verify.hpp) through its compiled driver tests/cpp/test_verify_proofs.cpp: N proofs, ONE point decompression, ONE segmented
     MSM, ONE pairing call.  cases: dictionaries with protocol (path or dict), instances, proof and verify_proof's per-proof keywords (transcript, vk_bytes, preprocessed,
     initial_state, check_accumulator, accumulator); protocols and transcripts may differ.  g2 / s_g2 / neg_s_g2 / host_only as in verify_proof.  Returns verify_proof's record
     per proof, each equal to what verify_proof gives for that proof alone; the last one carries "device_calls" (how many device calls the batch made).
-    one_by_one=True runs the unchanged verify_proof in a loop inside the same process instead."""
-    recs, summary = _run_verify_proofs(cases, ["--one-by-one"] if one_by_one else [], g2, s_g2, neg_s_g2, host_only, not host_only, timeout)
-    assert len(recs) == len(cases)
+    one_by_one=True runs the unchanged verify_proof in a loop inside the same process instead.  device_transcript=True (VerifyOptions::device_transcript, through
+    tests/cpp/test_device_transcripts.cpp): the Poseidon transcripts of the batch are hashed by ONE mi355_poseidon_transcripts_host call -- one device call more, the same
+    records; it needs the device, so it excludes host_only and one_by_one.  tile=N: the driver repeats the cases cyclically up to N proofs (--tile)."""
+    extra = ["--tile", str(int(tile))] if tile else []
+    if device_transcript:
+        assert not host_only and not one_by_one, "verify_proofs: device_transcript needs the device and the batched call"
+        recs, summary = _run_verify_proofs(cases, [], g2, s_g2, neg_s_g2, False, True, timeout, extra=extra, driver="test_device_transcripts")
+    else:
+        recs, summary = _run_verify_proofs(cases, ["--one-by-one"] if one_by_one else [], g2, s_g2, neg_s_g2, host_only, not host_only, timeout, extra=extra)
+    assert len(recs) == (tile or len(cases))
     for r in recs:
         r["device_calls"] = summary["device_calls"]
     return recs
 
 
-def aggregate(cases, g2=None, s_g2=None, neg_s_g2=None, pairing: bool = True, host_only: bool = False, timeout: int = 600) -> dict:
+def aggregate(cases, g2=None, s_g2=None, neg_s_g2=None, pairing: bool = True, host_only: bool = False, timeout: int = 600, device_transcript: bool = False) -> dict:
     """plonk::aggregate through the same driver (--aggregate): the KZG accumulators of the proofs -- (msm_result, W') of each, its carried accumulator after it -- folded with the
     powers of a Poseidon transcript challenge into the accumulator the next layer's first twelve instances carry.  Returns ok, error, detail, proofs (records), accumulators
     [((x, y), (x, y)), ...], r, lhs, rhs, limbs (12 integers below 2^88), pairing, device_calls.  pairing=False: fold only, no SRS.  host_only=True: no device; the lists'
-    sums come from the oracle and the result stops after r (lhs, rhs and limbs are zero)."""
-    recs, a = _run_verify_proofs(cases, ["--aggregate"], g2, s_g2, neg_s_g2, host_only, pairing and not host_only, timeout, extra=[] if pairing or host_only else ["--no-pairing"])
+    sums come from the oracle and the result stops after r (lhs, rhs and limbs are zero).  device_transcript=True: the proofs' Poseidon transcripts are hashed on the device
+    (as in verify_proofs; the aggregation's own transcript, one sponge, stays on the host)."""
+    assert not (device_transcript and host_only), "aggregate: device_transcript needs the device"
+    recs, a = _run_verify_proofs(cases, ["--aggregate"], g2, s_g2, neg_s_g2, host_only, pairing and not host_only, timeout, extra=[] if pairing or host_only else ["--no-pairing"],
+                                 driver="test_device_transcripts" if device_transcript else "test_verify_proofs")
     h = lambda s: int(s, 16)
     pt = lambda p: (h(p[0]), h(p[1]))
     a["proofs"] = recs
     a["accumulators"] = [(pt(l), pt(r)) for l, r in a["accumulators"]]
     a["r"] = h(a["r"]); a["lhs"] = pt(a["lhs"]); a["rhs"] = pt(a["rhs"]); a["limbs"] = [h(v) for v in a["limbs"]]
     return a
+
+
+def record_transcripts(cases, timeout: int = 600) -> list:
+    """the recording pass of VerifyOptions::device_transcript alone (tests/cpp/test_device_transcripts --host-only; no device): per proof {"job", "error", "detail", "words",
+    "squeeze_at", "challenges"} -- the words its Poseidon transcript absorbs (integers), the word count at each squeeze and, from the host sponge, the challenges.
+    job is False, and the lists empty, for a proof that records none: another transcript (error ""), or a named failure of the transcript section (error = its name)."""
+    recs, summary = _run_verify_proofs(cases, [], None, None, None, True, False, timeout, driver="test_device_transcripts", raw=True)
+    assert len(recs) == len(cases) and summary["jobs"] == sum(r["job"] for r in recs)
+    for r in recs:
+        r["words"] = [int(v, 16) for v in r["words"]]; r["challenges"] = [int(v, 16) for v in r["challenges"]]
+    return recs
 
 
 def msm_g1_segmented(bases, scalars, offsets) -> np.ndarray:
@@ -676,6 +698,22 @@ def msm_g1_segmented(bases, scalars, offsets) -> np.ndarray:
     segments = offsets.shape[0] - 1
     out = np.zeros((segments, 8), dtype=np.uint64)
     check(lib().mi355_msm_g1_segmented_host(ptr(bases), ptr(scalars), ptr(offsets), segments, ptr(out)))
+    return out
+
+
+def poseidon_transcripts(words, word_offsets, squeeze_at, squeeze_offsets) -> np.ndarray:
+    """mi355_poseidon_transcripts_host: MANY Poseidon sponges (T = 5, RATE = 4, R_F = 8, R_P = 60: the transcript of snark-verifier's native loader) in one launch, a lane per
+    job.  words [n, 4] u64 Fr (Montgomery, below r); job j hashes words[word_offsets[j]:word_offsets[j + 1]] and squeezes at the positions
+    squeeze_at[squeeze_offsets[j]:squeeze_offsets[j + 1]] (non-decreasing, relative to the job's first word, at most its length) -> [squeezes, 4] u64 challenges in the order of
+    squeeze_at.  Challenge k of a job = Sponge.squeeze() after update(the words up to squeeze_at[k] not yet absorbed)."""
+    word_offsets = np.ascontiguousarray(word_offsets, dtype=np.uint64).reshape(-1)
+    squeeze_offsets = np.ascontiguousarray(squeeze_offsets, dtype=np.uint64).reshape(-1)
+    squeeze_at = np.ascontiguousarray(squeeze_at, dtype=np.uint32).reshape(-1)
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, 4)
+    assert word_offsets.shape[0] >= 1 and word_offsets.shape == squeeze_offsets.shape, "poseidon_transcripts: both offset arrays hold jobs + 1 values"
+    assert int(word_offsets[-1]) == words.shape[0] and int(squeeze_offsets[-1]) == squeeze_at.shape[0], "poseidon_transcripts: the offsets must end at len(words) and len(squeeze_at)"
+    out = np.zeros((squeeze_at.shape[0], 4), dtype=np.uint64)
+    check(lib().mi355_poseidon_transcripts_host(ptr(words), ptr(word_offsets), ptr(squeeze_at), ptr(squeeze_offsets), word_offsets.shape[0] - 1, ptr(out)))
     return out
 
 
