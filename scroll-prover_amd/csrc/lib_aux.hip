@@ -3,6 +3,9 @@
 // (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), the multiplicities of the mv-lookup argument
 // (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), the compressed-point codec of G1 (g1codec.hpp), the two reductions of the witness
 // check (check.hpp), the prover's randomness (frrand.hpp), and the Poseidon transcripts of a batch of verifiers (poseidon.hpp).  Host logic only.
+// The shape of an entry point: guarded([&] { slot + DevGuard; need_init; argument checks; WsLayout names the fields of the workspace; PoolBlock owns it; the body calls
+// HIPCHK / CHK and returns where it fails -- the block goes back to the pool on every path; finish_async() }).  The exception: mi355_buf_upload_packed / _sparse take no
+// DevGuard and do not call finish_async() -- like mi355_buf_upload, which they stand in for, they only queue (see "narrow uploads" below).
 // kernel headers first: lib_common.hpp defines the macro `g` (the calling thread's device context), a name the kernels use for locals
 #include "g1fft.hpp"
 #include "frscan.hpp"
@@ -76,17 +79,19 @@ int linrec_impl(const fe_t *src, fe_t *dst, uint64_t n, const fe_t &m, bool reve
   return MI355_OK;
 }
 
-// ---- G1 point codec (g1codec.hpp).  Grid: grid-stride over at most 16 workgroups per CU; MI355_G1_CODEC_BLOCKS overrides the workgroup count (tests run the
-// error reporting at two grid sizes; the result must not depend on it)
-static uint32_t g1codec_grid(uint64_t n) {
-  uint64_t blocks = std::min<uint64_t>(ceil_div(n, G1CODEC_THREADS), (uint64_t)g.prop.multiProcessorCount * 16);
-  if (const char *e = getenv("MI355_G1_CODEC_BLOCKS")) { const long v = atol(e); if (v > 0) blocks = std::min<uint64_t>((uint64_t)v, 65535u * 4); }
+// workgroups of a grid-stride launch over n elements: enough to cover them, at most per_cu_cap per compute unit of the bound device (0: no such cap) and 65535 x 4 in all;
+// a positive value of the environment variable env_override replaces the count (tests: the result of a grid-stride kernel must not depend on its grid)
+static uint32_t grid_blocks(uint64_t n, uint32_t threads, uint32_t per_cu_cap = 0, const char *env_override = nullptr) {
+  uint64_t blocks = std::min<uint64_t>(ceil_div(n, threads), per_cu_cap ? (uint64_t)g.prop.multiProcessorCount * per_cu_cap : 65535u * 4);
+  if (const char *e = env_override ? getenv(env_override) : nullptr) { const long v = atol(e); if (v > 0) blocks = std::min<uint64_t>((uint64_t)v, 65535u * 4); }
   return (uint32_t)std::max<uint64_t>(1, blocks);
 }
+// ---- G1 point codec (g1codec.hpp).  Grid: grid-stride over at most 16 workgroups per CU; MI355_G1_CODEC_BLOCKS overrides the workgroup count (tests run the
+// error reporting at two grid sizes; the result must not depend on it)
 int launch_g1_decompress(const void *bytes_dev, void *affine_out_dev, uint64_t n, uint64_t base, unsigned long long *err_dev) {
   if (!n) return MI355_OK;
   Scope sc("g1_decompress");
-  hipLaunchKernelGGL(k_g1_decompress, dim3(g1codec_grid(n)), dim3(G1CODEC_THREADS), 0, g.stream, (const uint4 *)bytes_dev, (uint4 *)affine_out_dev, n, base, err_dev);
+  hipLaunchKernelGGL(k_g1_decompress, dim3(grid_blocks(n, G1CODEC_THREADS, 16, "MI355_G1_CODEC_BLOCKS")), dim3(G1CODEC_THREADS), 0, g.stream, (const uint4 *)bytes_dev, (uint4 *)affine_out_dev, n, base, err_dev);
   sc.close();
   HIPCHK(hipGetLastError());
   return MI355_OK;
@@ -94,7 +99,7 @@ int launch_g1_decompress(const void *bytes_dev, void *affine_out_dev, uint64_t n
 static int launch_g1_compress(const void *affine_dev, void *bytes_out_dev, uint64_t n) {
   if (!n) return MI355_OK;
   Scope sc("g1_compress");
-  hipLaunchKernelGGL(k_g1_compress, dim3(g1codec_grid(n)), dim3(G1CODEC_THREADS), 0, g.stream, (const uint4 *)affine_dev, (uint4 *)bytes_out_dev, n);
+  hipLaunchKernelGGL(k_g1_compress, dim3(grid_blocks(n, G1CODEC_THREADS, 16, "MI355_G1_CODEC_BLOCKS")), dim3(G1CODEC_THREADS), 0, g.stream, (const uint4 *)affine_dev, (uint4 *)bytes_out_dev, n);
   sc.close();
   HIPCHK(hipGetLastError());
   return MI355_OK;
@@ -111,6 +116,32 @@ static bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint6
 static int g1codec_bad_index(uint64_t bad, uint64_t *first_bad_out) {
   if (first_bad_out) *first_bad_out = bad;
   return fail(MI355_EBADARG, "g1_decompress: word " + std::to_string(bad) + " is not the compressed form of a G1 point (x >= q, x^3 + 3 a non-residue, or the identity with the sign bit set)");
+}
+// the argument checks a _dev / _host pair shares (n != 0); the alignment rule binds device pointers only: the host forms stage through the library's own buffers
+static int g1codec_check_args(const char *who, const void *in, uint64_t in_each, const void *out, uint64_t out_each, uint64_t n, bool dev) {
+  if (!in || !out) return fail(MI355_EBADARG, std::string(who) + ": null pointer");
+  if (n >= (1ull << 32)) return fail(MI355_EBADARG, std::string(who) + ": n must be < 2^32");
+  if (ranges_overlap(in, n * in_each, out, n * out_each)) return fail(MI355_EBADARG, std::string(who) + ": input and output must not overlap");
+  if (dev && (((uintptr_t)in | (uintptr_t)out) & 15)) return fail(MI355_EBADARG, std::string(who) + ": device pointers must be 16-byte aligned");
+  return MI355_OK;
+}
+// Curve::batch_normalize: the host form stages input and output side by side on the device, so only device operands can overlap
+static int g1norm_check_args(const void *jac, const void *affine, uint64_t n, bool dev) {
+  if (n && (!jac || !affine)) return fail(MI355_EBADARG, "g1_batch_normalize: null pointer");
+  if (n >= (1ull << 31)) return fail(MI355_EBADARG, "g1_batch_normalize: n must be < 2^31");
+  if (dev && n && ranges_overlap(jac, n * sizeof(g1_jac_t), affine, n * sizeof(g1_affine_t))) return fail(MI355_EBADARG, "g1_batch_normalize: input and output must not overlap");
+  return MI355_OK;
+}
+// ---- a host table of `count` device pointers (the columns of a witness, the vectors of a batch).  common_slot (lib_core.hip) names the device slot that owns them before the
+// lock is taken (null entries are skipped there and refused here); check_ptr_table, after the entry point's scalar checks: every entry non-null, 16-byte aligned, and
+// bytes_each bytes from it inside the library block that holds it.
+static int check_ptr_table(const void *const *ptrs, uint32_t count, uint64_t bytes_each, const char *who, const char *noun) {
+  for (uint32_t j = 0; j < count; j++) {
+    if (!ptrs[j]) return fail(MI355_EBADARG, std::string(who) + ": null " + noun + " " + std::to_string(j));
+    if ((uintptr_t)ptrs[j] & 15) return fail(MI355_EBADARG, std::string(who) + ": " + noun + " " + std::to_string(j) + " is not 16-byte aligned");
+    CHK(buf_check_range(ptrs[j], bytes_each, who));
+  }
+  return MI355_OK;
 }
 constexpr uint64_t G1CODEC_HOST_CHUNK = 1ull << 22;   // points per staged chunk of the host-pointer forms (128 + 256 MiB of workspace at most)
 
@@ -148,11 +179,8 @@ int mi355_g1_batch_normalize_dev(const void *jac_dev, void *affine_dev, uint64_t
   return guarded([&]() -> int {
   int slot; CHK(common_slot({jac_dev, affine_dev}, &slot, "g1_batch_normalize")); DevGuard lk(slot);
   CHK(need_init(slot));
-  if (n && (!jac_dev || !affine_dev)) return fail(MI355_EBADARG, "g1_batch_normalize: null pointer");
-  if (n >= (1ull << 31)) return fail(MI355_EBADARG, "g1_batch_normalize: n must be < 2^31");
+  CHK(g1norm_check_args(jac_dev, affine_dev, n, true));
   if (n) {
-    const char *a = (const char *)jac_dev, *b = (const char *)affine_dev;
-    if (a < b + n * sizeof(g1_affine_t) && b < a + n * sizeof(g1_jac_t)) return fail(MI355_EBADARG, "g1_batch_normalize: input and output must not overlap");
     hipLaunchKernelGGL(k_g1_batch_normalize, dim3(ceil_div(n, FRSCAN_THREADS)), dim3(FRSCAN_THREADS), 0, g.stream, (const g1_jac_t *)jac_dev, (g1_affine_t *)affine_dev, n);
     HIPCHK(hipGetLastError());
   }
@@ -163,8 +191,7 @@ int mi355_g1_batch_normalize_host(const void *jac_host, void *affine_host, uint6
   return guarded([&]() -> int {
   const int slot = pick_replica_slot(); DevGuard lk(slot);
   CHK(need_init(slot));
-  if (n && (!jac_host || !affine_host)) return fail(MI355_EBADARG, "g1_batch_normalize: null pointer");
-  if (n >= (1ull << 31)) return fail(MI355_EBADARG, "g1_batch_normalize: n must be < 2^31");
+  CHK(g1norm_check_args(jac_host, affine_host, n, false));
   if (!n) return MI355_OK;
   char *dev; CHK(ws_get("io.g1norm", n * (sizeof(g1_jac_t) + sizeof(g1_affine_t)), (void **)&dev));
   g1_jac_t *in = (g1_jac_t *)dev; g1_affine_t *out = (g1_affine_t *)(dev + n * sizeof(g1_jac_t));
@@ -183,10 +210,7 @@ int mi355_g1_decompress_dev(const void *bytes_dev, void *affine_out_dev, uint64_
   CHK(need_init(slot));
   if (first_bad_out) *first_bad_out = ~0ull;
   if (n == 0) return MI355_OK;
-  if (!bytes_dev || !affine_out_dev) return fail(MI355_EBADARG, "g1_decompress: null pointer");
-  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_decompress: n must be < 2^32");
-  if (ranges_overlap(bytes_dev, n * 32, affine_out_dev, n * sizeof(g1_affine_t))) return fail(MI355_EBADARG, "g1_decompress: input and output must not overlap");
-  if (((uintptr_t)bytes_dev | (uintptr_t)affine_out_dev) & 15) return fail(MI355_EBADARG, "g1_decompress: device pointers must be 16-byte aligned");
+  CHK(g1codec_check_args("g1_decompress", bytes_dev, 32, affine_out_dev, sizeof(g1_affine_t), n, true));
   unsigned long long *err; CHK(ws_get("g1codec.err", 8, (void **)&err));
   HIPCHK(hipMemsetAsync(err, 0xff, 8, g.stream));
   CHK(launch_g1_decompress(bytes_dev, affine_out_dev, n, 0, err));
@@ -203,9 +227,7 @@ int mi355_g1_decompress_host(const void *bytes_host, void *affine_out_host, uint
   CHK(need_init(slot));
   if (first_bad_out) *first_bad_out = ~0ull;
   if (n == 0) return MI355_OK;
-  if (!bytes_host || !affine_out_host) return fail(MI355_EBADARG, "g1_decompress: null pointer");
-  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_decompress: n must be < 2^32");
-  if (ranges_overlap(bytes_host, n * 32, affine_out_host, n * sizeof(g1_affine_t))) return fail(MI355_EBADARG, "g1_decompress: input and output must not overlap");
+  CHK(g1codec_check_args("g1_decompress", bytes_host, 32, affine_out_host, sizeof(g1_affine_t), n, false));
   const uint64_t chunk = std::min(n, G1CODEC_HOST_CHUNK);
   char *dev; CHK(ws_get("io.g1codec", chunk * (32 + sizeof(g1_affine_t)) + 256, (void **)&dev));
   unsigned long long *err = (unsigned long long *)dev; char *in = dev + 256, *out = in + chunk * 32;
@@ -229,10 +251,7 @@ int mi355_g1_compress_dev(const void *affine_dev, void *bytes_out_dev, uint64_t 
   int slot; CHK(common_slot({bytes_out_dev, affine_dev}, &slot, "g1_compress")); DevGuard lk(slot);
   CHK(need_init(slot));
   if (n == 0) return MI355_OK;
-  if (!affine_dev || !bytes_out_dev) return fail(MI355_EBADARG, "g1_compress: null pointer");
-  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_compress: n must be < 2^32");
-  if (ranges_overlap(affine_dev, n * sizeof(g1_affine_t), bytes_out_dev, n * 32)) return fail(MI355_EBADARG, "g1_compress: input and output must not overlap");
-  if (((uintptr_t)affine_dev | (uintptr_t)bytes_out_dev) & 15) return fail(MI355_EBADARG, "g1_compress: device pointers must be 16-byte aligned");
+  CHK(g1codec_check_args("g1_compress", affine_dev, sizeof(g1_affine_t), bytes_out_dev, 32, n, true));
   CHK(launch_g1_compress(affine_dev, bytes_out_dev, n));
   return finish_async();
   });
@@ -242,9 +261,7 @@ int mi355_g1_compress_host(const void *affine_host, void *bytes_out_host, uint64
   const int slot = pick_replica_slot(); DevGuard lk(slot);
   CHK(need_init(slot));
   if (n == 0) return MI355_OK;
-  if (!affine_host || !bytes_out_host) return fail(MI355_EBADARG, "g1_compress: null pointer");
-  if (n >= (1ull << 32)) return fail(MI355_EBADARG, "g1_compress: n must be < 2^32");
-  if (ranges_overlap(affine_host, n * sizeof(g1_affine_t), bytes_out_host, n * 32)) return fail(MI355_EBADARG, "g1_compress: input and output must not overlap");
+  CHK(g1codec_check_args("g1_compress", affine_host, sizeof(g1_affine_t), bytes_out_host, 32, n, false));
   const uint64_t chunk = std::min(n, G1CODEC_HOST_CHUNK);
   char *dev; CHK(ws_get("io.g1codec", chunk * (32 + sizeof(g1_affine_t)) + 256, (void **)&dev));
   char *out = dev + 256, *in = out + chunk * 32;
@@ -376,21 +393,17 @@ int mi355_buf_upload_packed(void *dst_dev, const void *src_host, uint64_t n, uin
   if (n > (1ull << 32)) return fail(MI355_EBADARG, "buf_upload_packed: more than 2^32 cells");   // also keeps n * width_bytes and n * 32 far from overflow
   CHK(buf_check_range(dst_dev, n * sizeof(fe_t), "buf_upload_packed"));
   const int slot = slot_of(dst_dev);
-  void *stage = nullptr; CHK(mi355_buf_alloc(stage_class(n * width_bytes), slot, &stage));
-  int rc = mi355_buf_upload(stage, src_host, n * width_bytes);
-  if (rc == MI355_OK) rc = need_init(slot);
-  if (rc == MI355_OK) {
-    hipStream_t s = g_ctx[slot].stream; const dim3 grid((uint32_t)std::min<uint64_t>(ceil_div(n, 256), 65535u * 4));
-    switch (width_bytes) {
-      case 1: hipLaunchKernelGGL(k_expand_packed<1>, grid, dim3(256), 0, s, (fe_t *)dst_dev, (const uint8_t *)stage, n); break;
-      case 2: hipLaunchKernelGGL(k_expand_packed<2>, grid, dim3(256), 0, s, (fe_t *)dst_dev, (const uint8_t *)stage, n); break;
-      case 4: hipLaunchKernelGGL(k_expand_packed<4>, grid, dim3(256), 0, s, (fe_t *)dst_dev, (const uint8_t *)stage, n); break;
-      default: hipLaunchKernelGGL(k_expand_packed<8>, grid, dim3(256), 0, s, (fe_t *)dst_dev, (const uint8_t *)stage, n); break;
-    }
-    if (hipGetLastError() != hipSuccess) rc = fail(MI355_EHIP, "buf_upload_packed: kernel launch failed");
+  PoolBlock stage; CHK(stage.alloc(stage_class(n * width_bytes), slot));
+  CHK(stage.upload(0, src_host, n * width_bytes));
+  hipStream_t s = g_ctx[slot].stream; const dim3 grid(grid_blocks(n, 256)); const uint8_t *src = (const uint8_t *)stage.p;
+  switch (width_bytes) {
+    case 1: hipLaunchKernelGGL(k_expand_packed<1>, grid, dim3(256), 0, s, (fe_t *)dst_dev, src, n); break;
+    case 2: hipLaunchKernelGGL(k_expand_packed<2>, grid, dim3(256), 0, s, (fe_t *)dst_dev, src, n); break;
+    case 4: hipLaunchKernelGGL(k_expand_packed<4>, grid, dim3(256), 0, s, (fe_t *)dst_dev, src, n); break;
+    default: hipLaunchKernelGGL(k_expand_packed<8>, grid, dim3(256), 0, s, (fe_t *)dst_dev, src, n); break;
   }
-  (void)mi355_buf_free(stage);   // back to the pool; its reuse waits for the kernel queued above
-  return rc;
+  HIPCHK(hipGetLastError());
+  return MI355_OK;   // the block goes back to the pool here; its reuse waits for the kernel queued above
   });
 }
 int mi355_buf_upload_sparse(void *dst_dev, uint64_t n, const uint32_t *idx_host, const void *vals_host, uint64_t count) {
@@ -404,19 +417,13 @@ int mi355_buf_upload_sparse(void *dst_dev, uint64_t n, const uint32_t *idx_host,
   hipStream_t s = g_ctx[slot].stream;
   if (count == 0) { HIPCHK(hipMemsetAsync(dst_dev, 0, n * sizeof(fe_t), s)); return MI355_OK; }
   const uint64_t idx_bytes = (count * 4 + 31) & ~31ull;
-  void *stage = nullptr; CHK(mi355_buf_alloc(stage_class(idx_bytes + count * sizeof(fe_t)), slot, &stage));
-  int rc = mi355_buf_upload(stage, idx_host, count * 4);
-  if (rc == MI355_OK) rc = mi355_buf_upload((char *)stage + idx_bytes, vals_host, count * sizeof(fe_t));
-  if (rc == MI355_OK) rc = need_init(slot);
-  if (rc == MI355_OK) {
-    if (hipMemsetAsync(dst_dev, 0, n * sizeof(fe_t), s) != hipSuccess) rc = fail(MI355_EHIP, "buf_upload_sparse: memset failed");
-    else {
-      hipLaunchKernelGGL(k_scatter_fr, dim3((uint32_t)std::min<uint64_t>(ceil_div(count, 256), 65535u * 4)), dim3(256), 0, s, (fe_t *)dst_dev, n, (const uint32_t *)stage, (const fe_t *)((char *)stage + idx_bytes), count);
-      if (hipGetLastError() != hipSuccess) rc = fail(MI355_EHIP, "buf_upload_sparse: kernel launch failed");
-    }
-  }
-  (void)mi355_buf_free(stage);
-  return rc;
+  PoolBlock stage; CHK(stage.alloc(stage_class(idx_bytes + count * sizeof(fe_t)), slot));
+  CHK(stage.upload(0, idx_host, count * 4));
+  CHK(stage.upload(idx_bytes, vals_host, count * sizeof(fe_t)));
+  HIPCHK(hipMemsetAsync(dst_dev, 0, n * sizeof(fe_t), s));
+  hipLaunchKernelGGL(k_scatter_fr, dim3(grid_blocks(count, 256)), dim3(256), 0, s, (fe_t *)dst_dev, n, (const uint32_t *)stage.p, (const fe_t *)stage.at(idx_bytes), count);
+  HIPCHK(hipGetLastError());
+  return MI355_OK;   // as above: the block's reuse waits for the scatter
   });
 }
 // host helper for the sparse form: the non-zero cells of a column of n 32-byte words as (index, value) pairs, in index order; `threads` workers scan disjoint ranges
@@ -441,8 +448,8 @@ int mi355_host_compact_nonzero(const void *src_host, uint64_t n, uint32_t *idx_o
 }
 
 // ---- the multiplicity column m of the mv-lookup argument (lookup.hpp): hash set of the table rows -> counts per row -> Montgomery Fr.  Workspace: ONE pooled
-// mi355_buf block (8 B of error word, 4 B per slot for the next power of two >= 2 x table_rows, 4 B per row of m: ~12 B per row), handed back to the pool on return
-// (mi355_mem_info counts it; mi355_buf_trim gives it back to HIP).  Synchronous: the error word is read back before the call returns.
+// mi355_buf block (PoolBlock; WsLayout: the error word, 4 B per slot for the next power of two >= 2 x table_rows, 4 B per row of m: ~12 B per row), back in the pool
+// on every return (mi355_mem_info counts it; mi355_buf_trim gives it back to HIP).  Synchronous: the error word is read back before the call returns.
 int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *table_dev, uint64_t table_rows, const void *const *inputs_dev, uint32_t n_inputs, uint64_t input_rows,
                                        uint32_t flags, uint64_t *missing_out) {
   return guarded([&]() -> int {
@@ -462,32 +469,29 @@ int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *tabl
   const bool last = flags & 1u;
   const uint64_t S = std::max<uint64_t>(64, 1ull << log2_ceil(2 * table_rows));
   const uint32_t mask = (uint32_t)(S - 1);
-  const uint64_t off_slots = 256, off_cnt = off_slots + ((S * 4 + 255) & ~255ull), bytes = off_cnt + n * 4;
-  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
-  int rc = MI355_OK; unsigned long long err_host = ~0ull;
-  [&]() {
-    hipStream_t s = g.stream;
-    unsigned long long *err = (unsigned long long *)ws; uint32_t *slots = (uint32_t *)((char *)ws + off_slots), *cnt = (uint32_t *)((char *)ws + off_cnt);
-    if (hipMemsetAsync(ws, 0xff, off_cnt, s) != hipSuccess || hipMemsetAsync(cnt, 0, n * 4, s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_lookup_multiplicities: memset failed"); return; }
-    Scope sc("lookup_multiplicities");
-    const fe_t *T = (const fe_t *)table_dev;
-    if (table_rows) {
-      const dim3 grid((uint32_t)std::min<uint64_t>(ceil_div(table_rows, LK_THREADS), 65535u * 4));
-      if (last) hipLaunchKernelGGL(k_lk_insert<true>, grid, dim3(LK_THREADS), 0, s, T, table_rows, slots, mask);
-      else hipLaunchKernelGGL(k_lk_insert<false>, grid, dim3(LK_THREADS), 0, s, T, table_rows, slots, mask);
-    }
-    // ~8 192 waves per column at most (one resident wave per SIMD slot of the chip, a few over): the hot row of each is one atomic at the end
-    const uint64_t wave_rows = std::max<uint64_t>(2048, (ceil_div(input_rows, 8192) + 63) & ~63ull);
-    const uint64_t waves = ceil_div(input_rows, wave_rows);
-    for (uint32_t c = 0; c < n_inputs && input_rows; c++)
-      hipLaunchKernelGGL(k_lk_probe, dim3(ceil_div(waves, LK_THREADS / 64)), dim3(LK_THREADS), 0, s, (const fe_t *)inputs_dev[c], input_rows, (uint64_t)c, T, (const uint32_t *)slots, mask, cnt, err, wave_rows);
-    hipLaunchKernelGGL(k_expand_packed<4>, dim3((uint32_t)std::min<uint64_t>(ceil_div(n, 256), 65535u * 4)), dim3(256), 0, s, (fe_t *)m_dev, (const uint8_t *)cnt, n);
-    sc.close();
-    if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_lookup_multiplicities: kernel launch failed"); return; }
-    if (hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_lookup_multiplicities: stream synchronize failed"); return; }
-  }();
-  (void)mi355_buf_free(ws);
-  if (rc != MI355_OK) return rc;
+  WsLayout L; const uint64_t off_err = L.take(8), off_slots = L.take(S * 4), off_cnt = L.take_exact(n * 4);
+  PoolBlock ws; CHK(ws.alloc(L.total(), slot));
+  hipStream_t s = g.stream;
+  unsigned long long *err = (unsigned long long *)ws.at(off_err), err_host = ~0ull; uint32_t *slots = (uint32_t *)ws.at(off_slots), *cnt = (uint32_t *)ws.at(off_cnt);
+  HIPCHK(hipMemsetAsync(ws.p, 0xff, off_cnt, s));   // the error word and the empty slots
+  HIPCHK(hipMemsetAsync(cnt, 0, n * 4, s));
+  Scope sc("lookup_multiplicities");
+  const fe_t *T = (const fe_t *)table_dev;
+  if (table_rows) {
+    const dim3 grid(grid_blocks(table_rows, LK_THREADS));
+    if (last) hipLaunchKernelGGL(k_lk_insert<true>, grid, dim3(LK_THREADS), 0, s, T, table_rows, slots, mask);
+    else hipLaunchKernelGGL(k_lk_insert<false>, grid, dim3(LK_THREADS), 0, s, T, table_rows, slots, mask);
+  }
+  // ~8 192 waves per column at most (one resident wave per SIMD slot of the chip, a few over): the hot row of each is one atomic at the end
+  const uint64_t wave_rows = std::max<uint64_t>(2048, (ceil_div(input_rows, 8192) + 63) & ~63ull);
+  const uint64_t waves = ceil_div(input_rows, wave_rows);
+  for (uint32_t c = 0; c < n_inputs && input_rows; c++)
+    hipLaunchKernelGGL(k_lk_probe, dim3(ceil_div(waves, LK_THREADS / 64)), dim3(LK_THREADS), 0, s, (const fe_t *)inputs_dev[c], input_rows, (uint64_t)c, T, (const uint32_t *)slots, mask, cnt, err, wave_rows);
+  hipLaunchKernelGGL(k_expand_packed<4>, dim3(grid_blocks(n, 256)), dim3(256), 0, s, (fe_t *)m_dev, (const uint8_t *)cnt, n);
+  sc.close();
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   if (err_host != ~0ull) {
     if (missing_out) *missing_out = err_host;
     return fail(MI355_EBADARG, "fr_lookup_multiplicities: input " + std::to_string(err_host >> 40) + ", row " + std::to_string(err_host & ((1ull << 40) - 1)) + " is not in the table");
@@ -497,15 +501,14 @@ int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *tabl
 }
 
 // ---- the sigma columns of the permutation argument from the copy mapping (perm.hpp).  The mapping is checked on the host first (perm_check): on MI355_EBADARG nothing has
-// been uploaded or launched.  Workspace: ONE pooled mi355_buf block -- the column pointers, the three power tables (n_cols + 2 x 2^(log_n / 2) words) and a staging area for
-// at most PERM_STAGE overrides (16 B each) -- handed back to the pool on return.  Longer lists go through the staging area piece by piece: an upload into it waits for the
+// been uploaded or launched.  Workspace: ONE pooled mi355_buf block (PoolBlock; WsLayout) -- the column pointers, the three power tables (n_cols + 2 x 2^(log_n / 2) words, packed)
+// and a staging area for at most PERM_STAGE overrides (16 B each) -- back in the pool on every return.  Longer lists go through the staging area piece by piece: an upload into it waits for the
 // kernel that reads the previous piece (mi355_buf_upload into a block in use).  Synchronous: the call returns when the columns are written.
 constexpr uint64_t PERM_STAGE = 1ull << 22;
 int mi355_fr_permutation_sigma_dev(void *const *sigma_dev, uint32_t n_cols, uint32_t log_n, const void *delta, const void *omega, const uint64_t *cells_host,
                                    const uint64_t *images_host, uint64_t count, uint32_t flags) {
   return guarded([&]() -> int {
-  int slot = 0;
-  for (uint32_t j = 0; sigma_dev && j < n_cols; j++) { int s2; CHK(common_slot({sigma_dev[0], sigma_dev[j]}, &s2, "fr_permutation_sigma")); if (j == 0) slot = s2; }
+  int slot; CHK(common_slot(sigma_dev, n_cols, true, &slot, "fr_permutation_sigma"));
   DevGuard lk(slot);
   CHK(need_init(slot));
   if (n_cols == 0 || n_cols > 65535u * PERM_COL_TILE) return fail(MI355_EBADARG, "fr_permutation_sigma: n_cols must be 1 .. " + std::to_string(65535u * PERM_COL_TILE));
@@ -513,102 +516,84 @@ int mi355_fr_permutation_sigma_dev(void *const *sigma_dev, uint32_t n_cols, uint
   if (!sigma_dev || !delta || !omega || (count && (!cells_host || !images_host))) return fail(MI355_EBADARG, "fr_permutation_sigma: null pointer");
   if (flags & ~PERM_FLAG_TRUSTED) return fail(MI355_EBADARG, "fr_permutation_sigma: unknown flag bits");
   const uint64_t n = 1ull << log_n, total = (uint64_t)n_cols * n;
-  for (uint32_t j = 0; j < n_cols; j++) {
-    if (!sigma_dev[j]) return fail(MI355_EBADARG, "fr_permutation_sigma: null column " + std::to_string(j));
-    if ((uintptr_t)sigma_dev[j] & 15) return fail(MI355_EBADARG, "fr_permutation_sigma: device pointers must be 16-byte aligned");
-    CHK(buf_check_range(sigma_dev[j], n * sizeof(fe_t), "fr_permutation_sigma"));
-  }
+  CHK(check_ptr_table(sigma_dev, n_cols, n * sizeof(fe_t), "fr_permutation_sigma", "column"));
   { uint64_t bad = 0; std::string why; if (perm_check(cells_host, images_host, count, total, flags, &bad, &why)) return fail(MI355_EBADARG, "fr_permutation_sigma: override " + std::to_string(bad) + ": " + why); }
   const uint32_t lo_bits = perm_lo_bits(log_n), n_lo = 1u << lo_bits, n_hi = 1u << (log_n - lo_bits);
   const uint64_t stage = std::min(count, PERM_STAGE);
-  const uint64_t off_dpow = ((uint64_t)n_cols * 8 + 255) & ~255ull, off_lo = off_dpow + (uint64_t)n_cols * sizeof(fe_t), off_hi = off_lo + (uint64_t)n_lo * sizeof(fe_t),
-                 off_cells = off_hi + (uint64_t)n_hi * sizeof(fe_t), off_images = off_cells + stage * 8, bytes = off_images + stage * 8;
-  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
-  int rc = MI355_OK;
-  [&]() {
-    char *base = (char *)ws; hipStream_t s = g.stream;
-    fe_t *const *cols = (fe_t *const *)base; fe_t *dpow = (fe_t *)(base + off_dpow), *tw_lo = (fe_t *)(base + off_lo), *tw_hi = (fe_t *)(base + off_hi);
-    if ((rc = mi355_buf_upload(ws, sigma_dev, (uint64_t)n_cols * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
-    fe_t d, w; memcpy(&d, delta, 32); memcpy(&w, omega, 32);
-    const PermTables T{tw_lo, tw_hi, dpow, lo_bits};
-    {
-      Scope sc("permutation_sigma");
-      if ((rc = launch_pow_table(dpow, d, 1, n_cols)) != MI355_OK || (rc = launch_pow_table(tw_lo, w, 1, n_lo)) != MI355_OK || (rc = launch_pow_table(tw_hi, w, n_lo, n_hi)) != MI355_OK) return;
-      hipLaunchKernelGGL(k_perm_identity, dim3(ceil_div(n, PERM_THREADS), ceil_div(n_cols, PERM_COL_TILE)), dim3(PERM_THREADS), 0, s, cols, n_cols, log_n, T, d);
-    }
-    if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: kernel launch failed"); return; }
-    for (uint64_t lo = 0; lo < count; lo += stage) {
-      const uint64_t len = std::min(stage, count - lo);
-      if ((rc = mi355_buf_upload(base + off_cells, cells_host + lo, len * 8)) != MI355_OK || (rc = mi355_buf_upload(base + off_images, images_host + lo, len * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
-      Scope sc("permutation_sigma");
-      hipLaunchKernelGGL(k_perm_override, dim3((uint32_t)std::min<uint64_t>(ceil_div(len, PERM_THREADS), 65535u * 4)), dim3(PERM_THREADS), 0, s, cols, log_n, T,
-                         (const uint64_t *)(base + off_cells), (const uint64_t *)(base + off_images), len);
-      sc.close();
-      if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: kernel launch failed"); return; }
-    }
-    if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_permutation_sigma: stream synchronize failed"); return; }
-  }();
-  (void)mi355_buf_free(ws);
-  if (rc != MI355_OK) return rc;
+  WsLayout L;
+  const uint64_t off_cols = L.take((uint64_t)n_cols * 8), off_dpow = L.take_exact((uint64_t)n_cols * sizeof(fe_t)), off_lo = L.take_exact((uint64_t)n_lo * sizeof(fe_t)),
+                 off_hi = L.take_exact((uint64_t)n_hi * sizeof(fe_t)), off_cells = L.take_exact(stage * 8), off_images = L.take_exact(stage * 8);
+  PoolBlock ws; CHK(ws.alloc(L.total(), slot));
+  hipStream_t s = g.stream;
+  fe_t *const *cols = (fe_t *const *)ws.at(off_cols); fe_t *dpow = (fe_t *)ws.at(off_dpow), *tw_lo = (fe_t *)ws.at(off_lo), *tw_hi = (fe_t *)ws.at(off_hi);
+  CHK(ws.upload(off_cols, sigma_dev, (uint64_t)n_cols * 8));
+  fe_t d, w; memcpy(&d, delta, 32); memcpy(&w, omega, 32);
+  const PermTables T{tw_lo, tw_hi, dpow, lo_bits};
+  {
+    Scope sc("permutation_sigma");
+    CHK(launch_pow_table(dpow, d, 1, n_cols)); CHK(launch_pow_table(tw_lo, w, 1, n_lo)); CHK(launch_pow_table(tw_hi, w, n_lo, n_hi));
+    hipLaunchKernelGGL(k_perm_identity, dim3(ceil_div(n, PERM_THREADS), ceil_div(n_cols, PERM_COL_TILE)), dim3(PERM_THREADS), 0, s, cols, n_cols, log_n, T, d);
+  }
+  HIPCHK(hipGetLastError());
+  for (uint64_t lo = 0; lo < count; lo += stage) {
+    const uint64_t len = std::min(stage, count - lo);
+    CHK(ws.upload(off_cells, cells_host + lo, len * 8)); CHK(ws.upload(off_images, images_host + lo, len * 8));
+    Scope sc("permutation_sigma");
+    hipLaunchKernelGGL(k_perm_override, dim3(grid_blocks(len, PERM_THREADS)), dim3(PERM_THREADS), 0, s, cols, log_n, T, (const uint64_t *)ws.at(off_cells), (const uint64_t *)ws.at(off_images), len);
+    sc.close();
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(s));
   return finish_async();
   });
 }
 
 // ---- the reductions of the witness check (check.hpp): count + the smallest `cap` failing indices, ascending.  Three launches per vector batch / staged piece --
 // count per workgroup, scan of the counts, ranked write -- and ONE synchronisation at the end, when the totals and the indices come back.  Workspace: ONE pooled
-// mi355_buf block (the pointer table, the totals, the index lists, 8 B per workgroup of CHECK_TILE elements; copy_check: two lists of at most CHECK_STAGE entries),
-// handed back to the pool on return.
+// mi355_buf block (PoolBlock; WsLayout: the pointer table, the totals, the index lists, 8 B per workgroup of CHECK_TILE elements; copy_check: two lists of at most
+// CHECK_STAGE entries), back in the pool on every return.
 constexpr uint64_t CHECK_STAGE = 1ull << 22;   // a multiple of CHECK_TILE
-static uint64_t align256(uint64_t b) { return (b + 255) & ~255ull; }
 int mi355_fr_nonzero_rows_dev(const void *const *vecs_dev, uint32_t batch, uint64_t n, uint32_t cap, uint64_t *counts_out_host, uint64_t *rows_out_host) {
   return guarded([&]() -> int {
-  int slot = 0;
-  for (uint32_t v = 0; vecs_dev && v < batch; v++) { int s2; CHK(common_slot({vecs_dev[0], vecs_dev[v]}, &s2, "fr_nonzero_rows")); if (v == 0) slot = s2; }
+  int slot; CHK(common_slot(vecs_dev, batch, true, &slot, "fr_nonzero_rows"));
   DevGuard lk(slot);
   CHK(need_init(slot));
   if (batch == 0 || n == 0) return fail(MI355_EBADARG, "fr_nonzero_rows: batch and n must not be zero");
   if (n >= (1ull << 40)) return fail(MI355_EBADARG, "fr_nonzero_rows: n too large");
   if (cap > CHECK_MAX_CAP) return fail(MI355_EBADARG, "fr_nonzero_rows: cap " + std::to_string(cap) + " exceeds " + std::to_string(CHECK_MAX_CAP));
   if (!vecs_dev || !counts_out_host || (cap && !rows_out_host)) return fail(MI355_EBADARG, "fr_nonzero_rows: null pointer");
-  for (uint32_t v = 0; v < batch; v++) {
-    if (!vecs_dev[v]) return fail(MI355_EBADARG, "fr_nonzero_rows: null vector " + std::to_string(v));
-    if ((uintptr_t)vecs_dev[v] & 15) return fail(MI355_EBADARG, "fr_nonzero_rows: vector " + std::to_string(v) + " is not 16-byte aligned");
-    CHK(buf_check_range(vecs_dev[v], n * sizeof(fe_t), "fr_nonzero_rows"));
-  }
+  CHK(check_ptr_table(vecs_dev, batch, n * sizeof(fe_t), "fr_nonzero_rows", "vector"));
   const uint32_t nblocks = (uint32_t)ceil_div(n, CHECK_TILE);
-  const uint64_t off_tot = align256((uint64_t)batch * 8), off_rows = off_tot + align256((uint64_t)batch * 8), off_cnt = off_rows + align256((uint64_t)batch * cap * 8),
-                 off_pre = off_cnt + align256((uint64_t)batch * nblocks * 4), bytes = off_pre + align256((uint64_t)batch * nblocks * 4);
-  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
-  int rc = MI355_OK;
-  [&]() {
-    char *base = (char *)ws; hipStream_t s = g.stream;
-    if ((rc = mi355_buf_upload(ws, vecs_dev, (uint64_t)batch * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
-    const fe_t *const *vecs = (const fe_t *const *)base; unsigned long long *tot = (unsigned long long *)(base + off_tot); uint64_t *rows = (uint64_t *)(base + off_rows);
-    uint32_t *cnt = (uint32_t *)(base + off_cnt), *pre = (uint32_t *)(base + off_pre);
-    if (hipMemsetAsync(tot, 0, (uint64_t)batch * 8, s) != hipSuccess || (cap && hipMemsetAsync(rows, 0xff, (uint64_t)batch * cap * 8, s) != hipSuccess)) { rc = fail(MI355_EHIP, "fr_nonzero_rows: memset failed"); return; }
-    {
-      Scope sc("nonzero_rows");
-      for (uint32_t v0 = 0; v0 < batch; v0 += 65535) {   // blockIdx.y = vector
-        const uint32_t nv = std::min<uint32_t>(65535, batch - v0); const uint64_t o = (uint64_t)v0 * nblocks;
-        hipLaunchKernelGGL(k_fr_nonzero_rows<0>, dim3(nblocks, nv), dim3(CHECK_THREADS), 0, s, vecs + v0, n, cap, cnt + o, (const uint32_t *)(pre + o), rows + (uint64_t)v0 * cap);
-        hipLaunchKernelGGL(k_check_scan, dim3(nv), dim3(CHECK_THREADS), 0, s, (const uint32_t *)(cnt + o), pre + o, nblocks, tot + v0);
-        if (cap) hipLaunchKernelGGL(k_fr_nonzero_rows<1>, dim3(nblocks, nv), dim3(CHECK_THREADS), 0, s, vecs + v0, n, cap, cnt + o, (const uint32_t *)(pre + o), rows + (uint64_t)v0 * cap);
-      }
+  WsLayout L;
+  const uint64_t off_vecs = L.take((uint64_t)batch * 8), off_tot = L.take((uint64_t)batch * 8), off_rows = L.take((uint64_t)batch * cap * 8), off_cnt = L.take((uint64_t)batch * nblocks * 4),
+                 off_pre = L.take((uint64_t)batch * nblocks * 4);
+  PoolBlock ws; CHK(ws.alloc(L.total(), slot));
+  hipStream_t s = g.stream;
+  CHK(ws.upload(off_vecs, vecs_dev, (uint64_t)batch * 8));
+  const fe_t *const *vecs = (const fe_t *const *)ws.at(off_vecs); unsigned long long *tot = (unsigned long long *)ws.at(off_tot); uint64_t *rows = (uint64_t *)ws.at(off_rows);
+  uint32_t *cnt = (uint32_t *)ws.at(off_cnt), *pre = (uint32_t *)ws.at(off_pre);
+  HIPCHK(hipMemsetAsync(tot, 0, (uint64_t)batch * 8, s));
+  if (cap) HIPCHK(hipMemsetAsync(rows, 0xff, (uint64_t)batch * cap * 8, s));
+  {
+    Scope sc("nonzero_rows");
+    for (uint32_t v0 = 0; v0 < batch; v0 += 65535) {   // blockIdx.y = vector
+      const uint32_t nv = std::min<uint32_t>(65535, batch - v0); const uint64_t o = (uint64_t)v0 * nblocks;
+      hipLaunchKernelGGL(k_fr_nonzero_rows<0>, dim3(nblocks, nv), dim3(CHECK_THREADS), 0, s, vecs + v0, n, cap, cnt + o, (const uint32_t *)(pre + o), rows + (uint64_t)v0 * cap);
+      hipLaunchKernelGGL(k_check_scan, dim3(nv), dim3(CHECK_THREADS), 0, s, (const uint32_t *)(cnt + o), pre + o, nblocks, tot + v0);
+      if (cap) hipLaunchKernelGGL(k_fr_nonzero_rows<1>, dim3(nblocks, nv), dim3(CHECK_THREADS), 0, s, vecs + v0, n, cap, cnt + o, (const uint32_t *)(pre + o), rows + (uint64_t)v0 * cap);
     }
-    if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_nonzero_rows: kernel launch failed"); return; }
-    if (hipMemcpyAsync(counts_out_host, tot, (uint64_t)batch * 8, hipMemcpyDeviceToHost, s) != hipSuccess || (cap && hipMemcpyAsync(rows_out_host, rows, (uint64_t)batch * cap * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_nonzero_rows: stream synchronize failed"); return; }
-  }();
-  (void)mi355_buf_free(ws);
-  if (rc != MI355_OK) return rc;
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(counts_out_host, tot, (uint64_t)batch * 8, hipMemcpyDeviceToHost, s));
+  if (cap) HIPCHK(hipMemcpyAsync(rows_out_host, rows, (uint64_t)batch * cap * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return finish_async();
   });
 }
 int mi355_fr_copy_check_dev(const void *const *cols_dev, uint32_t n_cols, uint32_t log_n, const uint64_t *cells_host, const uint64_t *images_host, uint64_t count, uint32_t cap,
                             uint64_t *n_failed_out, uint64_t *failed_t_out_host) {
   return guarded([&]() -> int {
-  int slot = 0;
-  for (uint32_t j = 0; cols_dev && j < n_cols; j++) { int s2; CHK(common_slot({cols_dev[0], cols_dev[j]}, &s2, "fr_copy_check")); if (j == 0) slot = s2; }
+  int slot; CHK(common_slot(cols_dev, n_cols, true, &slot, "fr_copy_check"));
   DevGuard lk(slot);
   CHK(need_init(slot));
   if (n_cols == 0) return fail(MI355_EBADARG, "fr_copy_check: n_cols must not be zero");
@@ -616,40 +601,34 @@ int mi355_fr_copy_check_dev(const void *const *cols_dev, uint32_t n_cols, uint32
   if (cap > CHECK_MAX_CAP) return fail(MI355_EBADARG, "fr_copy_check: cap " + std::to_string(cap) + " exceeds " + std::to_string(CHECK_MAX_CAP));
   if (!cols_dev || !n_failed_out || (cap && !failed_t_out_host) || (count && (!cells_host || !images_host))) return fail(MI355_EBADARG, "fr_copy_check: null pointer");
   const uint64_t n = 1ull << log_n, total = (uint64_t)n_cols * n;
-  for (uint32_t j = 0; j < n_cols; j++) {
-    if (!cols_dev[j]) return fail(MI355_EBADARG, "fr_copy_check: null column " + std::to_string(j));
-    if ((uintptr_t)cols_dev[j] & 15) return fail(MI355_EBADARG, "fr_copy_check: column " + std::to_string(j) + " is not 16-byte aligned");
-    CHK(buf_check_range(cols_dev[j], n * sizeof(fe_t), "fr_copy_check"));
-  }
+  CHK(check_ptr_table(cols_dev, n_cols, n * sizeof(fe_t), "fr_copy_check", "column"));
   // a cell >= n_cols * n would be a load outside the columns: the range check of perm_check (the bijection is not this call's business: any list of pairs may be compared)
   { uint64_t bad = 0; std::string why; if (perm_check(cells_host, images_host, count, total, PERM_FLAG_TRUSTED, &bad, &why)) return fail(MI355_EBADARG, "fr_copy_check: pair " + std::to_string(bad) + ": " + why); }
   const uint64_t stage = std::min(count, CHECK_STAGE); const uint32_t max_blocks = (uint32_t)ceil_div(stage, CHECK_TILE);
-  const uint64_t off_tot = align256((uint64_t)n_cols * 8), off_failed = off_tot + 256, off_cnt = off_failed + align256((uint64_t)cap * 8), off_pre = off_cnt + align256((uint64_t)max_blocks * 4),
-                 off_cells = off_pre + align256((uint64_t)max_blocks * 4), off_images = off_cells + align256(stage * 8), bytes = off_images + align256(stage * 8);
-  void *ws = nullptr; CHK(mi355_buf_alloc(bytes, slot, &ws));
-  int rc = MI355_OK;
-  [&]() {
-    char *base = (char *)ws; hipStream_t s = g.stream;
-    if ((rc = mi355_buf_upload(ws, cols_dev, (uint64_t)n_cols * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
-    const fe_t *const *cols = (const fe_t *const *)base; unsigned long long *tot = (unsigned long long *)(base + off_tot); uint64_t *failed = (uint64_t *)(base + off_failed);
-    uint32_t *cnt = (uint32_t *)(base + off_cnt), *pre = (uint32_t *)(base + off_pre);
-    const uint64_t *cells = (const uint64_t *)(base + off_cells), *images = (const uint64_t *)(base + off_images);
-    if (hipMemsetAsync(tot, 0, 8, s) != hipSuccess || (cap && hipMemsetAsync(failed, 0xff, (uint64_t)cap * 8, s) != hipSuccess)) { rc = fail(MI355_EHIP, "fr_copy_check: memset failed"); return; }
-    for (uint64_t lo = 0; lo < count; lo += stage) {   // an upload into the staging area waits for the kernels that read the previous piece (mi355_buf_upload into a block in use)
-      const uint64_t len = std::min(stage, count - lo); const uint32_t nblocks = (uint32_t)ceil_div(len, CHECK_TILE);
-      if ((rc = mi355_buf_upload(base + off_cells, cells_host + lo, len * 8)) != MI355_OK || (rc = mi355_buf_upload(base + off_images, images_host + lo, len * 8)) != MI355_OK || (rc = need_init(slot)) != MI355_OK) return;
-      Scope sc("copy_check");
-      hipLaunchKernelGGL(k_fr_copy_check<0>, dim3(nblocks), dim3(CHECK_THREADS), 0, s, cols, log_n, cells, images, len, lo, cap, cnt, (const uint32_t *)pre, failed);
-      hipLaunchKernelGGL(k_check_scan, dim3(1), dim3(CHECK_THREADS), 0, s, (const uint32_t *)cnt, pre, nblocks, tot);
-      if (cap) hipLaunchKernelGGL(k_fr_copy_check<1>, dim3(nblocks), dim3(CHECK_THREADS), 0, s, cols, log_n, cells, images, len, lo, cap, cnt, (const uint32_t *)pre, failed);
-      sc.close();
-      if (hipGetLastError() != hipSuccess) { rc = fail(MI355_EHIP, "fr_copy_check: kernel launch failed"); return; }
-    }
-    if (hipMemcpyAsync(n_failed_out, tot, 8, hipMemcpyDeviceToHost, s) != hipSuccess || (cap && hipMemcpyAsync(failed_t_out_host, failed, (uint64_t)cap * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        hipStreamSynchronize(s) != hipSuccess) { rc = fail(MI355_EHIP, "fr_copy_check: stream synchronize failed"); return; }
-  }();
-  (void)mi355_buf_free(ws);
-  if (rc != MI355_OK) return rc;
+  WsLayout L;
+  const uint64_t off_cols = L.take((uint64_t)n_cols * 8), off_tot = L.take(8), off_failed = L.take((uint64_t)cap * 8), off_cnt = L.take((uint64_t)max_blocks * 4), off_pre = L.take((uint64_t)max_blocks * 4),
+                 off_cells = L.take(stage * 8), off_images = L.take(stage * 8);
+  PoolBlock ws; CHK(ws.alloc(L.total(), slot));
+  hipStream_t s = g.stream;
+  CHK(ws.upload(off_cols, cols_dev, (uint64_t)n_cols * 8));
+  const fe_t *const *cols = (const fe_t *const *)ws.at(off_cols); unsigned long long *tot = (unsigned long long *)ws.at(off_tot); uint64_t *failed = (uint64_t *)ws.at(off_failed);
+  uint32_t *cnt = (uint32_t *)ws.at(off_cnt), *pre = (uint32_t *)ws.at(off_pre);
+  const uint64_t *cells = (const uint64_t *)ws.at(off_cells), *images = (const uint64_t *)ws.at(off_images);
+  HIPCHK(hipMemsetAsync(tot, 0, 8, s));
+  if (cap) HIPCHK(hipMemsetAsync(failed, 0xff, (uint64_t)cap * 8, s));
+  for (uint64_t lo = 0; lo < count; lo += stage) {   // an upload into the staging area waits for the kernels that read the previous piece (mi355_buf_upload into a block in use)
+    const uint64_t len = std::min(stage, count - lo); const uint32_t nblocks = (uint32_t)ceil_div(len, CHECK_TILE);
+    CHK(ws.upload(off_cells, cells_host + lo, len * 8)); CHK(ws.upload(off_images, images_host + lo, len * 8));
+    Scope sc("copy_check");
+    hipLaunchKernelGGL(k_fr_copy_check<0>, dim3(nblocks), dim3(CHECK_THREADS), 0, s, cols, log_n, cells, images, len, lo, cap, cnt, (const uint32_t *)pre, failed);
+    hipLaunchKernelGGL(k_check_scan, dim3(1), dim3(CHECK_THREADS), 0, s, (const uint32_t *)cnt, pre, nblocks, tot);
+    if (cap) hipLaunchKernelGGL(k_fr_copy_check<1>, dim3(nblocks), dim3(CHECK_THREADS), 0, s, cols, log_n, cells, images, len, lo, cap, cnt, (const uint32_t *)pre, failed);
+    sc.close();
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(n_failed_out, tot, 8, hipMemcpyDeviceToHost, s));
+  if (cap) HIPCHK(hipMemcpyAsync(failed_t_out_host, failed, (uint64_t)cap * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return finish_async();
   });
 }
@@ -658,11 +637,6 @@ int mi355_fr_copy_check_dev(const void *const *cols_dev, uint32_t n_cols, uint32
 // kernel argument and nothing else: it is never copied into an error text, a trace line or a range name.  A draw whose block counters would wrap 2^64 is refused before
 // the device is looked at: a (key, stream) pair must never repeat a block.  Grid: grid-stride over at most 8 workgroups per CU; MI355_FR_RANDOM_BLOCKS overrides the
 // workgroup count (tests make every lane loop; the result must not depend on it).
-static uint32_t frrand_grid(uint64_t n) {
-  uint64_t blocks = std::min<uint64_t>(ceil_div(n, FRRAND_THREADS), (uint64_t)g.prop.multiProcessorCount * 8);
-  if (const char *e = getenv("MI355_FR_RANDOM_BLOCKS")) { const long v = atol(e); if (v > 0) blocks = std::min<uint64_t>((uint64_t)v, 65535u * 4); }
-  return (uint32_t)std::max<uint64_t>(1, blocks);
-}
 static frrand_key_t frrand_key(const uint8_t *key32) { frrand_key_t k; memcpy(k.w, key32, 32); return k; }   // little-endian host: bytes -> words
 int mi355_fr_random_dev(void *dst, uint64_t n, const uint8_t *key32, uint64_t stream, uint64_t counter0) {
   return guarded([&]() -> int {
@@ -675,7 +649,7 @@ int mi355_fr_random_dev(void *dst, uint64_t n, const uint8_t *key32, uint64_t st
   if ((uintptr_t)dst & 15) return fail(MI355_EBADARG, "fr_random: device pointers must be 16-byte aligned");
   CHK(buf_check_range(dst, n * sizeof(fe_t), "fr_random"));
   Scope sc("fr_random");
-  hipLaunchKernelGGL(k_fr_random, dim3(frrand_grid(n)), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *)dst, n, frrand_key(key32), stream, counter0);
+  hipLaunchKernelGGL(k_fr_random, dim3(grid_blocks(n, FRRAND_THREADS, 8, "MI355_FR_RANDOM_BLOCKS")), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *)dst, n, frrand_key(key32), stream, counter0);
   sc.close();
   HIPCHK(hipGetLastError());
   return finish_async();
@@ -688,36 +662,20 @@ int mi355_fr_random_rows_dev(void *const *cols, uint32_t n_cols, uint64_t row0, 
   // the columns are looked up WITHOUT marking their blocks as in use: a witness upload into the other rows of a column (create_proof: rows [0, u + 1) cross the link while
   // rows [u + 1, n) are drawn) then keeps its fresh-block ordering instead of waiting for everything queued on the compute stream.  Disjoint rows need no order; calls
   // queued afterwards on the compute stream see both.
-  int slot = -1;
-  for (uint32_t c = 0; cols && c < n_cols; c++) {
-    if (!cols[c]) continue;
-    const int s2 = slot_of(cols[c], false);
-    if (slot < 0) slot = s2;
-    else if (s2 != slot && g_ctx[s2].device != g_ctx[slot].device) return fail(MI355_EBADARG, "fr_random_rows: the columns live on different devices");
-  }
-  if (slot < 0) slot = 0;
+  int slot; CHK(common_slot(cols, n_cols, false, &slot, "fr_random_rows"));
   DevGuard lk(slot);
   CHK(need_init(slot));
   if (total == 0) return MI355_OK;
   if (!cols || !key32) return fail(MI355_EBADARG, "fr_random_rows: null pointer");
   if (row0 >= (1ull << 40)) return fail(MI355_EBADARG, "fr_random_rows: row0 too large");
-  for (uint32_t c = 0; c < n_cols; c++) {
-    if (!cols[c]) return fail(MI355_EBADARG, "fr_random_rows: null column " + std::to_string(c));
-    if ((uintptr_t)cols[c] & 15) return fail(MI355_EBADARG, "fr_random_rows: device pointers must be 16-byte aligned");
-    CHK(buf_check_range(cols[c], (row0 + rows) * sizeof(fe_t), "fr_random_rows"));
-  }
-  void *ws = nullptr; CHK(mi355_buf_alloc(stage_class((uint64_t)n_cols * 8), slot, &ws));
-  int rc = mi355_buf_upload(ws, cols, (uint64_t)n_cols * 8);
-  if (rc == MI355_OK) rc = need_init(slot);
-  if (rc == MI355_OK) {
-    Scope sc("fr_random");
-    hipLaunchKernelGGL(k_fr_random_rows, dim3(frrand_grid(total)), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *const *)ws, n_cols, row0, rows, frrand_key(key32), stream, counter0);
-    sc.close();
-    if (hipGetLastError() != hipSuccess) rc = fail(MI355_EHIP, "fr_random_rows: kernel launch failed");
-  }
-  (void)mi355_buf_free(ws);   // back to the pool; its reuse waits for the kernel queued above
-  if (rc != MI355_OK) return rc;
-  return finish_async();
+  CHK(check_ptr_table(cols, n_cols, (row0 + rows) * sizeof(fe_t), "fr_random_rows", "column"));
+  PoolBlock ws; CHK(ws.alloc(stage_class((uint64_t)n_cols * 8), slot));
+  CHK(ws.upload(0, cols, (uint64_t)n_cols * 8));
+  Scope sc("fr_random");
+  hipLaunchKernelGGL(k_fr_random_rows, dim3(grid_blocks(total, FRRAND_THREADS, 8, "MI355_FR_RANDOM_BLOCKS")), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *const *)ws.p, n_cols, row0, rows, frrand_key(key32), stream, counter0);
+  sc.close();
+  HIPCHK(hipGetLastError());
+  return finish_async();   // the block goes back to the pool here; its reuse waits for the kernel queued above
   });
 }
 // Fr::from_uniform_bytes over an array: src 64-byte little-endian integers, dst their residues mod r as Montgomery words
@@ -732,7 +690,7 @@ int mi355_fr_from_u512_dev(void *dst, const void *src, uint64_t n) {
   if (ranges_overlap(src, n * 64, dst, n * sizeof(fe_t))) return fail(MI355_EBADARG, "fr_from_u512: input and output must not overlap");
   CHK(buf_check_range(dst, n * sizeof(fe_t), "fr_from_u512"));
   Scope sc("fr_from_u512");
-  hipLaunchKernelGGL(k_fr_from_u512, dim3(frrand_grid(n)), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *)dst, (const uint4 *)src, n);
+  hipLaunchKernelGGL(k_fr_from_u512, dim3(grid_blocks(n, FRRAND_THREADS, 8, "MI355_FR_RANDOM_BLOCKS")), dim3(FRRAND_THREADS), 0, g.stream, (fe_t *)dst, (const uint4 *)src, n);
   sc.close();
   HIPCHK(hipGetLastError());
   return finish_async();
@@ -782,17 +740,17 @@ int mi355_poseidon_transcripts_host(const void *words_host, const uint64_t *word
     const hipError_t e = hipMemcpyAsync(tab, t.data(), t.size() * sizeof(fe_t), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) { g.ws.erase("poseidon.tables"); (void)hipFree(tab); HIPCHK(e); }
   }
-  auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-  const uint64_t off_woff = al(n_words * sizeof(fe_t)), off_soff = off_woff + al(((uint64_t)jobs + 1) * 8), off_sq = off_soff + al(((uint64_t)jobs + 1) * 8),
-                 off_out = off_sq + al(n_sq * 4), bytes = off_out + al(n_sq * sizeof(fe_t));
-  char *dev; CHK(ws_get("io.poseidon", bytes, (void **)&dev));
-  if (n_words) HIPCHK(hipMemcpyAsync(dev, words_host, n_words * sizeof(fe_t), hipMemcpyHostToDevice, s));
+  WsLayout L;
+  const uint64_t off_words = L.take(n_words * sizeof(fe_t)), off_woff = L.take(((uint64_t)jobs + 1) * 8), off_soff = L.take(((uint64_t)jobs + 1) * 8), off_sq = L.take(n_sq * 4),
+                 off_out = L.take(n_sq * sizeof(fe_t));
+  char *dev; CHK(ws_get("io.poseidon", L.total(), (void **)&dev));
+  if (n_words) HIPCHK(hipMemcpyAsync(dev + off_words, words_host, n_words * sizeof(fe_t), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dev + off_woff, word_offsets_host, ((size_t)jobs + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dev + off_soff, squeeze_offsets_host, ((size_t)jobs + 1) * 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dev + off_sq, squeeze_at_host, n_sq * 4, hipMemcpyHostToDevice, s));
   {
     Scope sp("poseidon_transcripts", s);
-    hipLaunchKernelGGL(k_poseidon_transcripts, dim3(ceil_div(jobs, POS_LANES)), dim3(POS_LANES), 0, s, (const fe_t *)tab, (const fe_t *)dev, (const uint64_t *)(dev + off_woff),
+    hipLaunchKernelGGL(k_poseidon_transcripts, dim3(ceil_div(jobs, POS_LANES)), dim3(POS_LANES), 0, s, (const fe_t *)tab, (const fe_t *)(dev + off_words), (const uint64_t *)(dev + off_woff),
                        (const uint32_t *)(dev + off_sq), (const uint64_t *)(dev + off_soff), jobs, (fe_t *)(dev + off_out));
     HIPCHK(hipGetLastError());
   }

@@ -24,9 +24,11 @@
 #include "g1.hpp"
 #include "g1_29.hpp"
 #include "ntt_types.hpp"
+#include "ws_layout.hpp"
 
 namespace mi355 {
 using namespace zk;
+using mi355zk::WsLayout;
 
 extern thread_local std::string g_err;
 int fail(int code, const std::string &msg);
@@ -163,6 +165,21 @@ struct MsmGuard {   // slot 0, plus every other bound slot when the process driv
   MsmGuard() { lk[0] = std::unique_lock<std::mutex>(g_ctx_mu[0]); for (int i = 1; i < g_ndev && i < MAX_DEV; i++) lk[i] = std::unique_lock<std::mutex>(g_ctx_mu[i]); }
 };
 
+// One pooled mi355_buf block, back in the pool when its owner leaves scope -- on every exit path, so the body of an entry point uses HIPCHK / CHK and plain returns.  Declare it
+// AFTER the DevGuard: the block then goes back (its free event is recorded on the owner's stream, behind everything queued so far) before the device lock is released.  The
+// result of mi355_buf_free is ignored, and g_err is written by fail() alone: the error text of a failed body survives the destructor unless the free itself fails (it can,
+// after a sticky HIP error in the body: its event record then writes its own text).
+struct PoolBlock {
+  void *p = nullptr; int slot = 0;
+  PoolBlock() = default;
+  PoolBlock(const PoolBlock &) = delete; PoolBlock &operator=(const PoolBlock &) = delete;
+  ~PoolBlock() { if (p) (void)mi355_buf_free(p); }
+  int alloc(uint64_t bytes, int slot_) { slot = slot_; return mi355_buf_alloc(bytes, slot_, &p); }   // binds slot_'s context on the calling thread (need_init)
+  char *at(uint64_t off) const { return (char *)p + off; }
+  // host memory -> the block, on the copy stream (mi355_buf_upload: work queued afterwards on the compute stream waits for it); the owner's context is bound again afterwards
+  int upload(uint64_t off, const void *src_host, uint64_t bytes);
+};
+
 // per-THREAD MSM options (mi355_msm_set_normalise / _set_window_bits): a rayon worker that asks for un-normalised partial sums must not
 // change what another worker's commit returns (SURVEY 8b "Threading")
 struct MsmOpts { bool normalise = true; int force_c = 0; bool no_tables = false; };
@@ -173,6 +190,7 @@ inline void use_ctx(int slot) { g_cur = &g_ctx[slot]; }
 // create_proof (rayon workers included, SURVEY 8b "Threading"), so the bound device is re-selected on the calling thread each time.
 int bind_ctx(int slot);
 int need_init(int slot = 0);
+inline int PoolBlock::upload(uint64_t off, const void *src_host, uint64_t bytes) { CHK(mi355_buf_upload(at(off), src_host, bytes)); return need_init(slot); }
 
 // MI355_TRACE: per-call counters for the integrator (metrics / logging)
 struct CallTrace {
@@ -252,6 +270,8 @@ int slot_of(const void *dev_ptr, bool touch = true);
 int buf_check_range(const void *dev_ptr, uint64_t bytes, const char *who);   // MI355_EBADARG when [dev_ptr, dev_ptr + bytes) leaves the library block that holds dev_ptr
 // the slot that owns ALL of the given device pointers (null pointers ignored); MI355_EBADARG when they live on different devices
 int common_slot(std::initializer_list<const void *> ptrs, int *slot_out, const char *who);
+// the same over a host table of `count` device pointers (the columns of a witness, the vectors of a batch); touch as in slot_of
+int common_slot(const void *const *ptrs, size_t count, bool touch, int *slot_out, const char *who);
 // round-robin choice of a device for a host-pointer call (replicas: any bound device can run it); prefers a device whose lock is free
 int pick_replica_slot();
 

@@ -200,17 +200,18 @@ int slot_of(const void *dev_ptr, bool touch) {
   else (void)hipGetLastError();
   return 0;
 }
-int common_slot(std::initializer_list<const void *> ptrs, int *slot_out, const char *who) {
+int common_slot(const void *const *ptrs, size_t count, bool touch, int *slot_out, const char *who) {
   int slot = -1;
-  for (const void *p : ptrs) {
-    if (!p) continue;
-    const int s = slot_of(p);
+  for (size_t j = 0; ptrs && j < count; j++) {
+    if (!ptrs[j]) continue;
+    const int s = slot_of(ptrs[j], touch);
     if (slot < 0) slot = s;
     else if (s != slot && g_ctx[s].device != g_ctx[slot].device) return fail(MI355_EBADARG, std::string(who) + ": the operands live on different devices (copy one with mi355_buf_copy first)");
   }
   *slot_out = slot < 0 ? 0 : slot;
   return MI355_OK;
 }
+int common_slot(std::initializer_list<const void *> ptrs, int *slot_out, const char *who) { return common_slot(ptrs.begin(), ptrs.size(), true, slot_out, who); }
 int pick_replica_slot() {
   const int D = g_ndev;
   if (D <= 1) return 0;

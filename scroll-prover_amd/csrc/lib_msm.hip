@@ -589,40 +589,40 @@ static int stream_file_to_device(FILE *f, void *dev, size_t bytes, void *pinned[
 // SerdeFormat::Processed: the 32-byte words of one shard.  Chunk i + 1 is read and copied (a stream of its own) while chunk i is decompressed on the library
 // stream straight into the shard: two pinned host buffers, the two halves of one pooled device block.  *bad_out: the smallest rejected index of the basis, or ~0.
 static int stream_processed_to_shard(FILE *f, const Shard &sh, void *pinned[2], size_t chunk_pts, unsigned long long *bad_out) {
-  void *stage = nullptr; CHK(mi355_buf_alloc(2 * chunk_pts * 32, sh.slot, &stage));
-  hipStream_t cs = nullptr; hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
-  const int rc = [&]() -> int {
-    unsigned long long *err; CHK(ws_get("g1codec.err", 8, (void **)&err));
-    HIPCHK(hipMemsetAsync(err, 0xff, 8, g.stream));
-    HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-      HIPCHK(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&used[i], hipEventDisableTiming));
-      HIPCHK(hipEventRecord(copied[i], cs)); HIPCHK(hipEventRecord(used[i], g.stream));
+  PoolBlock stage; CHK(stage.alloc(2 * chunk_pts * 32, sh.slot));
+  struct Side {   // the copy stream and the events of the two halves.  Declared after the block: on every return both streams are drained, these go, and then the block is freed
+    hipStream_t cs = nullptr; hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
+    ~Side() {
+      if (cs) (void)hipStreamSynchronize(cs);
+      (void)hipStreamSynchronize(g.stream);
+      for (int i = 0; i < 2; i++) { if (copied[i]) (void)hipEventDestroy(copied[i]); if (used[i]) (void)hipEventDestroy(used[i]); }
+      if (cs) (void)hipStreamDestroy(cs);
     }
-    uint64_t done = 0; int which = 0;
-    while (done < sh.n) {
-      const uint64_t len = std::min<uint64_t>(chunk_pts, sh.n - done);
-      char *half = (char *)stage + (size_t)which * chunk_pts * 32;
-      HIPCHK(hipEventSynchronize(copied[which]));                       // the previous copy out of this pinned buffer has finished
-      if (fread(pinned[which], 1, len * 32, f) != len * 32) return fail(MI355_EBADARG, "srs_load_params_file: short read");
-      HIPCHK(hipStreamWaitEvent(cs, used[which], 0));                   // the kernel that read this half of the device block has finished
-      HIPCHK(hipMemcpyAsync(half, pinned[which], len * 32, hipMemcpyHostToDevice, cs));
-      HIPCHK(hipEventRecord(copied[which], cs));
-      HIPCHK(hipStreamWaitEvent(g.stream, copied[which], 0));
-      CHK(launch_g1_decompress(half, sh.dev + done, len, sh.lo + done, err));
-      HIPCHK(hipEventRecord(used[which], g.stream));
-      done += len; which ^= 1;
-    }
-    HIPCHK(hipMemcpyAsync(bad_out, err, 8, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    return MI355_OK;
-  }();
-  if (cs) { (void)hipStreamSynchronize(cs); }
-  (void)hipStreamSynchronize(g.stream);
-  for (int i = 0; i < 2; i++) { if (copied[i]) (void)hipEventDestroy(copied[i]); if (used[i]) (void)hipEventDestroy(used[i]); }
-  if (cs) (void)hipStreamDestroy(cs);
-  (void)mi355_buf_free(stage);
-  return rc;
+  } sd;
+  unsigned long long *err; CHK(ws_get("g1codec.err", 8, (void **)&err));
+  HIPCHK(hipMemsetAsync(err, 0xff, 8, g.stream));
+  HIPCHK(hipStreamCreateWithFlags(&sd.cs, hipStreamNonBlocking));
+  for (int i = 0; i < 2; i++) {
+    HIPCHK(hipEventCreateWithFlags(&sd.copied[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&sd.used[i], hipEventDisableTiming));
+    HIPCHK(hipEventRecord(sd.copied[i], sd.cs)); HIPCHK(hipEventRecord(sd.used[i], g.stream));
+  }
+  uint64_t done = 0; int which = 0;
+  while (done < sh.n) {
+    const uint64_t len = std::min<uint64_t>(chunk_pts, sh.n - done);
+    char *half = stage.at((uint64_t)which * chunk_pts * 32);
+    HIPCHK(hipEventSynchronize(sd.copied[which]));                       // the previous copy out of this pinned buffer has finished
+    if (fread(pinned[which], 1, len * 32, f) != len * 32) return fail(MI355_EBADARG, "srs_load_params_file: short read");
+    HIPCHK(hipStreamWaitEvent(sd.cs, sd.used[which], 0));                // the kernel that read this half of the device block has finished
+    HIPCHK(hipMemcpyAsync(half, pinned[which], len * 32, hipMemcpyHostToDevice, sd.cs));
+    HIPCHK(hipEventRecord(sd.copied[which], sd.cs));
+    HIPCHK(hipStreamWaitEvent(g.stream, sd.copied[which], 0));
+    CHK(launch_g1_decompress(half, sh.dev + done, len, sh.lo + done, err));
+    HIPCHK(hipEventRecord(sd.used[which], g.stream));
+    done += len; which ^= 1;
+  }
+  HIPCHK(hipMemcpyAsync(bad_out, err, 8, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return MI355_OK;
 }
 int mi355_srs_load_params_file(const char *path, uint32_t flags, uint32_t *k_out, uint64_t *g_handle_out, uint64_t *g_lagrange_handle_out, void *g2_out, void *s_g2_out) {
   return guarded([&]() -> int {
