@@ -1,7 +1,7 @@
-// lib_common.hpp -- host-side state shared by the translation units of libmi355zk.so (lib_core / lib_msm / lib_ntt / lib_aux .hip):
-// device contexts, the per-device locks, SRS handles, the workspace arena, the resident-buffer registry, HIP-event profiling and the
-// error plumbing of the C-ABI (include/mi355zk.h).  Host logic only; no kernel is declared here -- every lib_*.hip includes the
-// kernel headers it launches and nothing else, so a change to one kernel family rebuilds one translation unit.
+// lib_common.hpp -- host-side state shared by the translation units of libmi355zk.so (lib_core / lib_msm / lib_ntt / lib_aux / lib_pairing .hip): device contexts with their
+// knobs (knobs.hpp), streams and events, the per-device locks, SRS handles, the workspace arena, the slot look-ups of the resident-buffer registry, HIP-event profiling and the
+// error plumbing of the C-ABI (include/mi355zk.h).  Host logic only; no kernel is declared here -- every lib_*.hip includes the kernel headers it launches and nothing else, so a
+// change to one kernel family rebuilds one translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -25,6 +25,7 @@
 #include "g1_29.hpp"
 #include "ntt_types.hpp"
 #include "ws_layout.hpp"
+#include "knobs.hpp"
 
 namespace mi355 {
 using namespace zk;
@@ -72,61 +73,49 @@ struct Prof { double ms = 0; uint64_t launches = 0; };
 struct MsmSlot { int id = 0; hipEvent_t sorted = nullptr, acc_done = nullptr, red_done = nullptr; bool used = false; };   // per-chunk buffers + events of the pipelined MSM
 
 struct Span { std::string name; hipEvent_t a, b; };
-struct Ctx {
+// One bound device.  The environment knobs (seg_fill, ntt_tile_log, trace, ...) are the Knobs base: csrc/knobs.hpp is their table, DESIGN.md section 10 their description.
+struct Ctx : mi355zk::Knobs {
   bool inited = false;
   int slot = 0;                 // index in g_ctx (0 = primary)
-  std::vector<Span> spans;      // profiling: (name, start, stop) event pairs resolved after the stream is idle
-  void *comm = nullptr;         // ncclComm_t of this device (mi355_init_multi with distinct devices)
-  hipEvent_t ev_xchg = nullptr;
-  hipEvent_t ev_xchg2 = nullptr;   // recorded behind a cross-slot mi355_buf_copy on the destination's stream; the source slot's stream waits for it
-  // host-pointer MSM: chunked copy on its own stream, overlapped with the digit extraction (msm_host_single); also the stream the
-  // resident-buffer uploads run on (mi355_buf_upload)
-  hipStream_t copy_stream = nullptr; hipEvent_t ev_copy[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_up_fork = nullptr;   // mi355_buf_upload into a block in use: recorded on the compute stream, awaited by the copy stream (upload mutex)
-  hipEvent_t ev_up[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; uint32_t up_next = 0;   // uploads on copy_stream (ring: several threads may upload at once); the compute stream waits for each
-  uint32_t host_slice_min_log = 22;   // MI355_HOST_SLICE_MIN_LOG: smallest log2(n) the host-pointer MSM cuts into slices (tests lower it)
-  uint32_t host_batch_overlap = 1;   // MI355_HOST_BATCH_OVERLAP=0: the host-pointer batch transforms copy and compute one item at a time (no helper thread)
-  uint32_t host_chunks = 8;     // MI355_HOST_CHUNKS: upper bound on the point-range slices of the host-pointer MSM (1 = one copy, then compute)
   int device = -1;
   hipDeviceProp_t prop;
+  // streams (ctx_streams below lists the owned ones once, for init_ctx / destroy_ctx / sync_streams).  `stream` is the compute stream: own_stream, or the caller's (mi355_set_stream)
   hipStream_t own_stream = nullptr, stream = nullptr;
   hipStream_t aux_stream[2] = {nullptr, nullptr};   // side streams of the pipelined MSM (sort | reduction); the accumulation stays on `stream`
-  hipEvent_t ev_fork = nullptr;
+  hipStream_t copy_stream = nullptr;   // the chunked copy of the host-pointer MSM (msm_host_single) and the resident-buffer uploads (mi355_buf_upload)
+  // events (ctx_events below lists them once), all without timing
   MsmSlot msm_slot[2];
+  hipEvent_t ev_fork = nullptr;
+  hipEvent_t ev_xchg = nullptr;
+  hipEvent_t ev_xchg2 = nullptr;   // recorded behind a cross-slot mi355_buf_copy on the destination's stream; the source slot's stream waits for it
+  hipEvent_t ev_copy[4] = {};
+  hipEvent_t ev_up[8] = {}; uint32_t up_next = 0;   // uploads on copy_stream (ring: several threads may upload at once), under the upload mutex
+  hipEvent_t ev_up_fork = nullptr;   // mi355_buf_upload into a block in use: recorded on the compute stream, awaited by the copy stream (upload mutex)
+  void *comm = nullptr;         // ncclComm_t of this device (mi355_init_multi with distinct devices)
   std::vector<const fe_t *> polys_stage;
-  uint32_t msm_chunks = 1;       // MI355_MSM_CHUNKS / mi355_msm_set_pipeline (off by default: measured slower)
-  uint32_t msm_chunk_min_log = 23;
+  uint32_t msm_chunk_min_log = 23;   // mi355_msm_set_pipeline
   int last_chunks = 1;
   std::map<std::string, Buf> ws;           // grow-only workspace arena, keyed by role
   std::map<std::string, NttPlan> ntt_plans;  // key = log_n | omega bytes
   g1_affine_t *fixed_base_table = nullptr;
-  uint32_t sort_t2 = 0;         // MI355_SORT_T2 = 8192 | 16384 (0: by size)
-  uint32_t seg_factor = 16;
-  uint32_t sort_fb = 11;        // MI355_SORT_FB: fine (level-2) key bits of the sorter, 9..12
-  uint32_t sort_split = 1;      // MI355_SORT_SPLIT: the level-1 output is two streams (payload u32 + fine key u16); 1 = 24 576-entry tiles where the bin bookkeeping leaves room, 2 = 16 384-entry tiles (the single-stream u64 records were an A/B path of round 3 and left the library in round 6)
-  uint32_t reduce_chains = 131072;   // MI355_REDUCE_CHAINS: target number of running-sum chains of the bucket reduction
-  uint32_t seg_fill = 40, seg_fill_segfix = 40;   // MI355_SEG_FILL / MI355_SEG_FILL_SEGFIX (even, 2..100 %: above 100 the segments would no longer cover the entries): share of the launched accumulate threads the actual entries are spread over
-  uint32_t seg_min = 16;             // MI355_SEG_MIN: shortest accumulate segment (entries per thread) when few digits are non-zero
-  uint32_t fixup_mode = 2;           // MI355_FIXUP_MODE: 2 = by shape (see msm_enqueue), 0 = per-bucket kernels (four lanes / workgroup / several workgroups per bucket), 1 = one segmented reduction over the partial sums (k_msm_segfix: measured better for two-partial buckets, worse for spans of 15-30, profiles/r02b_segfix_ab.log)
-  uint32_t fixup_huge_min = 2048;    // MI355_FIXUP_HUGE_MIN (>= 2048): bucket spans from this many accumulate threads on are summed by several workgroups
-  uint32_t fixup_serial_max = 32;    // MI355_FIXUP_SERIAL_MAX: bucket spans (in accumulate threads) above this go to the workgroup-per-bucket fix-up
-  uint32_t fixup_lanes_max_log = 17;  // MI355_FIXUP_LANES_MAX_LOG: bucket sets up to 2^this records take the four-lanes-per-bucket fix-up
-  uint32_t tail_coop_mask = 15;      // MI355_TAIL_COOP_MASK: which tail kernels may take the quad form (1 fix-up, 2 running sums, 4 trees, 8 final Horner)
-  uint32_t tail_coop_max = 65536;    // MI355_TAIL_COOP_MAX: reduction-tail kernels with at most this many logical threads run the quad-cooperative (latency) form of the point addition; 0 disables
-  uint32_t reduce_min_chunk = 4;     // MI355_REDUCE_MIN_CHUNK: shortest running-sum chain (buckets per reduce thread) small bucket sets are cut into
-  uint32_t sort_t1 = 16384;     // MI355_SORT_T1=8192 selects the smaller level-1 tile (2 workgroups per CU)
-  uint32_t ntt_direct2_max_log = 25;   // MI355_NTT_DIRECT2_MAX_LOG: levels up to 2^this elements read their inter-level twiddles from a full [k][column] table (36 B per element of the level: 0.6 GB at 2^24; tables of 256 MB and more only while HBM has the table + max(16 GiB, 1/12 of the device) to spare, lib_ntt.hip hbm_spare_for_table; otherwise, and above the cap, the level multiplies two half-size table entries per element).  At 2^26 the 2.4 GB table buys 0.5 % (8.53 vs 8.58 ms, profiles/r06_direct2_k26_ab.json; round 3 had measured 1.7 %), so the default stops at 2^25; 0 disables
-  uint32_t ntt_coset_fold_max_log = 26;  // MI355_NTT_COSET_FOLD_MAX_LOG: coset transforms up to 2^this fold distribute_powers into their first pass (one 36 B x 2^log_n table per coset factor: 38 MB at 2^20, 0.6 GB at 2^24, 2.4 GB at 2^26; tables of 256 MB and more are only built while HBM has the table + max(16 GiB, 1/12 of the device) to spare -- otherwise, and above the cap, the separate pass runs); 0: always the separate k_distribute_powers pass
-  uint32_t ntt_direct2_min_log = 0;   // MI355_NTT_DIRECT2_MIN_LOG: levels of at least 2^this elements read their inter-level twiddles from the [k][column] table (coalesced, next to the data); smaller ones gather from ONE 1-D table w_S^e by e = column k.  Round 6: 0 (every level) -- the gather cost more than it looked: 2^20 transform 111.5 -> 103 us, 2^18 26.1 -> 25.3, 2^24 1 965 -> 1 932, 2^26 8.89 -> 8.73 ms (profiles/r06_direct2_small_levels_ab.json; 21 restores round 5)
-  uint32_t ntt_fold_scale = 1;  // MI355_NTT_FOLD_SCALE=0: the inverse transform's divisor stays a multiplication in the closing pass
-  uint32_t ntt_batch_max_log = 22;       // MI355_NTT_BATCH_MAX_LOG: the batch entry points run transforms up to 2^this as batched launches (blockIdx.y = polynomial); 0: always the loop of single transforms
-  uint32_t ntt_two_level_max_log = 18;   // MI355_NTT_TWO_LEVEL_MAX_LOG (18..20): transforms up to 2^this run as two passes instead of three
-  uint32_t ntt_tile_log = 11;   // log2 of the LDS tile in elements (MI355_NTT_TILE_LOG)
   bool profiling = false;
-  bool trace = false;           // MI355_TRACE=1: one stderr line per MSM / NTT call (host wall time; device transforms are synchronised for it)
+  std::vector<Span> spans;      // profiling: (name, start, stop) event pairs resolved after the stream is idle
   std::map<std::string, Prof> prof;
   int last_c = 0, last_w = 0; uint64_t last_entries = 0; bool last_shared = false; int last_host_slices = 1;
 };
+// The streams a context owns, in creation order, and every event it owns: init_ctx creates from these lists and destroy_ctx destroys from them, so a new member is named once.
+enum : unsigned { SYNC_COMPUTE = 1, SYNC_AUX = 2, SYNC_COPY = 4 };
+struct CtxStream { hipStream_t *s; unsigned kind; };
+inline std::vector<CtxStream> ctx_streams(Ctx &c) { return {{&c.own_stream, SYNC_COMPUTE}, {&c.aux_stream[0], SYNC_AUX}, {&c.aux_stream[1], SYNC_AUX}, {&c.copy_stream, SYNC_COPY}}; }
+inline std::vector<hipEvent_t *> ctx_events(Ctx &c) {
+  std::vector<hipEvent_t *> v = {&c.ev_fork, &c.ev_xchg, &c.ev_xchg2, &c.ev_up_fork};
+  for (auto &m : c.msm_slot) { v.push_back(&m.sorted); v.push_back(&m.acc_done); v.push_back(&m.red_done); }
+  for (auto &e : c.ev_copy) v.push_back(&e);
+  for (auto &e : c.ev_up) v.push_back(&e);
+  return v;
+}
+// waits for the streams of `which` (SYNC_COMPUTE is c.stream, the caller's stream included; streams not yet created are skipped); every stream is waited for, the first error is returned
+hipError_t sync_streams(Ctx &c, unsigned which);
 
 // One context per bound device; slot 0 is the primary.  LOCKING (round 3): one mutex PER DEVICE SLOT instead of one for the library.
 //   * an entry point that works on one device (every transform, scan, evaluation, element-wise operation, buffer copy) holds that slot's
@@ -142,15 +131,13 @@ extern std::mutex g_upload_mu[MAX_DEV];
 extern Ctx g_ctx[MAX_DEV];
 extern int g_ndev;
 extern bool g_dup_devices;     // test mode: the same physical device bound to several slots (exchange by device copies instead of RCCL)
-extern uint32_t g_shard_min_log;  // MI355_SHARD_MIN_LOG: a basis with fewer than 2^this points per device stays on the primary device (tests lower it)
 extern bool g_peer_ok[MAX_DEV][MAX_DEV];   // [s][t]: kernels on slot s may read memory of slot t directly
-extern bool g_force_exchange;  // MI355_MULTI_FORCE=1: take the sharded path (partials + exchange + fold) even with one device
+extern mi355zk::ProcessKnobs g_proc;   // the per-process knobs of mi355_init_multi (csrc/knobs.hpp): shard_min_log, multi_force, msm_auto_max_c
 extern thread_local Ctx *g_cur;
 #define g (*::mi355::g_cur)
 extern std::unordered_map<uint64_t, Srs> &g_srs;   // heap-allocated, never destroyed (no HIP calls from static destruction)
 extern uint64_t g_next_handle;
 extern int g_last_devices; extern const char *g_last_exchange;
-extern int g_auto_max_c;          // MI355_MSM_AUTO_MAX_C (22..24): widest window the automatic choices may take
 
 struct DevGuard {   // one device slot
   std::unique_lock<std::mutex> lk;
@@ -263,7 +250,7 @@ int srs_alloc(SrsMem &mem, uint64_t n);
 int srs_scatter_from_primary(SrsMem &mem, const g1_affine_t *src_dev, uint64_t n, bool alias_shard0);
 int srs_gather_to_primary(const Srs &sr, uint64_t n, const g1_affine_t **out);
 
-// ---- resident buffers (mi355_buf_*, lib_core.hip): which device slot owns a device pointer.  Pointers handed out by mi355_buf_alloc are
+// ---- resident buffers (mi355_buf_*, lib_core.hip over buf_registry.hpp): which device slot owns a device pointer.  Pointers handed out by mi355_buf_alloc are
 // looked up in the registry; anything else (a torch tensor, an SRS pointer) is asked of the HIP runtime when several devices are bound.
 // `touch` marks a registered block as used by queued work (an upload into it must then wait for the compute stream).
 int slot_of(const void *dev_ptr, bool touch = true);
@@ -287,7 +274,7 @@ int launch_g1_decompress(const void *bytes_dev, void *affine_out_dev, uint64_t n
 // the two G2 points of a Processed params file, decoded on the host (64 bytes -> 128-byte G2Affine); false for a word that is no point of the twist
 bool g2_decode_host(const uint8_t in[64], void *g2affine_out);
 // window-cost model shared by the MSM launch code and mi355_srs_precompute
-constexpr int MSM_SCALAR_BITS = 255, MSM_MAX_C = 24;   // hard limit of the sorter (23 key bits); the automatic choices stop at g_auto_max_c
+constexpr int MSM_SCALAR_BITS = 255, MSM_MAX_C = 24;   // hard limit of the sorter (23 key bits); the automatic choices stop at g_proc.msm_auto_max_c
 double msm_cost(uint64_t n, int c, bool shared);
 
 // ---- small helpers shared by the transform entry points (lib_ntt.hip, lib_aux.hip)

@@ -1,11 +1,12 @@
-// lib_core.hip -- libmi355zk.so, host state and the part of the C-ABI (include/mi355zk.h) that launches no kernel: lifecycle
-// (mi355_init / _init_multi / _shutdown, streams), the per-device locks, SRS handle bookkeeping (register / prefix / release / read-back),
-// the resident-buffer API (mi355_buf_*), the RCCL binding, HIP-event profiling.  There is deliberately no CPU fallback: without a gfx950
+// lib_core.hip -- libmi355zk.so, host state and the part of the C-ABI (include/mi355zk.h) that launches no kernel: lifecycle (mi355_init / _init_multi / _shutdown, streams),
+// the per-device contexts and their locks, SRS handle bookkeeping (register / prefix / release / read-back), the resident-buffer API (mi355_buf_*), the RCCL binding, HIP-event
+// profiling.  What needs no HIP lives in plain headers this file drives: the environment variables in knobs.hpp, the buffer bookkeeping and its allocation order in
+// buf_registry.hpp over slab_ranges.hpp; a context's streams and events are listed once, next to Ctx in lib_common.hpp.  There is deliberately no CPU fallback: without a gfx950
 // device every compute entry point returns MI355_ENODEVICE.
 #include <dlfcn.h>
 
 #include "lib_common.hpp"
-#include "slab_ranges.hpp"
+#include "buf_registry.hpp"
 
 namespace mi355 {
 
@@ -17,8 +18,7 @@ std::mutex g_upload_mu[MAX_DEV];   // mi355_buf_upload's bookkeeping (event ring
 Ctx g_ctx[MAX_DEV];
 int g_ndev = 0;
 bool g_dup_devices = false;
-uint32_t g_shard_min_log = 14;
-bool g_force_exchange = false;
+mi355zk::ProcessKnobs g_proc;
 bool g_peer_ok[MAX_DEV][MAX_DEV] = {};   // [s][t]: kernels on slot s may dereference memory of slot t (same device, or hipDeviceEnablePeerAccess succeeded)
 thread_local Ctx *g_cur = &g_ctx[0];
 // The handle table is heap-allocated and never destroyed: the destructors of its entries (SrsMem / SrsTables) call hipFree, and a process
@@ -27,7 +27,6 @@ thread_local Ctx *g_cur = &g_ctx[0];
 std::unordered_map<uint64_t, Srs> &g_srs = *new std::unordered_map<uint64_t, Srs>();
 uint64_t g_next_handle = 1;
 int g_last_devices = 1; const char *g_last_exchange = "none";
-int g_auto_max_c = 22;
 thread_local MsmOpts t_opts;
 Rccl g_rccl;
 
@@ -77,12 +76,19 @@ int dev_malloc(void **out, size_t bytes, const char *what) {
   return MI355_OK;
 }
 
+hipError_t sync_streams(Ctx &c, unsigned which) {
+  hipError_t first = hipSuccess;
+  auto wait = [&](hipStream_t st) { const hipError_t e = hipStreamSynchronize(st); if (first == hipSuccess) first = e; };
+  if (which & SYNC_COMPUTE) wait(c.stream);
+  for (const CtxStream &cs : ctx_streams(c)) if (cs.kind != SYNC_COMPUTE && (which & cs.kind) && *cs.s) wait(*cs.s);
+  return first;
+}
+
 int ws_get(const char *role, size_t bytes, void **out) {
   Buf &b = g.ws[role];
   if (b.cap < bytes) {
     if (b.p) {   // every stream that may still touch the old block: compute, the two auxiliary streams, and the copy stream (host-pointer entry points stage through workspace blocks)
-      HIPCHK(hipStreamSynchronize(g.stream)); for (int i = 0; i < 2; i++) if (g.aux_stream[i]) HIPCHK(hipStreamSynchronize(g.aux_stream[i]));
-      if (g.copy_stream) HIPCHK(hipStreamSynchronize(g.copy_stream));
+      HIPCHK(sync_streams(g, SYNC_COMPUTE | SYNC_AUX | SYNC_COPY));
       HIPCHK(hipFree(b.p)); b.p = nullptr; b.cap = 0;
     }
     size_t cap = bytes + bytes / 8 + 256;
@@ -95,8 +101,7 @@ int ws_get(const char *role, size_t bytes, void **out) {
 
 void resolve_spans() {
   if (g.spans.empty()) return;
-  (void)hipStreamSynchronize(g.stream);
-  for (int i = 0; i < 2; i++) if (g.aux_stream[i]) (void)hipStreamSynchronize(g.aux_stream[i]);
+  (void)sync_streams(g, SYNC_COMPUTE | SYNC_AUX);
   for (auto &s : g.spans) { float ms = 0; (void)hipEventElapsedTime(&ms, s.a, s.b); Prof &p = g.prof[s.name]; p.ms += ms; p.launches++; (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
   g.spans.clear();
 }
@@ -133,66 +138,71 @@ static int rccl_load() {
 }
 
 // ------------------------------------------------------------------------------------------------ resident buffers
-// A block handed out by mi355_buf_alloc.  free_ev: recorded on the owner's compute stream when the block was last returned to the pool --
-// the only work an upload into the recycled block has to wait for.  used: the block has been passed to a library call since it was
-// allocated (an upload into it must then wait for the whole compute stream).
-struct BufBlock { void *p = nullptr; size_t bytes = 0; int slot = 0; hipEvent_t free_ev = nullptr; bool used = false; bool arena = false; };
+// The bookkeeping -- live blocks, the pool of freed blocks by exact size, the slabs blocks are carved from, and the order in which an allocation tries them -- is
+// csrc/buf_registry.hpp (plain C++, model-checked on the host).  This file keeps what calls HIP, and g_buf_mu, the one mutex every registry call runs under.
+// Slabs (round 5): the pool alone is right for one layer's proofs in a row (the second proof allocates nothing), wrong for a prover process that holds several layers -- a chunk
+// prover runs 2^20-, 2^24- and 2^25-row proofs back to back [REF integration/src/prove.rs:30-43], every layer's blocks have another size and the working sets do not fit HBM
+// together (profiles/r05_prover_process_*.json) -- so blocks are carved out of slabs (hipMalloc'd once, >= MI355_BUF_SLAB_MB each, default 1 GiB).  A range only enters a slab's
+// free list after the last use of the block it came from has COMPLETED (retire_blocks synchronises its free event first), so a carved block is fresh: an upload into it waits for
+// nothing.  Slabs go back to HIP when they are entirely free and somebody needs the memory (mi355_buf_trim, an out-of-memory retry, shutdown).  MI355_BUF_ARENA=0 restores one
+// hipMalloc per block.  Both variables are read once per process.
+using mi355zk::BufBlock;
 static std::mutex g_buf_mu;
-static std::map<uintptr_t, BufBlock> &g_bufs = *new std::map<uintptr_t, BufBlock>();                         // live blocks by base address
-static std::multimap<std::pair<int, size_t>, BufBlock> &g_pool = *new std::multimap<std::pair<int, size_t>, BufBlock>();   // free blocks by (slot, size)
+static mi355zk::BufRegistry &g_reg = *new mi355zk::BufRegistry();   // heap-allocated, never destroyed (as g_srs)
 static std::atomic<uint32_t> g_rr{0};
-// Slabs (round 5).  The pool above keeps freed blocks by EXACT size: right for one layer's proofs in a row (the second proof allocates nothing), wrong for a prover process that
-// holds several layers -- a chunk prover runs 2^20-, 2^24- and 2^25-row proofs back to back [REF integration/src/prove.rs:30-43], every layer's blocks have another size, the working
-// sets do not fit HBM together, and each proof used to give the previous layer's blocks back to HIP and hipMalloc its own (measured: 8.4 s per chunk round against 4.3 s for the three
-// layers alone, profiles/r05_prover_process_*.json).  Now blocks are CARVED out of slabs (hipMalloc'd once, >= MI355_BUF_SLAB_MB each, default 1 GiB; a larger request gets a slab of its
-// own size).  Order on a pool miss: carve from the free ranges; else move this device's pooled blocks into the free ranges (adjacent ranges of one slab coalesce) and carve; else a new
-// slab.  A range only enters the free list after the last use of the block it came from has COMPLETED (its free event is synchronised first -- the events of a previous layer's proof are
-// long done), so a carved block is fresh: an upload into it waits for nothing, exactly like a block straight from hipMalloc.  Slabs go back to HIP when they are entirely free and
-// somebody needs the memory (mi355_buf_trim, an out-of-memory retry, shutdown).  MI355_BUF_ARENA=0 restores one hipMalloc per block.
-static mi355zk::SlabRanges *g_arena = new mi355zk::SlabRanges[MAX_DEV];   // per device slot: its slabs and their quiescent free ranges (csrc/slab_ranges.hpp, model-checked on the host)
-static bool arena_on() { static const bool on = [] { const char *e = getenv("MI355_BUF_ARENA"); return !(e && e[0] == '0'); }(); return on; }
-static size_t slab_min_bytes() { static const size_t v = [] { const char *e = getenv("MI355_BUF_SLAB_MB"); const long mb = e ? atol(e) : 1024; return (size_t)std::max<long>(1, mb) << 20; }(); return v; }
-// this device's pooled blocks -> free ranges (the calling thread is bound to the device: events are synchronised outside the registry mutex).  The copy stream is drained as well: a
-// block's free event only covers the compute stream, and an upload that was queued into a block and never consumed before its mi355_buf_free must not land in whatever is carved there next
+static const mi355zk::SlabPolicy &slab_policy() {
+  static const mi355zk::SlabPolicy pol = [] {
+    mi355zk::SlabPolicy q;
+    if (const char *e = getenv("MI355_BUF_ARENA")) q.on = e[0] != '0';
+    const char *m = getenv("MI355_BUF_SLAB_MB"); q.slab_min = (size_t)std::max<long>(1, m ? atol(m) : 1024) << 20;
+    return q;
+  }();
+  return pol;
+}
+// Blocks of ONE slot that have left the registry stop existing as blocks; the calling thread is bound to the slot's device, and no registry mutex is held while HIP waits.
+//   ToSlab: carved blocks return to their slab's free ranges, each after its free event has completed, and after the copy stream has drained: the free event only covers the
+//           compute stream, and an upload that was queued into a block and never consumed before its mi355_buf_free must not land in whatever is carved there next.
+//   ToHip:  the caller has synchronised the streams; directly allocated blocks are hipFree'd (carved ones only lose their event: their memory goes with the slab).  Returns bytes freed.
+enum class Retire { ToSlab, ToHip };
+static size_t retire_blocks(int slot, const std::vector<BufBlock> &blocks, Retire how) {
+  size_t freed = 0;
+  for (const auto &b : blocks) {
+    if (b.free_ev) { if (how == Retire::ToSlab) (void)hipEventSynchronize((hipEvent_t)b.free_ev); (void)hipEventDestroy((hipEvent_t)b.free_ev); }
+    if (how == Retire::ToHip && !b.arena && b.p) { (void)hipFree(b.p); freed += b.bytes; }
+  }
+  if (how == Retire::ToSlab && !blocks.empty()) {
+    (void)sync_streams(g_ctx[slot], SYNC_COPY);
+    std::lock_guard<std::mutex> bl(g_buf_mu);
+    g_reg.give_back(slot, blocks);
+  }
+  return freed;
+}
 static void arena_recycle_pool(int slot) {
   std::vector<BufBlock> take;
-  { std::lock_guard<std::mutex> bl(g_buf_mu); for (auto it = g_pool.begin(); it != g_pool.end();) { if (it->first.first == slot && it->second.arena) { take.push_back(it->second); it = g_pool.erase(it); } else ++it; } }
-  if (take.empty()) return;
-  for (auto &b : take) if (b.free_ev) { (void)hipEventSynchronize(b.free_ev); (void)hipEventDestroy(b.free_ev); }
-  if (g_ctx[slot].copy_stream) (void)hipStreamSynchronize(g_ctx[slot].copy_stream);
-  std::lock_guard<std::mutex> bl(g_buf_mu);
-  for (auto &b : take) g_arena[slot].insert((uintptr_t)b.p, b.bytes);
+  { std::lock_guard<std::mutex> bl(g_buf_mu); take = g_reg.take_pooled(slot, true); }
+  retire_blocks(slot, take, Retire::ToSlab);
 }
 // slabs of this device that are entirely free go back to HIP; returns the bytes freed
 static size_t arena_release_free_slabs(int slot) {
   std::vector<uintptr_t> drop; size_t freed = 0;
-  { std::lock_guard<std::mutex> bl(g_buf_mu); freed = g_arena[slot].take_whole_slabs(drop); }
+  { std::lock_guard<std::mutex> bl(g_buf_mu); freed = g_reg.arena[slot].take_whole_slabs(drop); }
   for (uintptr_t q : drop) (void)hipFree((void *)q);
   return freed;
 }
 
-static BufBlock *buf_find_locked(const void *p) {
-  auto it = g_bufs.upper_bound((uintptr_t)p);
-  if (it == g_bufs.begin()) return nullptr;
-  --it;
-  if ((uintptr_t)p < it->first + it->second.bytes) return &it->second;
-  return nullptr;
-}
-// a write of `bytes` starting at dev_ptr must stay inside the library block that holds dev_ptr (blocks are carved next to each other inside slabs: an overrun lands
-// in a neighbouring LIVE polynomial, not in a fault).  Pointers the library did not hand out (torch tensors, caller allocations) cannot be checked and pass.
+// a write of `bytes` starting at dev_ptr must stay inside the library block that holds dev_ptr.  Pointers the library did not hand out (torch tensors, caller allocations) cannot
+// be checked and pass.
 int buf_check_range(const void *dev_ptr, uint64_t bytes, const char *who) {
   std::lock_guard<std::mutex> lk(g_buf_mu);
-  if (BufBlock *b = buf_find_locked(dev_ptr)) {
-    const uint64_t off = (uint64_t)((uintptr_t)dev_ptr - (uintptr_t)b->p);
-    if (bytes > b->bytes - off) return fail(MI355_EBADARG, std::string(who) + ": range exceeds the block");
-  }
+  const BufBlock *b = g_reg.find(dev_ptr);
+  if (b && !g_reg.fits(*b, dev_ptr, bytes)) return fail(MI355_EBADARG, std::string(who) + ": range exceeds the block");
   return MI355_OK;
 }
 int slot_of(const void *dev_ptr, bool touch) {
   if (!dev_ptr) return 0;
   {
     std::lock_guard<std::mutex> lk(g_buf_mu);
-    if (BufBlock *b = buf_find_locked(dev_ptr)) { if (touch) b->used = true; return b->slot; }
+    if (BufBlock *b = g_reg.find(dev_ptr)) { if (touch) b->used = true; return b->slot; }
   }
   if (g_ndev <= 1) return 0;
   hipPointerAttribute_t a;
@@ -220,95 +230,50 @@ int pick_replica_slot() {
   return start;
 }
 // give the pooled (free) blocks of one device slot back to HIP.  Returns bytes freed.  Callers: dev_malloc on an out-of-memory retry -- reached WITH the slot's lock from the
-// compute entry points and WITHOUT it from mi355_buf_alloc -- and mi355_buf_trim.  The invariant that makes both safe: this function touches only state under g_buf_mu
-// (the pool map) plus thread-safe HIP calls (stream synchronisation, hipFree) on the calling thread's bound device; it must never read or write Ctx members that the
-// slot's lock protects (g.ws, the event rings, the plans).
+// compute entry points and WITHOUT it from mi355_buf_alloc.  The invariant that makes both safe: this function touches only state under g_buf_mu (the registry) plus
+// thread-safe HIP calls (stream synchronisation, hipFree) on the calling thread's bound device; it must never read or write Ctx members that the slot's lock protects
+// (g.ws, the event rings, the plans).
 static size_t pool_release_slot(int slot) {
-  std::vector<BufBlock> drop; bool any_arena = false;
-  { std::lock_guard<std::mutex> bl(g_buf_mu); for (auto it = g_pool.begin(); it != g_pool.end();) { if (it->first.first == slot && !it->second.arena) { drop.push_back(it->second); it = g_pool.erase(it); } else { any_arena = any_arena || (it->first.first == slot); ++it; } }
-    any_arena = any_arena || !g_arena[slot].free_ranges.empty(); }
-  if (drop.empty() && !any_arena) return 0;
-  (void)hipStreamSynchronize(g_ctx[slot].stream);   // work queued on a block before its mi355_buf_free
-  if (g_ctx[slot].copy_stream) (void)hipStreamSynchronize(g_ctx[slot].copy_stream);
-  size_t freed = 0;
-  for (auto &b : drop) { if (b.free_ev) (void)hipEventDestroy(b.free_ev); (void)hipFree(b.p); freed += b.bytes; }
+  std::vector<BufBlock> drop;
+  { std::lock_guard<std::mutex> bl(g_buf_mu); drop = g_reg.take_pooled(slot, false); if (drop.empty() && !g_reg.holds_carved(slot)) return 0; }
+  (void)sync_streams(g_ctx[slot], SYNC_COMPUTE | SYNC_COPY);   // work queued on a block before its mi355_buf_free
+  size_t freed = retire_blocks(slot, drop, Retire::ToHip);
   arena_recycle_pool(slot);                         // carved blocks return to their slabs; slabs that are whole again go back to HIP
-  freed += arena_release_free_slabs(slot);
-  return freed;
+  return freed + arena_release_free_slabs(slot);
 }
-static void buf_release_all_locked() {   // shutdown: every slot's lock is held, the devices are still bound
-  auto drop = [](BufBlock &b) {
-    if (b.slot < g_ndev && g_ctx[b.slot].inited) (void)hipSetDevice(g_ctx[b.slot].device);
-    if (b.free_ev) (void)hipEventDestroy(b.free_ev);
-    if (b.p && !b.arena) (void)hipFree(b.p);        // carved blocks are freed with their slabs below
-  };
-  for (auto &kv : g_bufs) drop(kv.second);
-  for (auto &kv : g_pool) drop(kv.second);
+static void buf_release_all_locked() {   // shutdown: every slot's lock and g_buf_mu are held, the compute streams are idle
   for (int d = 0; d < MAX_DEV; d++) {
-    if (!g_arena[d].slabs.empty() && d < g_ndev && g_ctx[d].inited) (void)hipSetDevice(g_ctx[d].device);
-    for (auto &sl : g_arena[d].slabs) (void)hipFree((void *)sl.base);
-    g_arena[d].clear();
+    const std::vector<BufBlock> all = g_reg.take_all(d);
+    if ((!all.empty() || !g_reg.arena[d].slabs.empty()) && d < g_ndev && g_ctx[d].inited) (void)hipSetDevice(g_ctx[d].device);
+    retire_blocks(d, all, Retire::ToHip);
+    for (auto &sl : g_reg.arena[d].slabs) (void)hipFree((void *)sl.base);
+    g_reg.arena[d].clear();
   }
-  g_bufs.clear(); g_pool.clear();
 }
 
 // ------------------------------------------------------------------------------------------------ contexts
 // everything mi355_init does for ONE device slot (the calling thread ends up bound to that device)
-static int init_ctx(int slot, int device_id) {
+static int init_ctx(int slot, int device_id, const mi355zk::Knobs &knobs) {
   use_ctx(slot);
   { const bool keep_profiling = g.profiling; g = Ctx(); g.profiling = keep_profiling; }   // mi355_profile_enable before mi355_init stays in force
+  static_cast<mi355zk::Knobs &>(g) = knobs;
   g.slot = slot;
   HIPCHK(hipSetDevice(device_id));
   g.device = device_id;                     // from here on destroy_ctx() releases whatever the steps below created
   HIPCHK(hipGetDeviceProperties(&g.prop, device_id));
   if (strncmp(g.prop.gcnArchName, "gfx950", 6) != 0) return fail(MI355_ENODEVICE, std::string("device is ") + g.prop.gcnArchName + ", this library is built for gfx950 only");
-  HIPCHK(hipStreamCreateWithFlags(&g.own_stream, hipStreamNonBlocking));
-  g.stream = g.own_stream;
-  for (int i = 0; i < 2; i++) {
-    { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); const char *e = getenv("MI355_AUX_PRIO"); const bool high = !(e && e[0] == '0');
-      HIPCHK(hipStreamCreateWithPriority(&g.aux_stream[i], hipStreamNonBlocking, high ? hi : lo)); }   // the side streams outrank the accumulation
-    g.msm_slot[i].id = i; g.msm_slot[i].used = false;
-    HIPCHK(hipEventCreateWithFlags(&g.msm_slot[i].sorted, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&g.msm_slot[i].acc_done, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&g.msm_slot[i].red_done, hipEventDisableTiming));
+  int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  for (const CtxStream &cs : ctx_streams(g)) {
+    if (cs.kind == SYNC_AUX) HIPCHK(hipStreamCreateWithPriority(cs.s, hipStreamNonBlocking, g.aux_prio_high ? prio_hi : prio_lo));   // the side streams outrank the accumulation
+    else HIPCHK(hipStreamCreateWithFlags(cs.s, hipStreamNonBlocking));
   }
-  HIPCHK(hipEventCreateWithFlags(&g.ev_fork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&g.ev_xchg, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&g.ev_xchg2, hipEventDisableTiming));
-  HIPCHK(hipStreamCreateWithFlags(&g.copy_stream, hipStreamNonBlocking));
-  for (int i = 0; i < 4; i++) HIPCHK(hipEventCreateWithFlags(&g.ev_copy[i], hipEventDisableTiming));
-  for (int i = 0; i < 8; i++) HIPCHK(hipEventCreateWithFlags(&g.ev_up[i], hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&g.ev_up_fork, hipEventDisableTiming));
-  { const char *e = getenv("MI355_MSM_CHUNKS"); if (e) { int v = atoi(e); if (v >= 1 && v <= 16) g.msm_chunks = (uint32_t)v; } }
+  g.stream = g.own_stream;
+  for (hipEvent_t *e : ctx_events(g)) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  for (int i = 0; i < 2; i++) g.msm_slot[i].id = i;
   // dynamic-LDS limits are per device and per kernel: each translation unit sets the ones of the kernels it launches
   CHK(msm_tu_init_device());
   CHK(ntt_tu_init_device());
   CHK(aux_tu_init_device());
-  { const char *e = getenv("MI355_TRACE"); g.trace = e && e[0] == '1'; }
-  { const char *e = getenv("MI355_REDUCE_CHAINS"); if (e) { int v = atoi(e); if (v >= 1024) g.reduce_chains = (uint32_t)v; } }
-  { const char *e = getenv("MI355_SEG_FILL"); if (e) { int v = atoi(e); if (v >= 2 && v <= 100) g.seg_fill = (uint32_t)v; } }
-  { const char *e = getenv("MI355_SEG_FILL_SEGFIX"); if (e) { int v = atoi(e); if (v >= 2 && v <= 100) g.seg_fill_segfix = (uint32_t)v; } }
-  { const char *e = getenv("MI355_SEG_MIN"); if (e) { int v = atoi(e); if (v >= 1 && v <= 4096) g.seg_min = (uint32_t)v; } }
-  { const char *e = getenv("MI355_FIXUP_MODE"); if (e && e[0] >= '0' && e[0] <= '2') g.fixup_mode = (uint32_t)(e[0] - '0'); }
-  { const char *e = getenv("MI355_FIXUP_HUGE_MIN"); if (e) { long v = atol(e); if (v >= 2048 && v <= 0x7fffffffL) g.fixup_huge_min = (uint32_t)v; } }
-  { const char *e = getenv("MI355_FIXUP_SERIAL_MAX"); if (e) { int v = atoi(e); if (v >= 1 && v <= 1024) g.fixup_serial_max = (uint32_t)v; } }
-  { const char *e = getenv("MI355_FIXUP_LANES_MAX_LOG"); if (e) { int v = atoi(e); if (v >= 0 && v <= 31) g.fixup_lanes_max_log = (uint32_t)v; } }
-  { const char *e = getenv("MI355_TAIL_COOP_MASK"); if (e) g.tail_coop_mask = (uint32_t)atoi(e) & 15u; }
-  { const char *e = getenv("MI355_TAIL_COOP_MAX"); if (e) { long v = atol(e); if (v >= 0 && v <= (1l << 24)) g.tail_coop_max = (uint32_t)v; } }
-  { const char *e = getenv("MI355_REDUCE_MIN_CHUNK"); if (e) { int v = atoi(e); if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) g.reduce_min_chunk = (uint32_t)v; } }
-  { const char *e = getenv("MI355_SORT_FB"); if (e) { int v = atoi(e); if (v >= 9 && v <= 12) g.sort_fb = (uint32_t)v; } }
-  { const char *e = getenv("MI355_SORT_SPLIT"); if (e && e[0] >= '1' && e[0] <= '2') g.sort_split = (uint32_t)(e[0] - '0'); }
-  { const char *e = getenv("MI355_SEG_FACTOR"); if (e) { int v = atoi(e); if (v >= 1 && v <= 256) g.seg_factor = (uint32_t)v; } }
-  { const char *e = getenv("MI355_SORT_T2"); if (e) { int v = atoi(e); if (v == 8192 || v == 16384) g.sort_t2 = (uint32_t)v; } }
-  { const char *e = getenv("MI355_SORT_T1"); if (e && atoi(e) == 8192) g.sort_t1 = 8192; }
-  { const char *e = getenv("MI355_NTT_DIRECT2_MAX_LOG"); if (e) { int v = atoi(e); if (v >= 0 && v <= 28) g.ntt_direct2_max_log = (uint32_t)v; } }
-  { const char *e = getenv("MI355_NTT_DIRECT2_MIN_LOG"); if (e) { int v = atoi(e); if (v >= 0 && v <= 28) g.ntt_direct2_min_log = (uint32_t)v; } }
-  { const char *e = getenv("MI355_NTT_FOLD_SCALE"); if (e) g.ntt_fold_scale = e[0] == '0' ? 0u : 1u; }
-  { const char *e = getenv("MI355_NTT_COSET_FOLD_MAX_LOG"); if (e) { int v = atoi(e); if (v >= 0 && v <= 28) g.ntt_coset_fold_max_log = (uint32_t)v; } }
-  { const char *e = getenv("MI355_NTT_BATCH_MAX_LOG"); if (e) { int v = atoi(e); if (v >= 0 && v <= 28) g.ntt_batch_max_log = (uint32_t)v; } }
-  { const char *e = getenv("MI355_NTT_TWO_LEVEL_MAX_LOG"); if (e) { int v = atoi(e); if (v >= 9 && v <= 20) g.ntt_two_level_max_log = (uint32_t)v; } }
-  { const char *e = getenv("MI355_NTT_TILE_LOG"); if (e) { int v = atoi(e); if (v >= 8 && v <= 12) g.ntt_tile_log = (uint32_t)v; } }
-  { const char *e = getenv("MI355_HOST_BATCH_OVERLAP"); if (e) g.host_batch_overlap = atoi(e) != 0; }
-  { const char *e = getenv("MI355_HOST_CHUNKS"); if (e) { int v = atoi(e); if (v >= 1 && v <= 64) g.host_chunks = (uint32_t)v; } }
-  { const char *e = getenv("MI355_HOST_SLICE_MIN_LOG"); if (e) { int v = atoi(e); if (v >= 4 && v <= 31) g.host_slice_min_log = (uint32_t)v; } }
   g.inited = true;
   return MI355_OK;
 }
@@ -316,27 +281,17 @@ static void destroy_ctx(int slot) {
   use_ctx(slot);
   if (g.device < 0) return;                 // never reached hipSetDevice: nothing was created
   (void)hipSetDevice(g.device);
-  if (g.stream) (void)hipStreamSynchronize(g.stream);
-  if (g.copy_stream) (void)hipStreamSynchronize(g.copy_stream);
+  (void)sync_streams(g, (g.stream ? SYNC_COMPUTE : 0u) | SYNC_COPY);
   for (auto &kv : g.ws) if (kv.second.p) (void)hipFree(kv.second.p);
   g.ws.clear();
   for (auto &kv : g.ntt_plans) for (void *q : kv.second.owned) (void)hipFree(q);
   g.ntt_plans.clear();
   if (g.fixed_base_table) { (void)hipFree(g.fixed_base_table); g.fixed_base_table = nullptr; }
   if (g.comm && g_rccl.CommDestroy) { (void)g_rccl.CommDestroy(g.comm); g.comm = nullptr; }
-  if (g.own_stream) (void)hipStreamDestroy(g.own_stream);
-  for (int i = 0; i < 2; i++) {
-    if (g.aux_stream[i]) { (void)hipStreamDestroy(g.aux_stream[i]); g.aux_stream[i] = nullptr; }
-    if (g.msm_slot[i].sorted) { (void)hipEventDestroy(g.msm_slot[i].sorted); (void)hipEventDestroy(g.msm_slot[i].acc_done); (void)hipEventDestroy(g.msm_slot[i].red_done); g.msm_slot[i] = MsmSlot(); }
-  }
-  if (g.ev_fork) { (void)hipEventDestroy(g.ev_fork); g.ev_fork = nullptr; }
-  if (g.ev_xchg) { (void)hipEventDestroy(g.ev_xchg); g.ev_xchg = nullptr; }
-  if (g.ev_xchg2) { (void)hipEventDestroy(g.ev_xchg2); g.ev_xchg2 = nullptr; }
-  for (int i = 0; i < 8; i++) if (g.ev_up[i]) { (void)hipEventDestroy(g.ev_up[i]); g.ev_up[i] = nullptr; }
-  if (g.ev_up_fork) { (void)hipEventDestroy(g.ev_up_fork); g.ev_up_fork = nullptr; }
-  for (int i = 0; i < 4; i++) if (g.ev_copy[i]) { (void)hipEventDestroy(g.ev_copy[i]); g.ev_copy[i] = nullptr; }
-  if (g.copy_stream) { (void)hipStreamDestroy(g.copy_stream); g.copy_stream = nullptr; }
-  g.own_stream = g.stream = nullptr; g.inited = false; g.device = -1;
+  for (const CtxStream &cs : ctx_streams(g)) if (*cs.s) { (void)hipStreamDestroy(*cs.s); *cs.s = nullptr; }   // a failed init_ctx leaves the later ones null
+  for (hipEvent_t *e : ctx_events(g)) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
+  for (auto &m : g.msm_slot) m.used = false;
+  g.stream = nullptr; g.inited = false; g.device = -1;
 }
 static void shutdown_all() {
   for (int s = 0; s < g_ndev; s++) if (g_ctx[s].inited) { (void)hipSetDevice(g_ctx[s].device); (void)hipStreamSynchronize(g_ctx[s].stream); }
@@ -344,7 +299,7 @@ static void shutdown_all() {
   for (auto &kv : g_srs) { kv.second.tab.reset(); kv.second.mem.reset(); }   // the destructors bind each shard's device and free
   g_srs.clear();
   for (int s = g_ndev - 1; s >= 0; s--) destroy_ctx(s);
-  g_ndev = 0; g_dup_devices = false; g_force_exchange = false;
+  g_ndev = 0; g_dup_devices = false; g_proc = mi355zk::ProcessKnobs();
   use_ctx(0);
 }
 
@@ -354,7 +309,7 @@ static void shutdown_all() {
 std::vector<Shard> plan_shards(uint64_t n) {
   std::vector<Shard> v;
   int D = g_ndev;
-  if (D > 1 && n / (uint64_t)D < (1ull << g_shard_min_log)) D = 1;
+  if (D > 1 && n / (uint64_t)D < (1ull << g_proc.shard_min_log)) D = 1;
   for (int d = 0; d < D; d++) { Shard s; s.slot = d; s.lo = n * d / D; s.n = n * (d + 1) / D - s.lo; if (s.n) v.push_back(s); }
   return v;
 }
@@ -424,21 +379,20 @@ int mi355_init_multi(const int *device_ids, int n_devices) {
   }
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); return fail(MI355_ENODEVICE, "no HIP device visible"); }
+  mi355zk::AllKnobs knobs; mi355zk::apply_knobs(knobs, [](const char *name) -> const char * { return getenv(name); });   // the 33 init-time variables: csrc/knobs.hpp
   bool dup = false;
   for (int i = 0; i < n_devices; i++) {
     if (device_ids[i] < 0 || device_ids[i] >= count) return fail(MI355_EBADARG, "device_id out of range");
     for (int j = 0; j < i; j++) if (device_ids[j] == device_ids[i]) dup = true;
   }
-  if (dup) { const char *e = getenv("MI355_ALLOW_DUP_DEVICES"); if (!(e && e[0] == '1')) return fail(MI355_EBADARG, "init_multi: the same device listed twice (test mode needs MI355_ALLOW_DUP_DEVICES=1)"); }
+  if (dup && !knobs.allow_dup_devices) return fail(MI355_EBADARG, "init_multi: the same device listed twice (test mode needs MI355_ALLOW_DUP_DEVICES=1)");
   int rc = MI355_OK;
-  for (int s = 0; s < n_devices && rc == MI355_OK; s++) { rc = init_ctx(s, device_ids[s]); g_ndev = s + 1; }
+  for (int s = 0; s < n_devices && rc == MI355_OK; s++) { rc = init_ctx(s, device_ids[s], knobs); g_ndev = s + 1; }
   if (rc != MI355_OK) { const std::string keep = g_err; shutdown_all(); g_err = keep; return rc; }
   g_dup_devices = dup;
-  { const char *e = getenv("MI355_MULTI_FORCE"); g_force_exchange = e && e[0] == '1'; }
-  { const char *e = getenv("MI355_MSM_AUTO_MAX_C"); g_auto_max_c = 22; if (e) { int v = atoi(e); if (v >= 16 && v <= MSM_MAX_C) g_auto_max_c = v; } }
-  { const char *e = getenv("MI355_SHARD_MIN_LOG"); g_shard_min_log = 14; if (e) { int v = atoi(e); if (v >= 0 && v <= 30) g_shard_min_log = (uint32_t)v; } }
+  g_proc = knobs;
   for (int s = 0; s < MAX_DEV; s++) for (int t = 0; t < MAX_DEV; t++) g_peer_ok[s][t] = s == t;
-  if (n_devices > 1 || g_force_exchange) {
+  if (n_devices > 1 || g_proc.multi_force) {
     // one communicator per process over the bound devices: ncclCommInitAll.  Duplicate devices (test mode) cannot form a
     // communicator; their exchange is a device-to-device copy.
     if (!dup) {
@@ -619,35 +573,28 @@ int mi355_buf_alloc(uint64_t bytes, int device_slot, void **dev_ptr_out) {
   // layers uploaded at 34 GB/s instead of the link's 53 (kernel timeline in profiles/r04_kernel_vs_wall_L0_L3.md: 18.6 ms of idle device per batch).
   CHK(need_init(device_slot));
   const size_t want = ((size_t)bytes + 255) & ~(size_t)255;
-  {
-    std::lock_guard<std::mutex> bl(g_buf_mu);
-    auto it = g_pool.find({device_slot, want});
-    if (it != g_pool.end()) { BufBlock b = it->second; g_pool.erase(it); b.used = false; g_bufs[(uintptr_t)b.p] = b; *dev_ptr_out = b.p; return MI355_OK; }
-  }
-  void *p = nullptr;
-  BufBlock b; b.bytes = want; b.slot = device_slot;
-  if (arena_on()) {
-    { std::lock_guard<std::mutex> bl(g_buf_mu); p = (void *)g_arena[device_slot].carve(want); }
-    if (!p) { arena_recycle_pool(device_slot); std::lock_guard<std::mutex> bl(g_buf_mu); p = (void *)g_arena[device_slot].carve(want); }
-    if (!p) {
-      size_t sbytes = std::max(want, slab_min_bytes()); void *base = nullptr;
-      // a new slab; near the HBM limit the head-room of a shared slab is given up and the request gets exactly its size (dev_malloc frees whole slabs and retries before failing)
-      if (sbytes > want && dev_malloc(&base, sbytes, "buf_alloc (slab)") != MI355_OK) { base = nullptr; sbytes = want; }
-      if (!base) CHK(dev_malloc(&base, sbytes, "buf_alloc"));
-      std::lock_guard<std::mutex> bl(g_buf_mu);
-      // a slab made for this one (large) request is dedicated: small blocks are never carved out of it, so it is whole again as soon as its polynomial comes back (slab_ranges.hpp)
-      g_arena[device_slot].small_limit = slab_min_bytes() / 64;   // 16 MiB with the default 1 GiB slabs: staging blocks, pointer tables, short vectors
-      g_arena[device_slot].add_slab((uintptr_t)base, sbytes, want >= slab_min_bytes());
-      p = (void *)g_arena[device_slot].carve(want);
-      if (!p) return fail(MI355_EHIP, "buf_alloc: slab bookkeeping");   // another thread took the new range: cannot happen with best fit on a range >= want, kept as a guard
+  const mi355zk::SlabPolicy &pol = slab_policy();
+  std::unique_lock<std::mutex> bl(g_buf_mu);
+  for (bool recycled = false, slab_added = false;;) {
+    const mi355zk::AllocStep st = g_reg.alloc_step(device_slot, want, recycled, pol);
+    if (st.kind == mi355zk::AllocStep::Block) { *dev_ptr_out = st.p; return MI355_OK; }
+    if (st.kind == mi355zk::AllocStep::Slab && slab_added) return fail(MI355_EHIP, "buf_alloc: slab bookkeeping");   // the new slab did not serve the request: cannot happen with best fit on a range >= want, kept as a guard
+    bl.unlock();   // every HIP call below runs without the registry mutex
+    void *base = nullptr; size_t got = st.bytes;
+    switch (st.kind) {
+      case mi355zk::AllocStep::Recycle: arena_recycle_pool(device_slot); recycled = true; bl.lock(); break;
+      case mi355zk::AllocStep::Slab:
+        // near the HBM limit the head-room of a shared slab is given up and the request gets exactly its size (dev_malloc frees whole slabs and retries before failing)
+        if (got > want && dev_malloc(&base, got, "buf_alloc (slab)") != MI355_OK) { base = nullptr; got = want; }
+        if (!base) CHK(dev_malloc(&base, got, "buf_alloc"));
+        bl.lock(); g_reg.add_slab(device_slot, base, got, st.dedicated, pol); slab_added = true;   // carved under the same hold of the mutex: no other thread can take the new range
+        break;
+      default:   // Direct (slabs off): the pool of this device is given back to the allocator before giving up
+        CHK(dev_malloc(&base, want, "buf_alloc"));
+        bl.lock(); g_reg.adopt(device_slot, base, want, false);
+        *dev_ptr_out = base; return MI355_OK;
     }
-    b.arena = true;
-  } else {
-    CHK(dev_malloc(&p, want, "buf_alloc"));   // the pool of this device is given back to the allocator before giving up
   }
-  b.p = p;
-  { std::lock_guard<std::mutex> bl(g_buf_mu); g_bufs[(uintptr_t)p] = b; }
-  *dev_ptr_out = p; return MI355_OK;
   });
 }
 // Returns the block to the library's pool (a later mi355_buf_alloc of the same size on the same device reuses it without a hipMalloc /
@@ -656,15 +603,15 @@ int mi355_buf_free(void *dev_ptr) {
   return guarded([&]() -> int {
   if (!dev_ptr) return MI355_OK;
   int slot;
-  { std::lock_guard<std::mutex> bl(g_buf_mu); auto it = g_bufs.find((uintptr_t)dev_ptr); if (it == g_bufs.end()) return fail(MI355_EBADARG, "buf_free: not the base pointer of a live mi355_buf_alloc block"); slot = it->second.slot; }
+  { std::lock_guard<std::mutex> bl(g_buf_mu); const BufBlock *f = g_reg.find(dev_ptr); if (!f || f->p != dev_ptr) return fail(MI355_EBADARG, "buf_free: not the base pointer of a live mi355_buf_alloc block"); slot = f->slot; }
   // no device lock either: the event below marks "everything queued on the owner's compute stream so far", which includes every use the freeing
   // thread issued before this call (HIP streams take work from several threads); nobody may use the block after its free
   CHK(need_init(slot));
   BufBlock b;
-  { std::lock_guard<std::mutex> bl(g_buf_mu); auto it = g_bufs.find((uintptr_t)dev_ptr); if (it == g_bufs.end()) return fail(MI355_EBADARG, "buf_free: block freed twice"); b = it->second; g_bufs.erase(it); }
-  if (!b.free_ev) HIPCHK(hipEventCreateWithFlags(&b.free_ev, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(b.free_ev, g_ctx[slot].stream));
-  { std::lock_guard<std::mutex> bl(g_buf_mu); g_pool.insert({{b.slot, b.bytes}, b}); }
+  { std::lock_guard<std::mutex> bl(g_buf_mu); if (!g_reg.take_live(dev_ptr, &b)) return fail(MI355_EBADARG, "buf_free: block freed twice"); }   // between the two look-ups another thread freed it
+  if (!b.free_ev) HIPCHK(hipEventCreateWithFlags((hipEvent_t *)&b.free_ev, hipEventDisableTiming));
+  HIPCHK(hipEventRecord((hipEvent_t)b.free_ev, g_ctx[slot].stream));
+  { std::lock_guard<std::mutex> bl(g_buf_mu); g_reg.pool_put(b); }
   return MI355_OK;
   });
 }
@@ -673,11 +620,14 @@ int mi355_buf_trim(void) {
   return guarded([&]() -> int {
   AllGuard lk;
   if (!g_ndev) return MI355_OK;
-  std::vector<BufBlock> drop;
-  { std::lock_guard<std::mutex> bl(g_buf_mu); for (auto it = g_pool.begin(); it != g_pool.end();) { if (!it->second.arena) { drop.push_back(it->second); it = g_pool.erase(it); } else ++it; } }
-  for (int s = 0; s < g_ndev; s++) { CHK(bind_ctx(s)); HIPCHK(hipStreamSynchronize(g.stream)); }
-  for (auto &b : drop) { CHK(bind_ctx(b.slot)); if (b.free_ev) (void)hipEventDestroy(b.free_ev); (void)hipFree(b.p); }
-  for (int s = 0; s < g_ndev; s++) { CHK(bind_ctx(s)); arena_recycle_pool(s); (void)arena_release_free_slabs(s); }   // carved blocks back to their slabs; whole slabs back to HIP
+  for (int s = 0; s < g_ndev; s++) { CHK(bind_ctx(s)); HIPCHK(sync_streams(g, SYNC_COMPUTE)); }   // every slot's compute stream first (a block may have been read from another slot); all locks are held: nothing new is queued
+  for (int s = 0; s < g_ndev; s++) {
+    CHK(bind_ctx(s));
+    std::vector<BufBlock> drop;
+    { std::lock_guard<std::mutex> bl(g_buf_mu); drop = g_reg.take_pooled(s, false); }
+    retire_blocks(s, drop, Retire::ToHip);
+    arena_recycle_pool(s); (void)arena_release_free_slabs(s);   // carved blocks back to their slabs; whole slabs back to HIP
+  }
   return bind_ctx(0);
   });
 }
@@ -709,7 +659,7 @@ int mi355_buf_upload(void *dst_dev, const void *src_host, uint64_t bytes) {
   {
     std::lock_guard<std::mutex> ul(g_upload_mu[slot]);
     bool fresh = false; hipEvent_t free_ev = nullptr;
-    { std::lock_guard<std::mutex> bl(g_buf_mu); if (BufBlock *b = buf_find_locked(dst_dev)) { if ((uintptr_t)dst_dev + bytes > (uintptr_t)b->p + b->bytes) return fail(MI355_EBADARG, "buf_upload: range exceeds the block"); fresh = !b->used; free_ev = b->free_ev; b->used = true; } }
+    { std::lock_guard<std::mutex> bl(g_buf_mu); if (BufBlock *b = g_reg.find(dst_dev)) { if (!g_reg.fits(*b, dst_dev, bytes)) return fail(MI355_EBADARG, "buf_upload: range exceeds the block"); fresh = !b->used; free_ev = (hipEvent_t)b->free_ev; b->used = true; } }
     if (fresh) { if (free_ev) HIPCHK(hipStreamWaitEvent(c.copy_stream, free_ev, 0)); }
     else { HIPCHK(hipEventRecord(c.ev_up_fork, c.stream)); HIPCHK(hipStreamWaitEvent(c.copy_stream, c.ev_up_fork, 0)); }   // everything queued on the compute stream so far
     done = c.ev_up[c.up_next++ & 7];
@@ -803,9 +753,7 @@ int mi355_mem_info(int device_slot, uint64_t *free_bytes, uint64_t *total_bytes,
   HIPCHK(hipMemGetInfo(&fr, &tot));
   uint64_t live = 0, pooled = 0, ws = 0;
   { std::lock_guard<std::mutex> bl(g_buf_mu);
-    for (const auto &kv : g_bufs) if (kv.second.slot == device_slot) live += kv.second.bytes;
-    for (const auto &kv : g_pool) if (kv.first.first == device_slot) pooled += kv.second.bytes;
-    pooled += g_arena[device_slot].free_bytes(); }   // free ranges of the slabs: held by the library, reusable, not live
+    live = g_reg.live_bytes(device_slot); pooled = g_reg.pooled_bytes(device_slot); }
   for (const auto &kv : g.ws) ws += kv.second.cap;
   if (free_bytes) *free_bytes = fr; if (total_bytes) *total_bytes = tot; if (live_buf_bytes) *live_buf_bytes = live;
   if (pooled_bytes) *pooled_bytes = pooled; if (workspace_bytes) *workspace_bytes = ws;

@@ -36,7 +36,7 @@ double msm_cost(uint64_t n, int c, bool shared) { const double W = (MSM_SCALAR_B
 int choose_c(uint64_t n) {
   if (t_opts.force_c) return t_opts.force_c;
   double best = 1e300; int best_c = 8;
-  for (int c = 4; c <= g_auto_max_c; c++) {
+  for (int c = 4; c <= (int)g_proc.msm_auto_max_c; c++) {
     const double W = (MSM_SCALAR_BITS + c - 1) / c, nb = (double)(1ull << (c - 1));
     if (W * nb * sizeof(g1_xyzz29_t) > 6.0e9) continue;
     const double cost = msm_cost(n, c, false);
@@ -716,7 +716,7 @@ int mi355_srs_precompute(uint64_t handle, uint64_t n_hint, int c) {
   const bool automatic = c == 0;
   if (automatic) {   // best shared-bucket window for MSMs of n_hint points (per shard), within the sorter's key range
     double best = 1e300;
-    for (int cc = 4; cc <= g_auto_max_c; cc++) { const double co = msm_cost(per_shard, cc, true); if (co < best) { best = co; c = cc; } }
+    for (int cc = 4; cc <= (int)g_proc.msm_auto_max_c; cc++) { const double co = msm_cost(per_shard, cc, true); if (co < best) { best = co; c = cc; } }
   }
   if (c < 2 || c > MSM_MAX_C) return fail(MI355_EBADARG, "srs_precompute: window bits out of range");
   if (sp->tab) {
@@ -851,7 +851,7 @@ static int msm_multi(const std::vector<Piece> &pieces, const fe_t *const *polys,
   g_last_devices = D;
   return MI355_OK;
 }
-static bool single_device_call(const std::vector<Piece> &pieces) { return pieces.size() == 1 && pieces[0].slot == 0 && !g_force_exchange; }
+static bool single_device_call(const std::vector<Piece> &pieces) { return pieces.size() == 1 && pieces[0].slot == 0 && !g_proc.multi_force; }
 
 // host scalars, one device: mi355_msm_g1_host.  The copy is cut into chunks on a second stream; the digit extraction of chunk j runs while
 // chunk j + 1 crosses PCIe (msm_host_single in the MSM section above).

@@ -630,10 +630,10 @@ int mi355_fr_gate_eval_dev(void *dst_dev, const void *const *polys_dev, uint32_t
     if (factor_poly[q] >= n_polys) return fail(MI355_EBADARG, "fr_gate_eval: factor refers to a polynomial outside the list");
     G.factor_poly[q] = (uint8_t)factor_poly[q]; G.factor_rot[q] = factor_rot[q];
   }
-  int slot = slot_of(dst_dev);
+  const void *all[1 + GATE_MAX_POLYS] = {dst_dev};
+  for (uint32_t p = 0; p < n_polys; p++) { if (!polys_dev[p]) return fail(MI355_EBADARG, "fr_gate_eval: null polynomial pointer"); all[1 + p] = polys_dev[p]; }
+  int slot; CHK(common_slot(all, 1 + n_polys, true, &slot, "fr_gate_eval"));   // dst comes first: its slot runs the launch
   for (uint32_t p = 0; p < n_polys; p++) {
-    if (!polys_dev[p]) return fail(MI355_EBADARG, "fr_gate_eval: null polynomial pointer");
-    int s; CHK(common_slot({dst_dev, polys_dev[p]}, &s, "fr_gate_eval"));
     G.poly[p] = (const fe_t *)polys_dev[p];
     // dst may BE one of the operands only where every thread reads exactly the element it writes: same base address, every factor of that
     // polynomial un-rotated.  Any other overlap is a cross-thread race (thread i would read what thread i - r is writing): rejected.
@@ -656,10 +656,10 @@ int mi355_fr_interleave_dev(void *dst_dev, const void *const *parts_dev, uint32_
   return guarded([&]() -> int {
   if (!dst_dev || !parts_dev || q_parts == 0 || q_parts > 8) return fail(MI355_EBADARG, "fr_interleave: 1..8 parts");
   InterleavePlan P; memset(&P, 0, sizeof P); P.q = q_parts;
-  int slot = slot_of(dst_dev);
+  const void *all[1 + 8] = {dst_dev};
+  for (uint32_t q = 0; q < q_parts; q++) { if (!parts_dev[q]) return fail(MI355_EBADARG, "fr_interleave: null part pointer"); all[1 + q] = parts_dev[q]; }
+  int slot; CHK(common_slot(all, 1 + q_parts, true, &slot, "fr_interleave"));   // dst comes first: its slot runs the launch
   for (uint32_t q = 0; q < q_parts; q++) {
-    if (!parts_dev[q]) return fail(MI355_EBADARG, "fr_interleave: null part pointer");
-    int s; CHK(common_slot({dst_dev, parts_dev[q]}, &s, "fr_interleave"));
     const uintptr_t d0 = (uintptr_t)dst_dev, d1 = d0 + (uint64_t)q_parts * n * sizeof(fe_t), p0 = (uintptr_t)parts_dev[q], p1 = p0 + n * sizeof(fe_t);
     if (p0 < d1 && d0 < p1) return fail(MI355_EBADARG, "fr_interleave: dst overlaps a part");
     P.part[q] = (const fe_t *)parts_dev[q];
@@ -733,12 +733,8 @@ int mi355_eval_polynomial_batch_dev(const void *const *polys_dev, uint32_t batch
   return guarded([&]() -> int {
   if (batch == 0) return MI355_OK;
   if (!polys_dev || !points || !out_fr_host) return fail(MI355_EBADARG, "eval_polynomial_batch: null pointer");
-  int slot = -1;
-  for (uint32_t i = 0; i < batch; i++) {
-    if (n && !polys_dev[i]) return fail(MI355_EBADARG, "eval_polynomial_batch: null polynomial pointer");
-    const int s = slot_of(polys_dev[i]);
-    if (slot < 0) slot = s; else if (s != slot && g_ctx[s].device != g_ctx[slot].device) return fail(MI355_EBADARG, "eval_polynomial_batch: the polynomials live on different devices");
-  }
+  for (uint32_t i = 0; n && i < batch; i++) if (!polys_dev[i]) return fail(MI355_EBADARG, "eval_polynomial_batch: null polynomial pointer");
+  int slot; CHK(common_slot(polys_dev, batch, true, &slot, "eval_polynomial_batch"));
   DevGuard lk(slot);
   CHK(need_init(slot));
   if (n == 0) { memset(out_fr_host, 0, (size_t)batch * 32); return MI355_OK; }

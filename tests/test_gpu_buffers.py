@@ -439,3 +439,65 @@ def test_slabs_serve_another_block_size_without_going_back_to_hip(zk):
         b.free()
     check(lib.mi355_buf_trim())
     assert int(h2.mem_info()["free"]) >= int(after["free"]) + (1 << 30)                        # the slabs went back to HIP
+
+
+def _lifecycle_round(zk, seed):
+    """steps 2-7 of test_blocks_survive_a_trim_and_the_library_restarts_clean, on an initialised library"""
+    h2, capi = zk.halo2, zk._capi
+    lib, check = capi.lib(), capi.check
+    rng = np.random.default_rng(seed)
+    sizes = [64, 4096, (1 << 20) + 32]
+    ptrs, data = [], []
+    for s in sizes:
+        p = C.c_void_p()
+        check(lib.mi355_buf_alloc(s, 0, C.byref(p)))
+        d = rng.integers(0, 256, size=s, dtype=np.uint8)
+        check(lib.mi355_buf_upload(p, capi.ptr(d), s))
+        ptrs.append(p); data.append(d)
+
+    def read(i):
+        out = np.zeros(sizes[i], dtype=np.uint8)
+        check(lib.mi355_buf_download(capi.ptr(out), ptrs[i], sizes[i]))
+        return out
+
+    k = 10
+    v = rand_fr(rng, 1 << k)
+    dom = h2.EvaluationDomain(2, k)
+    poly = h2.DeviceBuffer.from_host(v)
+    dom.coeff_to_lagrange(poly)
+    assert (poly.fr() == cref.best_fft(v, dom.omega, k, threads=2)).all()
+    poly.free()
+    check(lib.mi355_buf_free(ptrs[1]))
+    info = h2.mem_info()
+    assert info["live_buffers"] == 256 + (1 << 20) + 256 and info["pooled"] > 0, info
+    check(lib.mi355_buf_trim())
+    assert (read(0) == data[0]).all() and (read(2) == data[2]).all()      # the blocks still allocated kept their contents through the drain
+    check(lib.mi355_buf_free(ptrs[0])); check(lib.mi355_buf_free(ptrs[2]))
+    check(lib.mi355_buf_trim())
+    info = h2.mem_info()
+    assert info["live_buffers"] == 0 and info["pooled"] == 0, info
+
+
+def _lifecycle_child():
+    zk = ge.load_package()
+    zk.init(0)
+    _lifecycle_round(zk, 11)
+    zk.shutdown()
+    zk.init(0)
+    info = zk.halo2.mem_info()
+    assert info["live_buffers"] == 0 and info["pooled"] == 0 and info["workspace"] == 0, info
+    _lifecycle_round(zk, 12)
+    zk.shutdown()
+    print("LIFECYCLE-OK")
+
+
+def test_blocks_survive_a_trim_and_the_library_restarts_clean():
+    """in a process of its own (the module's fixture keeps its library): init; blocks of 64 B, 4 KiB and 2^20 + 32 B on slot 0, a pattern uploaded into each; a 2^10 transform on
+    a fourth block; two blocks freed; mi355_buf_trim leaves the two still allocated readable with their patterns; everything freed and trimmed, mi355_mem_info reports no live and
+    no pooled byte; mi355_shutdown, mi355_init, and live == pooled == workspace == 0; the same sequence once more with the data intact.  Pins the create / destroy pairing of a
+    context's streams and events and the one drain of the buffer pool on the real runtime."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import sys; sys.path.insert(0, %r); import tests.test_gpu_buffers as t; t._lifecycle_child()" % root
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "LIFECYCLE-OK" in r.stdout, (r.stdout[-500:], r.stderr[-2500:])
