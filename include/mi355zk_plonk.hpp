@@ -424,6 +424,73 @@ inline std::unique_ptr<ProvingKey> keygen(const Protocol &P, const Circuit &C, u
   return pk;
 }
 
+// ------------------------------------------------------------------------------------------------ what check_witness and create_proof share
+namespace detail {
+struct Joiner { std::vector<std::thread> th; void join() { for (auto &t : th) if (t.joinable()) t.join(); } ~Joiner() { join(); } };   // every thread is joined on every path
+
+// Items 0 .. items - 1 on `stripes` host threads, worker w taking w, w + stripes, ...: how witness columns cross the link.  Every worker runs ITS OWN COPY of `item`, so what
+// `item` captures by value is that worker's scratch.  A worker stops at its first exception; the first one of all is kept in `error`, and `failed()` runs under `mu` right
+// after it is stored.  With `caller_works`, stripe 0 runs on the calling thread before start() returns.
+struct StripedUploader {
+  std::mutex mu; std::string error; Joiner workers;
+  template <class Item, class Failed> void start(size_t items, size_t stripes, bool caller_works, Item item, Failed failed) {
+    auto worker = [this, items, stripes, item, failed](size_t w) mutable {
+      try { for (size_t i = w; i < items; i += stripes) item(i); }
+      catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu); if (error.empty()) error = e.what(); failed(); }
+    };
+    for (size_t w = caller_works ? 1 : 0; w < stripes; w++) workers.th.emplace_back(worker, w);
+    if (caller_works) worker(0);
+  }
+  void join() { workers.join(); }
+};
+
+// dst = (accumulate ? dst : 0) + sum_i coeffs[i] ptrs[i], one launch of the fused kernel (at most PLAN_MAX_TERMS polynomials)
+inline void linear_combination(void *dst, const std::vector<const void *> &ptrs, const std::vector<Fr> &coeffs, uint64_t n, bool accumulate) {
+  const uint32_t m = (uint32_t)ptrs.size(); std::vector<uint32_t> tl(m, 1), fp(m); std::vector<int32_t> rot(m, 0);
+  for (uint32_t i = 0; i < m; i++) fp[i] = i;
+  gate_eval(dst, ptrs.data(), m, coeffs.data(), tl.data(), m, fp.data(), rot.data(), n, accumulate ? 1 : 0);
+}
+
+// Plans that run on the Lagrange domain, rotations in rows: step 3's device route and step 4 of create_proof, and check_witness.  Owns the compiler, the pool of
+// temporaries and the launch loop.  `column` gives the witness and instance polynomials; the key's own come from its kept Lagrange values.  Where the key kept none, a
+// prover step fails under its name (`step`); with step == nullptr (check_witness) they come back from the coefficients by a forward transform into scratch, once.
+struct LagrangePlan {
+  static constexpr uint32_t RESULT_BASE = 1u << 20;   // ids of result temporaries (check_witness judges a batch of them in one call), above every id the compiler hands out
+  const ProvingKey &pk; const uint64_t n; const char *step; std::function<const void *(uint32_t)> column;
+  Compiler cmp; std::vector<DevicePoly> tmp, result; std::map<Atom, DevicePoly> scratch; uint32_t launches = 0;
+  LagrangePlan(const ProvingKey &pk_, const char *step_, std::vector<Fr> challenges, std::function<const void *(uint32_t)> column_)
+      : pk(pk_), n(pk_.P->n), step(step_), column(std::move(column_)), cmp(const_cast<CommonRegistry &>(pk_.commons), false, std::move(challenges)) {}
+  DevicePoly &tmp_at(uint32_t i) { while (tmp.size() <= i) tmp.emplace_back(n, 0); return tmp[i]; }
+  void *dst(uint32_t id) { return id >= RESULT_BASE ? result.at(id - RESULT_BASE).p : tmp_at(id).p; }
+  const void *key_lagrange(const Atom &a) {
+    if (step && a.kind == A_COMMON && a.idx != pk.identity_common) throw std::invalid_argument(std::string(step) + " reads no common polynomial but X");
+    const DevicePoly &kept = a.kind == A_COMMON ? pk.common_lagrange[a.idx] : pk.pre_lagrange[a.idx];
+    if (kept.p) return kept.p;
+    if (step) throw std::invalid_argument(std::string(step) + (a.kind == A_COMMON ? ": Lagrange values of X were not kept" : ": Lagrange values of a preprocessed polynomial were not kept"));
+    auto it = scratch.find(a);
+    if (it == scratch.end()) { DevicePoly c = clone(pk.coeff(a), 0); check(mi355_ntt_fr_dev(c.p, pk.dom->k, pk.dom->omega.data())); it = scratch.emplace(a, std::move(c)).first; }
+    return it->second.p;
+  }
+  const void *resolve(const Atom &a) { return a.kind == A_TMP ? dst(a.idx) : a.kind == A_COMMON || pk.P->is_pre(a.idx) ? key_lagrange(a) : column(a.idx); }
+  void run() {   // everything compiled so far, in order
+    for (const auto &L : cmp.out) { run_launch(L, dst((uint32_t)L.dst), n, fr_one(), L.accumulate, [this](const Atom &a) { return resolve(a); }); launches++; }
+    cmp.out.clear();
+  }
+  // The challenges later compiles read.  The compiler keeps nothing of a compile but its pending launches, and run() has drained those: the only state to replace is the list
+  void set_challenges(std::vector<Fr> challenges) { if (!cmp.out.empty()) throw std::logic_error("LagrangePlan: challenges changed with launches pending"); cmp.ch = std::move(challenges); }
+  // TMP 0 = the lookup's table, TMP 1 = its input, both compressed with theta (challenge 0)
+  void compress_lookup(const Lookup &lk) { cmp.tmp_base = 2; cmp.tmp_next = 0; cmp.emit(0, cmp.compile(*lk.table)); cmp.emit(1, cmp.compile(*lk.input)); run(); }
+  // m = how often each of TMP 0's usable rows is looked up by TMP 1's; an input cell that is not in the table comes back as (any, input, row), the smallest one
+  struct Missing { bool any; uint32_t input; uint64_t row; };
+  Missing multiplicities(void *m, uint64_t usable, uint32_t rule) {
+    const void *inputs[1] = {tmp_at(1).p}; uint64_t missing = ~uint64_t(0);
+    const int rc = mi355_fr_lookup_multiplicities_dev(m, n, tmp_at(0).p, usable, inputs, 1, usable, rule, &missing);
+    if (rc == MI355_EBADARG && missing != ~uint64_t(0)) return {true, (uint32_t)(missing >> 40), missing & ((uint64_t(1) << 40) - 1)};
+    check(rc); return {false, 0, 0};
+  }
+};
+}  // namespace detail
+
 // ------------------------------------------------------------------------------------------------ check_witness
 // halo2_proofs::dev::MockProver::verify for a PlonkProtocol, on the device [EXT-recalled halo2_proofs src/dev.rs, MockProver::verify: gate, lookup and permutation
 // failures]; the reference runs it on every trace before proving [REF integration/src/mock.rs:16-24], [REF bin/src/prove_utils.rs:54-55,81-88].  create_proof takes any
@@ -455,7 +522,7 @@ struct WitnessError : std::runtime_error {
   explicit WitnessError(std::vector<VerifyFailure> f) : std::runtime_error("witness check: " + describe(f.at(0)) + (f.size() > 1 ? "; " + std::to_string(f.size()) + " failures reported" : std::string())), failures(std::move(f)) {}
 };
 inline std::vector<VerifyFailure> check_witness(const ProvingKey &pk, const Circuit &wit, const CheckOptions &opt) {
-  const Protocol &P = *pk.P; const EvaluationDomain &dom = *pk.dom;
+  const Protocol &P = *pk.P;
   const uint64_t n = P.n, u = P.usable; const uint32_t A = P.num_advice(), NL = (uint32_t)P.lookups.size();
   if (wit.advice.size() != A) throw std::invalid_argument("check_witness: the witness has " + std::to_string(wit.advice.size()) + " advice columns, the protocol " + std::to_string(A));
   if (wit.instances.size() > n) throw std::invalid_argument("check_witness: more instance values than rows");
@@ -466,53 +533,34 @@ inline std::vector<VerifyFailure> check_witness(const ProvingKey &pk, const Circ
   if (!wit.instances.empty()) check(mi355_buf_upload(inst.p, wit.instances.data(), wit.instances.size() * 32));
   {
     const size_t UT = (size_t)std::max(1, std::min<int>(std::min(3, opt.threads / 4), (int)A));
-    std::mutex mu; std::string upload_error;
-    auto worker = [&](size_t first) {
-      try { for (size_t i = first; i < A; i += UT) { if (wit.advice[i].size() != n) throw std::invalid_argument("advice column " + std::to_string(i) + " is not n rows"); DevicePoly d(n, 0); check(mi355_buf_upload(d.p, wit.advice[i].data(), n * 32)); adv[i] = std::move(d); } }
-      catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu); upload_error = e.what(); }
-    };
-    std::vector<std::thread> th; for (size_t w = 1; w < UT; w++) th.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : th) t.join();
-    if (!upload_error.empty()) throw Error(MI355_EHIP, "check_witness: witness upload: " + upload_error);
+    detail::StripedUploader up;
+    up.start(A, UT, true, [&](size_t i) {
+      if (wit.advice[i].size() != n) throw std::invalid_argument("advice column " + std::to_string(i) + " is not n rows");
+      DevicePoly d(n, 0); check(mi355_buf_upload(d.p, wit.advice[i].data(), n * 32)); adv[i] = std::move(d);
+    }, [] {});
+    up.join();
+    if (!up.error.empty()) throw Error(MI355_EHIP, "check_witness: witness upload: " + up.error);
   }
-  // ---- operands: Lagrange values; what the key holds as coefficients only comes back by a forward transform, once, when first named
-  std::map<Atom, DevicePoly> scratch; std::vector<DevicePoly> tmp;
-  auto tmp_at = [&](uint32_t i) -> DevicePoly & { while (tmp.size() <= i) tmp.emplace_back(n, 0); return tmp[i]; };
-  auto from_coeff = [&](const Atom &a) -> const void * {
-    auto it = scratch.find(a);
-    if (it == scratch.end()) { DevicePoly c = clone(pk.coeff(a), 0); check(mi355_ntt_fr_dev(c.p, dom.k, dom.omega.data())); it = scratch.emplace(a, std::move(c)).first; }
-    return it->second.p;
-  };
-  auto column = [&](uint32_t poly) -> const void * {
-    if (P.is_pre(poly)) return pk.pre_lagrange[poly].p ? pk.pre_lagrange[poly].p : from_coeff(Atom{A_POLY, poly, 0});
+  // ---- operands: Lagrange values; what the key holds as coefficients only comes back by a forward transform, once, when first named (LagrangePlan::key_lagrange)
+  detail::LagrangePlan plan(pk, nullptr, {}, [&](uint32_t poly) -> const void * {   // no challenge is drawn before the gates: one that names a challenge is no gate of a one-phase circuit
     if (P.is_instance(poly)) return inst.p;
     if (poly >= P.phase0[0] && poly < P.phase0[0] + A) return adv[poly - P.phase0[0]].p;
     throw std::invalid_argument("check_witness: polynomial " + std::to_string(poly) + " is neither fixed, instance nor advice");
-  };
-  constexpr uint32_t RESULT_BASE = 1u << 20;   // ids of a batch's result temporaries, above every id the compiler hands out
-  std::vector<DevicePoly> result;
-  auto resolve = [&](const Atom &a) -> const void * {
-    if (a.kind == A_TMP) return a.idx >= RESULT_BASE ? result.at(a.idx - RESULT_BASE).p : tmp_at(a.idx).p;
-    if (a.kind == A_COMMON) return pk.common_lagrange[a.idx].p ? pk.common_lagrange[a.idx].p : from_coeff(a);
-    return column(a.idx);
-  };
-  auto dst_of = [&](int dst) -> void * { return (uint32_t)dst >= RESULT_BASE ? result.at((uint32_t)dst - RESULT_BASE).p : tmp_at((uint32_t)dst).p; };
+  });
+  Compiler &cmp = plan.cmp;
   // ---- gates: batches of temporaries, one synchronisation per batch
   {
-    Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, {});   // no challenge is drawn before the gates: one that names a challenge is no gate of a one-phase circuit
     const uint32_t B = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, (uint64_t(1) << 28) / n));   // 8 GiB of temporaries at most
     const size_t NG = P.gates.size();
     for (size_t g0 = 0; g0 < NG; g0 += B) {
       const uint32_t nb = (uint32_t)std::min<size_t>(B, NG - g0);
-      while (result.size() < nb) result.emplace_back(n, 0);
+      while (plan.result.size() < nb) plan.result.emplace_back(n, 0);
       std::vector<const void *> ptrs(nb);
       for (uint32_t b = 0; b < nb; b++) {
         cmp.tmp_base = 0; cmp.tmp_next = 0;
-        cmp.emit((int)(RESULT_BASE + b), cmp.compile(*P.gates[g0 + b].expr));
-        for (const auto &L : cmp.out) run_launch(L, dst_of(L.dst), n, fr_one(), L.accumulate, resolve);
-        cmp.out.clear();
-        ptrs[b] = result[b].p;
+        cmp.emit((int)(detail::LagrangePlan::RESULT_BASE + b), cmp.compile(*P.gates[g0 + b].expr));
+        plan.run();
+        ptrs[b] = plan.result[b].p;
       }
       const halo2::NonzeroRows r = halo2::nonzero_rows(ptrs, n, opt.cap);
       for (uint32_t b = 0; b < nb; b++) {
@@ -521,14 +569,14 @@ inline std::vector<VerifyFailure> check_witness(const ProvingKey &pk, const Circ
         if (opt.cap == 0 && r.counts[b]) out.push_back({VerifyFailure::Gate, index, ~uint64_t(0), r.counts[b], 0, 0, 0});   // counts only: the row is not known
       }
     }
-    result.clear(); tmp.clear();
+    plan.result.clear(); plan.tmp.clear();
   }
   // ---- copy constraints
   {
     const uint32_t NP = (uint32_t)wit.pcols.size();
     std::vector<uint64_t> cells, images;
     { halo2::PermutationAssembly as(NP, n); for (const auto &cp : wit.pairs) as.copy(cp.ja, cp.ra, cp.jb, cp.rb); as.overrides(cells, images); }
-    std::vector<const void *> cols(NP); for (uint32_t j = 0; j < NP; j++) cols[j] = column(wit.pcols[j].column);
+    std::vector<const void *> cols(NP); for (uint32_t j = 0; j < NP; j++) cols[j] = plan.resolve(Atom{A_POLY, wit.pcols[j].column, 0});
     if (NP) {
       const halo2::CopyCheck r = halo2::copy_check(cols, P.k, cells, images, opt.cap);
       const uint64_t mask = n - 1;
@@ -542,18 +590,12 @@ inline std::vector<VerifyFailure> check_witness(const ProvingKey &pk, const Circ
   // ---- lookups, under a theta of the check's own
   if (NL) {
     detail::Rng rng(opt.theta_seed); Fr theta = rng.uniform(); while (fr_is_zero(theta)) theta = rng.uniform();
-    Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, {theta});
+    plan.set_challenges({theta});
     DevicePoly m(n, 0);
     for (uint32_t l = 0; l < NL; l++) {
-      const Lookup &lk = P.lookups[l];
-      cmp.tmp_base = 2; cmp.tmp_next = 0;
-      cmp.emit(0, cmp.compile(*lk.table)); cmp.emit(1, cmp.compile(*lk.input));
-      for (const auto &L : cmp.out) run_launch(L, dst_of(L.dst), n, fr_one(), L.accumulate, resolve);
-      cmp.out.clear();
-      const void *inputs[1] = {tmp_at(1).p}; uint64_t missing = ~uint64_t(0);
-      const int rc = mi355_fr_lookup_multiplicities_dev(m.p, n, tmp_at(0).p, u, inputs, 1, u, 0, &missing);
-      if (rc == MI355_EBADARG && missing != ~uint64_t(0)) out.push_back({VerifyFailure::Lookup, l, missing & ((uint64_t(1) << 40) - 1), 1, (uint32_t)(missing >> 40), 0, 0});
-      else check(rc);
+      plan.compress_lookup(P.lookups[l]);
+      const auto miss = plan.multiplicities(m.p, u, 0);
+      if (miss.any) out.push_back({VerifyFailure::Lookup, l, miss.row, 1, miss.input, 0, 0});
     }
   }
   check(mi355_synchronize());
@@ -620,252 +662,283 @@ inline std::vector<Fr> interpolate(const std::vector<Fr> &pts, const std::vector
   return out;
 }
 inline Fr horner(const std::vector<Fr> &c, const Fr &x) { Fr acc = fr_zero(); for (size_t i = c.size(); i-- > 0;) acc = fr_add(fr_mul(acc, x), c[i]); return acc; }
-}  // namespace detail
+inline std::vector<Fr> powers(const Fr &b, size_t m) { std::vector<Fr> p(m, fr_one()); for (size_t i = 1; i < m; i++) p[i] = fr_mul(p[i - 1], b); return p; }
 
-inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const ProvingKey &pk, const Circuit &wit, const ProofOptions &opt) {
-  using Clock = std::chrono::steady_clock;
-  const Protocol &P = *pk.P; const EvaluationDomain &dom = *pk.dom;
-  const uint32_t k = P.k, Q = P.Q; const uint64_t n = P.n, u = P.usable;
-  const uint32_t A = P.num_advice(), NL = (uint32_t)P.lookups.size(), NZ = (uint32_t)P.perm.size();
-  ProofResult R;
-  // resident coset parts were placed by keygen at q % pk.devices: the gate kernel on device d must find part q on d, so the proof runs on the key's device count
-  // (ADVICE r5: a differing opt.devices would read a coset that sits on another device)
-  if (pk.resident_cosets && pk.devices != std::max(1, opt.devices)) throw std::invalid_argument("create_proof: ProofOptions::devices (" + std::to_string(opt.devices) + ") differs from the proving key's (" + std::to_string(pk.devices) + ") while its coset parts are resident");
-  const int D = std::max(1, std::min<int>(opt.devices, (int)Q));
-  auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-  if (opt.check_witness) { CheckOptions co; co.threads = opt.threads; std::vector<VerifyFailure> bad = check_witness(pk, wit, co); if (!bad.empty()) throw WitnessError(std::move(bad)); }
-  const auto t_start = Clock::now(); auto tl = t_start;
-  auto lap = [&](int step) { R.step_ms[step] += ms_since(tl); tl = Clock::now(); };
-  Transcript T(opt.transcript == TranscriptKind::ByLayer ? reference_transcript(P) : opt.transcript);
-  T.common_scalar(vk_transcript_scalar(P, pk.vk));
-  for (const auto &v : wit.instances) T.common_scalar(v);
-  std::map<uint32_t, DevicePoly> poly;   // protocol index -> Lagrange values until step 6, coefficients afterwards
-  auto commit_one = [&](uint64_t basis, const void *ptr) { G1 out; check(mi355_msm_g1_dev(basis, 0, ptr, n, out.data())); R.msm++; T.write_point(out); };
-  auto commit_many = [&](uint64_t basis, const std::vector<uint32_t> &refs) {
-    const uint32_t B = opt.commit_batch ? opt.commit_batch : 32;
-    for (size_t base = 0; base < refs.size(); base += B) {
-      const uint32_t cnt = (uint32_t)std::min<size_t>(B, refs.size() - base);
-      std::vector<const void *> ptrs(cnt); std::vector<G1> outs(cnt);
-      for (uint32_t i = 0; i < cnt; i++) ptrs[i] = poly.at(refs[base + i]).p;
-      check(mi355_msm_g1_batch_dev(basis, 0, ptrs.data(), cnt, n, outs.data())); R.msm += cnt;
-      for (uint32_t i = 0; i < cnt; i++) T.write_point(outs[i]);
+// SHPLONK's scalar side: host arithmetic, no device call.  points[i] = the opening points of rotation set i, in the order of its rotations.  It comes in two parts because
+// the transcript sits between them (u is drawn after the commitment to H, and H needs the remainders), and the first runs set by set, under the device's work on that set.
+//   remainder      of one set: R = sum_j ys^j r_j, r_j = the polynomial of degree < |rots| through the evaluations of the set's j-th polynomial (coefficients, low first)
+//   linearisation  L = sum_i v^i zd_i (A_i - R_i(u)) - Z_T(u) H, scaled by 1 / zd_0, with zd_i = prod (u - point) over the points set i does not open at and Z_T over
+//                  every point: the coefficient of each A_i, the one of H, and the constant that is subtracted.  L(u) = 0
+inline std::vector<Fr> shplonk_remainder(const RotationSet &s, const std::vector<Fr> &points, const std::map<PolyRot, Fr> &evals, const Fr &ys) {
+  std::vector<Fr> sum(s.rots.size(), fr_zero()); Fr yp = fr_one();
+  for (uint32_t p : s.polys) {
+    std::vector<Fr> vals; for (int32_t r : s.rots) vals.push_back(evals.at({p, r}));
+    const std::vector<Fr> rj = interpolate(points, vals);
+    for (size_t t = 0; t < sum.size(); t++) sum[t] = fr_add(sum[t], fr_mul(yp, rj[t]));
+    yp = fr_mul(yp, ys);
+  }
+  return sum;
+}
+struct ShplonkLinearisation { std::vector<Fr> a; Fr h, constant; };
+inline ShplonkLinearisation shplonk_linearisation(const std::vector<std::vector<Fr>> &points, const std::vector<std::vector<Fr>> &rem, const Fr &v, const Fr &u) {
+  const size_t M = points.size();
+  std::vector<Fr> super; for (size_t i = 0; i < M; i++) for (const auto &pt : points[i]) if (std::find(super.begin(), super.end(), pt) == super.end()) super.push_back(pt);
+  Fr zt = fr_one(); for (const auto &pt : super) zt = fr_mul(zt, fr_sub(u, pt));
+  const std::vector<Fr> vpow = powers(v, M);
+  std::vector<Fr> lc(M); Fr zd0 = fr_one(), cst = fr_zero();
+  for (size_t i = 0; i < M; i++) {
+    Fr zd = fr_one(); for (const auto &pt : super) if (std::find(points[i].begin(), points[i].end(), pt) == points[i].end()) zd = fr_mul(zd, fr_sub(u, pt));
+    if (i == 0) zd0 = zd;
+    lc[i] = fr_mul(vpow[i], zd); cst = fr_add(cst, fr_mul(lc[i], horner(rem[i], u)));
+  }
+  const Fr zi = fr_inv(zd0);
+  ShplonkLinearisation out; for (size_t i = 0; i < M; i++) out.a.push_back(fr_mul(lc[i], zi));
+  out.h = fr_neg(fr_mul(zt, zi)); out.constant = fr_mul(cst, zi);
+  return out;
+}
+
+// Commitments into the transcript.  One rule for a group of finished polynomials (steps 4 and 8): on small domains one batched pass whatever the count (one reduction tail
+// per batch); big ones keep one commitment per pass -- a batch of two at 2^24 doubles the sorter's workspace (8.8 GB) for no gain, and a multi-layer prover process has no
+// HBM to spare.
+struct Committer {
+  Transcript &T; uint32_t &msm; const uint64_t n;
+  static bool small_domain(uint64_t n) { return n <= (uint64_t(1) << 22); }
+  void commit_one(uint64_t basis, const void *ptr) { G1 out; check(mi355_msm_g1_dev(basis, 0, ptr, n, out.data())); msm++; T.write_point(out); }
+  void commit_many(uint64_t basis, const std::vector<const void *> &ptrs, uint32_t cap) {   // batched passes of at most `cap`
+    for (size_t base = 0; base < ptrs.size(); base += cap) {
+      const uint32_t cnt = (uint32_t)std::min<size_t>(cap, ptrs.size() - base); std::vector<G1> outs(cnt);
+      check(mi355_msm_g1_batch_dev(basis, 0, ptrs.data() + base, cnt, n, outs.data())); msm += cnt;
+      for (const auto &o : outs) T.write_point(o);
     }
-  };
-  // ---- steps 1-3: the witness crosses PCIe on other host threads (rayon workers in the real caller); commitments as the columns arrive
-  std::vector<std::pair<uint32_t, const Column *>> uploads;
-  for (uint32_t i = 0; i < A; i++) uploads.push_back({P.phase0[0] + i, &wit.advice[i]});
-  const bool dev_m = opt.device_multiplicities && NL > 0;
-  const bool dev_rng = opt.device_randomness;
-  halo2::RngKey rng_key; std::memcpy(rng_key.data(), opt.rng_key, 32);
-  if (dev_rng && opt.rng_key_from_os) {
-    for (size_t got = 0; got < 32;) { const ssize_t r = getrandom(rng_key.data() + got, 32 - got, 0); if (r < 0) { if (errno == EINTR) continue; throw Error(MI355_EHIP, "create_proof: getrandom failed (errno " + std::to_string(errno) + "): no key for the device randomness"); } got += (size_t)r; }
   }
-  // rows [u + 1, n) of a group of resident columns (all on one device) in ONE launch; column i of the group draws the blocks (first + i) * blind + j of `stream`
-  auto draw_blinding = [&](const std::vector<void *> &cols, uint64_t stream, uint64_t first) {
-    if (!P.blind || cols.empty()) return;
-    const auto t0 = Clock::now();
-    halo2::fr_random_rows(cols, u + 1, P.blind, rng_key, stream, first * P.blind);
-    R.random_ms += ms_since(t0);
-  };
-  if (dev_rng) for (uint32_t i = 0; i < A; i++) if (wit.advice.at(i).size() < u + 1) throw std::invalid_argument("create_proof: advice column " + std::to_string(i) + " has fewer than the usable rows + 1");
-  if (dev_m && !dev_rng && wit.m_blind.size() != NL) throw std::invalid_argument("create_proof: device_multiplicities needs the blinding values of every multiplicity column (Circuit::m_blind)");
-  if (!dev_m) for (uint32_t l = 0; l < NL; l++) uploads.push_back({P.phase0[1] + l, &wit.m[l]});
-  if (!dev_rng) uploads.push_back({P.random_poly, &wit.random_poly});                     // step 5's polynomial (coefficients): needed last, crosses last
-  for (const auto &up : uploads) poly[up.first];
-  poly[P.random_poly];
-  poly[P.inst0];
-  for (uint32_t l = 0; l < NL; l++) poly[P.phase0[1] + l];
-  for (const auto &c : P.perm) poly[c.z];                                                 // every entry exists before the uploaders start: the map's structure does not change under them
-  for (const auto &l : P.lookups) poly[l.phi];
-  std::mutex mu; std::condition_variable cv; std::vector<char> arrived(uploads.size(), 0); std::string upload_error;
-  const size_t UT = (size_t)std::max(1, std::min<int>(opt.upload_threads, (int)uploads.size()));
+  void commit_group(uint64_t basis, const std::vector<const void *> &ptrs, bool batched, uint32_t cap) { if (batched) commit_many(basis, ptrs, cap); else for (const void *p : ptrs) commit_one(basis, p); }
+  // columns of `poly` committed in the order of `refs`, at most `cap` per pass (cap 1: single commitments): wait(i) returns once refs[i] is on the device, done(pass) runs
+  // after each pass with the columns it committed
+  template <class Wait, class Done> void commit_in_batches(uint64_t basis, const std::map<uint32_t, DevicePoly> &poly, const std::vector<uint32_t> &refs, uint32_t cap, Wait wait, Done done) {
+    std::vector<uint32_t> pass;
+    for (size_t i = 0; i < refs.size(); i++) {
+      wait(i); pass.push_back(refs[i]);
+      if (pass.size() < cap && i + 1 < refs.size()) continue;
+      if (cap == 1) commit_one(basis, poly.at(pass[0]).p);
+      else { std::vector<const void *> ptrs; for (uint32_t r : pass) ptrs.push_back(poly.at(r).p); commit_many(basis, ptrs, cap); }
+      done(pass); pass.clear();
+    }
+  }
+};
+
+// The state of one proof; the steps are SURVEY 3.2's, numbered as the replay record's step_ms and rust_shim/create_proof_resident.rs number them.
+struct ProofRun {
+  using Clock = std::chrono::steady_clock;
+  static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+  const uint64_t h_g, h_g_lagrange; const ProvingKey &pk; const Circuit &wit; const ProofOptions &opt; const Protocol &P; const EvaluationDomain &dom;
+  const uint32_t k, Q; const uint64_t n, u; const uint32_t A, NL, NZ; const int D; const bool dev_m, dev_rng;
+  const uint32_t batch_cap; const bool batch_cols, early_intt;   // steps 2 and 3: commitments per pass as the columns arrive; their coefficient copies made pass by pass
+  ProofResult R; const Clock::time_point t_start; Clock::time_point tl; Transcript T; Committer C;
+  halo2::RngKey rng_key; std::vector<Fr> ch; Fr x;
+  std::map<uint32_t, DevicePoly> poly;          // protocol index -> Lagrange values until step 6, coefficients afterwards
+  std::map<uint32_t, DevicePoly> coeff_early;   // coefficient copies made while the witness still arrives; step 6 moves them into `poly`
+  DevicePoly inst_lagrange;                     // the instance column's Lagrange values, from step 1's transform until step 4 has read them
+  DevicePoly h;                                 // the quotient: Q pieces of n coefficients, from step 7 on
+  std::map<PolyRot, Fr> evals;
+  // the witness crosses PCIe on other host threads (rayon workers in the real caller): arrived[i] is set, under up.mu, when uploads[i] is in `poly`
+  std::vector<std::pair<uint32_t, const Column *>> uploads; std::vector<char> arrived; std::condition_variable cv; size_t UT = 1;
   std::atomic<uint64_t> sparse_cols{0}, packed_cols{0}, link_bytes{0};
-  auto upload_worker = [&](size_t first) {
-    try {
-      std::vector<uint32_t> sidx; std::vector<Fr> svals;   // this worker's scratch for the sparse form
-      for (size_t i = first; i < uploads.size(); i += UT) {
-        // device_randomness: the block exists already and its rows [u + 1, n) are being drawn; rows [0, u + 1) cross the link.  The two regions are disjoint
-        const uint64_t len = dev_rng ? u + 1 : uploads[i].second->size();
-        if (uploads[i].second->size() < len) throw std::invalid_argument("create_proof: a witness column has fewer than the usable rows + 1");
-        DevicePoly d = dev_rng ? std::move(poly.at(uploads[i].first)) : DevicePoly(len, 0);
-        uint64_t nz = len;
-        if (opt.sparse_uploads && len >= (1u << 12) && uploads[i].first != P.random_poly) {
-          sidx.resize(len); svals.resize(len);
-          check(mi355_host_compact_nonzero(uploads[i].second->data(), len, sidx.data(), svals.data(), &nz, std::max(1, opt.threads / (int)UT)));
-        }
-        const bool is_m = uploads[i].first >= P.phase0[1] && uploads[i].first < P.phase0[1] + NL;
-        if (opt.packed_multiplicities && is_m && wit.m_counts.size() == NL) {
-          // a column whose KIND bounds its cells: counts below 2^32 on the rows up to l_last, then the prover's blinding values
-          check(mi355_buf_upload_packed(d.p, wit.m_counts[uploads[i].first - P.phase0[1]].data(), len, 4));
-          if (P.blind && !dev_rng) check(mi355_buf_upload(d.at(u + 1), uploads[i].second->data() + (u + 1), P.blind * 32));
-          packed_cols++; link_bytes += len * 4 + (dev_rng ? 0 : P.blind * 32);
-        }
-        else if (2 * nz <= len) { check(mi355_buf_upload_sparse(d.p, len, sidx.data(), svals.data(), nz)); sparse_cols++; link_bytes += nz * 36; }
-        else { check(mi355_buf_upload(d.p, uploads[i].second->data(), len * 32)); link_bytes += len * 32; }
-        { std::lock_guard<std::mutex> lk(mu); poly.at(uploads[i].first) = std::move(d); arrived[i] = 1; }
-        cv.notify_all();
-      }
-    } catch (const std::exception &e) { { std::lock_guard<std::mutex> lk(mu); upload_error = e.what(); std::fill(arrived.begin(), arrived.end(), 1); } cv.notify_all(); }
-  };
-  {                                                                                     // step 1's input, made NOW: the instance column (public values, zero below).  Its few words must
-    // cross PCIe before the uploader threads fill the copy stream: that stream is first-in first-out, and queued behind the witness this 1 KiB upload waited for the random polynomial
-    // of step 5 (2 GiB at k = 26) -- 33 ms of host time in step 1 of every k = 26 proof until round 6 (17 ms at k = 25).  No device-wide synchronisation either: mi355_buf_upload
-    // orders itself behind the zeroing of its block, and the compute stream behind the copy.
-    DevicePoly inst(n, 0); check(mi355_buf_zero(inst.p, n * 32));
-    if (!wit.instances.empty()) check(mi355_buf_upload(inst.p, wit.instances.data(), wit.instances.size() * 32));
-    poly.at(P.inst0) = std::move(inst);
+  StripedUploader up;                           // declared last: its threads are joined before anything they touch goes away
+
+  ProofRun(uint64_t h_g_, uint64_t h_g_lagrange_, const ProvingKey &pk_, const Circuit &wit_, const ProofOptions &opt_)
+      : h_g(h_g_), h_g_lagrange(h_g_lagrange_), pk(pk_), wit(wit_), opt(opt_), P(*pk_.P), dom(*pk_.dom), k(P.k), Q(P.Q), n(P.n), u(P.usable), A(P.num_advice()), NL((uint32_t)P.lookups.size()),
+        NZ((uint32_t)P.perm.size()), D(std::max(1, std::min<int>(opt_.devices, (int)Q))), dev_m(opt_.device_multiplicities && NL > 0), dev_rng(opt_.device_randomness),
+        batch_cap(opt_.commit_batch ? opt_.commit_batch : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (uint64_t(1) << 25) / n))), batch_cols(A >= 16 && batch_cap > 1),
+        early_intt(opt_.early_intt < 0 ? A >= 8 : opt_.early_intt != 0), t_start(Clock::now()), tl(t_start),
+        T(opt_.transcript == TranscriptKind::ByLayer ? reference_transcript(P) : opt_.transcript), C{T, R.msm, n} {
+    T.common_scalar(vk_transcript_scalar(P, pk.vk));
+    for (const auto &v : wit.instances) T.common_scalar(v);
+    std::memcpy(rng_key.data(), opt.rng_key, 32);
+    if (dev_rng && opt.rng_key_from_os) {
+      for (size_t got = 0; got < 32;) { const ssize_t r = getrandom(rng_key.data() + got, 32 - got, 0); if (r < 0) { if (errno == EINTR) continue; throw Error(MI355_EHIP, "create_proof: getrandom failed (errno " + std::to_string(errno) + "): no key for the device randomness"); } got += (size_t)r; }
+    }
   }
-  if (dev_rng) {                                                                        // the blocks of every uploaded column, their blinding rows drawn: one launch per kind of column
-    std::vector<void *> adv, ms;
-    for (size_t i = 0; i < uploads.size(); i++) { DevicePoly d(n, 0); (i < A ? adv : ms).push_back(d.p); poly.at(uploads[i].first) = std::move(d); }
-    draw_blinding(adv, RNG_STREAM_ADVICE_BLIND, 0); draw_blinding(ms, RNG_STREAM_M_BLIND, 0);
+  void lap(int step) { R.step_ms[step] += ms_since(tl); tl = Clock::now(); }
+  void squeeze_challenges(uint32_t count) { for (uint32_t i = 0; i < count; i++) ch.push_back(T.squeeze_challenge()); }
+  const void *coeff_ptr(uint32_t p) const { return P.is_pre(p) ? pk.pre_coeff.at(p).p : poly.at(p).p; }
+  Fr rot_point(int32_t rot) const { return fr_mul(x, rot_power(dom.omega, dom.omega_inv, rot)); }
+  uint32_t commit_pass() const { return opt.commit_batch ? opt.commit_batch : 32; }   // commitments per batched pass of a finished group
+  // rows [u + 1, n) of a group of resident columns (all on one device) in ONE launch; column i of the group draws the blocks i * blind + j of `stream`
+  void draw_blinding(const std::vector<uint32_t> &refs, uint64_t stream) {
+    if (!P.blind || refs.empty()) return;
+    const auto t0 = Clock::now();
+    std::vector<void *> cols; for (uint32_t r : refs) cols.push_back(poly.at(r).p);
+    halo2::fr_random_rows(cols, u + 1, P.blind, rng_key, stream, 0);
+    R.random_ms += ms_since(t0);
   }
-  struct Joiner { std::vector<std::thread> th; void join() { for (auto &t : th) if (t.joinable()) t.join(); } ~Joiner() { join(); } } uploaders;
-  for (size_t w = 0; w < UT; w++) uploaders.th.emplace_back(upload_worker, w);
-  auto wait_for = [&](size_t i) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return arrived[i] != 0; }); if (!upload_error.empty()) throw Error(MI355_EHIP, "witness upload: " + upload_error); };
-  const uint32_t batch_cap = opt.commit_batch ? opt.commit_batch : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (uint64_t(1) << 25) / n));
-  const bool batch_cols = A >= 16 && batch_cap > 1;
-  const bool early_intt = opt.early_intt < 0 ? A >= 8 : opt.early_intt != 0;
-  std::map<uint32_t, DevicePoly> coeff_early;
-  auto to_coeff_early = [&](const std::vector<uint32_t> &refs) {
+  void wait_for(size_t i) { std::unique_lock<std::mutex> lk(up.mu); cv.wait(lk, [&] { return arrived[i] != 0; }); if (!up.error.empty()) throw Error(MI355_EHIP, "witness upload: " + up.error); }
+  void to_coeff_early(const std::vector<uint32_t> &refs) {
     if (!early_intt) return;
     std::vector<void *> ptrs;
     for (uint32_t r : refs) { DevicePoly c = clone(poly.at(r), 0); ptrs.push_back(c.p); coeff_early[r] = std::move(c); }
     check(mi355_ntt_fr_batch_dev(ptrs.data(), (uint32_t)ptrs.size(), k, dom.omega_inv.data(), dom.ifft_divisor.data())); R.intt += (uint32_t)ptrs.size();
-  };
-  auto commit_phase = [&](size_t lo, size_t hi) {                                       // uploads[lo, hi): one phase's columns, committed in order as they arrive
-    std::vector<uint32_t> pending;
-    for (size_t i = lo; i < hi; i++) {
-      wait_for(i);
-      if (!batch_cols) { commit_one(h_g_lagrange, poly.at(uploads[i].first).p); to_coeff_early({uploads[i].first}); }
-      else { pending.push_back(uploads[i].first); if (pending.size() == batch_cap || i + 1 == hi) { commit_many(h_g_lagrange, pending); to_coeff_early(pending); pending.clear(); } }
+  }
+  // one phase's columns, committed in order: uploads[lo, hi) as they arrive, or columns made on the device
+  template <class Wait> void commit_columns(const std::vector<uint32_t> &refs, Wait wait) {
+    C.commit_in_batches(h_g_lagrange, poly, refs, batch_cols ? batch_cap : 1, wait, [this](const std::vector<uint32_t> &pass) { to_coeff_early(pass); });
+  }
+  void commit_uploaded(size_t lo, size_t hi) { std::vector<uint32_t> refs; for (size_t i = lo; i < hi; i++) refs.push_back(uploads[i].first); commit_columns(refs, [this, lo](size_t i) { wait_for(lo + i); }); }
+
+  // uploads[i] crosses the link in the cheapest form its content allows; sidx / svals: the calling worker's scratch for the sparse form
+  void upload_column(size_t i, std::vector<uint32_t> &sidx, std::vector<Fr> &svals) {
+    // device_randomness: the block exists already and its rows [u + 1, n) are being drawn; rows [0, u + 1) cross the link.  The two regions are disjoint
+    const uint64_t len = dev_rng ? u + 1 : uploads[i].second->size();
+    if (uploads[i].second->size() < len) throw std::invalid_argument("create_proof: a witness column has fewer than the usable rows + 1");
+    DevicePoly d = dev_rng ? std::move(poly.at(uploads[i].first)) : DevicePoly(len, 0);
+    uint64_t nz = len;
+    if (opt.sparse_uploads && len >= (1u << 12) && uploads[i].first != P.random_poly) {
+      sidx.resize(len); svals.resize(len);
+      check(mi355_host_compact_nonzero(uploads[i].second->data(), len, sidx.data(), svals.data(), &nz, std::max(1, opt.threads / (int)UT)));
     }
-  };
-  std::vector<Fr> ch;
-  commit_phase(0, A);                                                                   // step 2
-  for (uint32_t i = 0; i < P.num_challenge[0]; i++) ch.push_back(T.squeeze_challenge()); // theta
-  if (!dev_m) commit_phase(A, A + NL);                                                  // step 3 (the multiplicities are the caller's: they do not depend on theta for the lookups halo2 compresses)
-  else {
-    // step 3 as the scroll fork's mv_lookup prover runs it [EXT-recalled halo2_proofs src/plonk/mv_lookup/prover.rs, `prepare`]: table and input compressed with theta (the
-    // expressions of step 4 without the beta term, into TMP 0 / 1), every input cell of the usable rows looked up in the table's usable rows on the device, the rng's blinding
-    // values into the last rows.  The instance column still holds its Lagrange values here (step 1's inverse transform comes after step 3).  Commitments as commit_phase makes them.
+    const bool is_m = uploads[i].first >= P.phase0[1] && uploads[i].first < P.phase0[1] + NL;
+    if (opt.packed_multiplicities && is_m && wit.m_counts.size() == NL) {
+      // a column whose KIND bounds its cells: counts below 2^32 on the rows up to l_last, then the prover's blinding values
+      check(mi355_buf_upload_packed(d.p, wit.m_counts[uploads[i].first - P.phase0[1]].data(), len, 4));
+      if (P.blind && !dev_rng) check(mi355_buf_upload(d.at(u + 1), uploads[i].second->data() + (u + 1), P.blind * 32));
+      packed_cols++; link_bytes += len * 4 + (dev_rng ? 0 : P.blind * 32);
+    }
+    else if (2 * nz <= len) { check(mi355_buf_upload_sparse(d.p, len, sidx.data(), svals.data(), nz)); sparse_cols++; link_bytes += nz * 36; }
+    else { check(mi355_buf_upload(d.p, uploads[i].second->data(), len * 32)); link_bytes += len * 32; }
+    { std::lock_guard<std::mutex> lk(up.mu); poly.at(uploads[i].first) = std::move(d); arrived[i] = 1; }
+    cv.notify_all();
+  }
+
+  // ---- steps 1-3: the uploads start; commitments as the columns arrive; theta; the multiplicities; beta, gamma
+  void witness_commits() {
+    for (uint32_t i = 0; i < A; i++) uploads.push_back({P.phase0[0] + i, &wit.advice[i]});
+    if (!dev_m) for (uint32_t l = 0; l < NL; l++) uploads.push_back({P.phase0[1] + l, &wit.m[l]});
+    if (!dev_rng) uploads.push_back({P.random_poly, &wit.random_poly});                   // step 5's polynomial (coefficients): needed last, crosses last
+    for (const auto &up_ : uploads) poly[up_.first];
+    poly[P.random_poly];
+    poly[P.inst0];
+    for (uint32_t l = 0; l < NL; l++) poly[P.phase0[1] + l];
+    for (const auto &c : P.perm) poly[c.z];                                               // every entry exists before the uploaders start: the map's structure does not change under them
+    for (const auto &l : P.lookups) poly[l.phi];
+    {                                                                                     // step 1's input, made NOW: the instance column (public values, zero below).  Its few words must
+      // cross PCIe before the uploader threads fill the copy stream: that stream is first-in first-out, and queued behind the witness this 1 KiB upload waited for the random polynomial
+      // of step 5 (2 GiB at k = 26) -- 33 ms of host time in step 1 of every k = 26 proof until round 6 (17 ms at k = 25).  No device-wide synchronisation either: mi355_buf_upload
+      // orders itself behind the zeroing of its block, and the compute stream behind the copy.
+      DevicePoly inst(n, 0); check(mi355_buf_zero(inst.p, n * 32));
+      if (!wit.instances.empty()) check(mi355_buf_upload(inst.p, wit.instances.data(), wit.instances.size() * 32));
+      poly.at(P.inst0) = std::move(inst);
+    }
+    if (dev_rng) {                                                                        // the blocks of every uploaded column, their blinding rows drawn: one launch per kind of column
+      std::vector<uint32_t> adv, ms;
+      for (size_t i = 0; i < uploads.size(); i++) { poly.at(uploads[i].first) = DevicePoly(n, 0); (i < A ? adv : ms).push_back(uploads[i].first); }
+      draw_blinding(adv, RNG_STREAM_ADVICE_BLIND); draw_blinding(ms, RNG_STREAM_M_BLIND);
+    }
+    arrived.assign(uploads.size(), 0);
+    UT = (size_t)std::max(1, std::min<int>(opt.upload_threads, (int)uploads.size()));
+    up.start(uploads.size(), UT, false, [this, sidx = std::vector<uint32_t>(), svals = std::vector<Fr>()](size_t i) mutable { upload_column(i, sidx, svals); },
+             [this] { std::fill(arrived.begin(), arrived.end(), 1); cv.notify_all(); });
+    commit_uploaded(0, A);                                                                // step 2
+    squeeze_challenges(P.num_challenge[0]);                                               // theta
+    if (!dev_m) commit_uploaded(A, A + NL);                                               // step 3 (the multiplicities are the caller's: they do not depend on theta for the lookups halo2 compresses)
+    else device_multiplicities();
+    squeeze_challenges(P.num_challenge[1]);                                               // beta, gamma
+  }
+  // step 3 as the scroll fork's mv_lookup prover runs it [EXT-recalled halo2_proofs src/plonk/mv_lookup/prover.rs, `prepare`]: table and input compressed with theta (the
+  // expressions of step 4 without the beta term, into TMP 0 / 1), every input cell of the usable rows looked up in the table's usable rows on the device, the rng's blinding
+  // values into the last rows.  The instance column still holds its Lagrange values here (step 1's inverse transform comes after step 3).  Commitments as step 2 makes them.
+  void device_multiplicities() {
     const auto t_m = Clock::now();
-    Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, ch);
-    std::vector<DevicePoly> tmp;
-    auto tmp_at = [&](uint32_t i) -> DevicePoly & { while (tmp.size() <= i) tmp.emplace_back(n, 0); return tmp[i]; };
-    auto resolve = [&](const Atom &a) -> const void * {
-      if (a.kind == A_TMP) return tmp_at(a.idx).p;
-      if (a.kind == A_COMMON) { if (a.idx != pk.identity_common) throw std::invalid_argument("step 3 reads no common polynomial but X"); return pk.common_lagrange[a.idx].p; }
-      if (P.is_pre(a.idx)) { if (!pk.pre_lagrange[a.idx].p) throw std::invalid_argument("step 3: Lagrange values of a preprocessed polynomial were not kept"); return pk.pre_lagrange[a.idx].p; }
-      return poly.at(a.idx).p;   // advice (committed in step 2) or the instance column (Lagrange values)
-    };
     std::vector<uint32_t> made;
-    for (uint32_t l = 0; l < NL; l++) {
-      const Lookup &lk = P.lookups[l];
-      cmp.tmp_base = 2; cmp.tmp_next = 0;
-      cmp.emit(0, cmp.compile(*lk.table)); cmp.emit(1, cmp.compile(*lk.input));
-      for (const auto &L : cmp.out) { run_launch(L, tmp_at((uint32_t)L.dst).p, n, fr_one(), L.accumulate, resolve); R.gate_launches++; }
-      cmp.out.clear();
-      DevicePoly m(n, 0);
-      const void *inputs[1] = {tmp_at(1).p}; uint64_t missing = ~0ull;
-      const int rc = mi355_fr_lookup_multiplicities_dev(m.p, n, tmp_at(0).p, u, inputs, 1, u, opt.multiplicity_rule_last ? 1u : 0u, &missing);
-      if (rc == MI355_EBADARG && missing != ~0ull) throw Error(MI355_EBADARG, "lookup " + std::to_string(l) + ": input row " + std::to_string(missing & ((uint64_t(1) << 40) - 1)) + " is not in the table");
-      check(rc);
-      if (P.blind && !dev_rng) check(mi355_buf_upload(m.at(u + 1), wit.m_blind[l].data(), P.blind * 32));
-      { std::lock_guard<std::mutex> lk_(mu); poly.at(P.phase0[1] + l) = std::move(m); }
-      made.push_back(P.phase0[1] + l);
-    }
-    if (dev_rng) { std::vector<void *> ms; for (uint32_t r : made) ms.push_back(poly.at(r).p); draw_blinding(ms, RNG_STREAM_M_BLIND, 0); }
-    tmp.clear();
-    R.multiplicity_ms = ms_since(t_m);
-    std::vector<uint32_t> pending;
-    for (size_t i = 0; i < made.size(); i++) {
-      if (!batch_cols) { commit_one(h_g_lagrange, poly.at(made[i]).p); to_coeff_early({made[i]}); }
-      else { pending.push_back(made[i]); if (pending.size() == batch_cap || i + 1 == made.size()) { commit_many(h_g_lagrange, pending); to_coeff_early(pending); pending.clear(); } }
-    }
-  }
-  for (uint32_t i = 0; i < P.num_challenge[1]; i++) ch.push_back(T.squeeze_challenge()); // beta, gamma
-  const Fr beta = ch.at(1), gamma = ch.at(2);
-  lap(2);
-  DevicePoly inst_lagrange = clone(poly.at(P.inst0), 0);
-  check(mi355_intt_fr_dev(poly.at(P.inst0).p, k, dom.omega_inv.data(), dom.ifft_divisor.data())); R.intt++;
-  lap(1);
-  // ---- step 4: grand products and running sums, built on the device from the Lagrange values
-  {
-    uint32_t max_chunk = 0; for (const auto &c : P.perm) max_chunk = std::max<uint32_t>(max_chunk, (uint32_t)c.columns.size());
-    Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, ch);
-    std::vector<DevicePoly> tmp;
-    auto tmp_at = [&](uint32_t i) -> DevicePoly & { while (tmp.size() <= i) tmp.emplace_back(n, 0); return tmp[i]; };
-    auto resolve = [&](const Atom &a) -> const void * {
-      if (a.kind == A_TMP) return tmp_at(a.idx).p;
-      if (a.kind == A_COMMON) { if (a.idx != pk.identity_common) throw std::invalid_argument("step 4 reads no common polynomial but X"); return pk.common_lagrange[a.idx].p; }
-      if (P.is_pre(a.idx)) { if (!pk.pre_lagrange[a.idx].p) throw std::invalid_argument("step 4: Lagrange values of a preprocessed polynomial were not kept"); return pk.pre_lagrange[a.idx].p; }
-      if (P.is_instance(a.idx)) return inst_lagrange.p;
-      return poly.at(a.idx).p;
-    };
-    auto run_all = [&]() { for (const auto &L : cmp.out) { run_launch(L, tmp_at((uint32_t)L.dst).p, n, fr_one(), L.accumulate, resolve); R.gate_launches++; } cmp.out.clear(); };
-    Fr carry = fr_one();
-    for (uint32_t c = 0; c < NZ; c++) {
-      const PermChunk &chunk = P.perm[c]; const uint32_t cl = (uint32_t)chunk.columns.size();
-      SoP us{Term{fr_one(), {}}}, vs{Term{fr_one(), {}}};
-      cmp.tmp_base = 2; cmp.tmp_next = 0;
-      for (uint32_t j = 0; j < cl; j++) {
-        const PermColumn &pc = chunk.columns[j];
-        SoP uj{Term{fr_one(), {Atom{A_POLY, pc.column, 0}}}, Term{fr_mul(beta, pc.delta_pow), {Atom{A_COMMON, pk.identity_common, 0}}}, Term{gamma, {}}};
-        SoP vj{Term{fr_one(), {Atom{A_POLY, pc.column, 0}}}, Term{beta, {Atom{A_POLY, pc.sigma, 0}}}, Term{gamma, {}}};
-        us = cmp.product(std::move(us), cmp.materialize(uj)); vs = cmp.product(std::move(vs), cmp.materialize(vj));
+    {
+      LagrangePlan plan(pk, "step 3", ch, [this](uint32_t p) { return poly.at(p).p; });   // advice (committed in step 2) or the instance column (Lagrange values)
+      for (uint32_t l = 0; l < NL; l++) {
+        plan.compress_lookup(P.lookups[l]);
+        DevicePoly m(n, 0);
+        const auto miss = plan.multiplicities(m.p, u, opt.multiplicity_rule_last ? 1u : 0u);
+        if (miss.any) throw Error(MI355_EBADARG, describe(VerifyFailure{VerifyFailure::Lookup, l, miss.row, 1, miss.input, 0, 0}));
+        if (P.blind && !dev_rng) check(mi355_buf_upload(m.at(u + 1), wit.m_blind[l].data(), P.blind * 32));
+        { std::lock_guard<std::mutex> lk(up.mu); poly.at(P.phase0[1] + l) = std::move(m); }
+        made.push_back(P.phase0[1] + l);
       }
-      cmp.emit(0, us); cmp.emit(1, vs);                                                  // TMP[0] = prod_j u_j, TMP[1] = prod_j v_j
-      run_all();
-      check(mi355_fr_batch_invert_dev(tmp_at(1).p, n));
-      check(mi355_fr_vec_op_dev(2, tmp_at(0).p, tmp_at(0).p, tmp_at(1).p, n));
-      DevicePoly z(n, 0);
-      check(mi355_fr_prefix_product_dev(z.p, tmp_at(0).p, n, nullptr));                  // z[0] = 1, z[i + 1] = z[i] prod u / prod v
-      if (c > 0) check(mi355_fr_vec_axpy_dev(z.p, nullptr, z.p, carry.data(), n));       // chunk c starts where chunk c - 1 ended: z_c(1) = z_(c-1)(w^last)
-      if (c + 1 < NZ) check(mi355_buf_download(carry.data(), z.at(u), 32));
-      if (P.blind && !dev_rng) check(mi355_buf_upload(z.at(u + 1), wit.z_blind.at(c).data(), P.blind * 32));
-      poly.at(chunk.z) = std::move(z);
-    }
-    if (dev_rng) { std::vector<void *> zs; for (uint32_t c = 0; c < NZ; c++) zs.push_back(poly.at(P.perm[c].z).p); draw_blinding(zs, RNG_STREAM_Z_BLIND, 0); }
-    for (uint32_t l = 0; l < NL; l++) {                                                 // phi[i + 1] = phi[i] + 1 / (I + beta) - m / (T + beta)
-      const Lookup &lk = P.lookups[l];
-      cmp.tmp_base = 4; cmp.tmp_next = 0;
-      SoP tb = cmp.compile(*lk.table); tb.push_back(Term{beta, {}}); Compiler::merge_scalars(tb);
-      SoP ib = cmp.compile(*lk.input); ib.push_back(Term{beta, {}}); Compiler::merge_scalars(ib);
-      cmp.emit(0, tb); cmp.emit(1, ib);
-      const Atom t0{A_TMP, 0, 0}, t1{A_TMP, 1, 0}, mm{A_POLY, lk.m, 0};
-      cmp.emit(2, SoP{Term{fr_one(), {t0, t1}}});
-      cmp.emit(3, SoP{Term{fr_one(), {t0}}, Term{fr_neg(fr_one()), {mm, t1}}});
-      run_all();
-      check(mi355_fr_batch_invert_dev(tmp_at(2).p, n));
-      check(mi355_fr_vec_op_dev(2, tmp_at(3).p, tmp_at(3).p, tmp_at(2).p, n));
-      DevicePoly phi(n, 0);
-      check(mi355_fr_prefix_sum_dev(phi.p, tmp_at(3).p, n, nullptr));
-      if (P.blind && !dev_rng) check(mi355_buf_upload(phi.at(u + 1), wit.phi_blind.at(l).data(), P.blind * 32));
-      poly.at(lk.phi) = std::move(phi);
-    }
-    if (dev_rng) { std::vector<void *> phis; for (uint32_t l = 0; l < NL; l++) phis.push_back(poly.at(P.lookups[l].phi).p); draw_blinding(phis, RNG_STREAM_PHI_BLIND, 0); }
-    std::vector<uint32_t> made; for (uint32_t c = 0; c < NZ; c++) made.push_back(P.perm[c].z); for (uint32_t l = 0; l < NL; l++) made.push_back(P.lookups[l].phi);
-    // small domains: one pass whatever the count (round 6: one reduction tail per batch); big ones keep one commitment per pass -- a batch of two at 2^24 doubles the sorter's
-    // workspace (8.8 GB) for no gain, and a multi-layer prover process has no HBM to spare
-    if (made.size() >= 8 || n <= (uint64_t(1) << 22)) commit_many(h_g_lagrange, made); else for (uint32_t r : made) commit_one(h_g_lagrange, poly.at(r).p);
-    inst_lagrange.release();
+      if (dev_rng) draw_blinding(made, RNG_STREAM_M_BLIND);
+      R.gate_launches += plan.launches;
+    }                                                                                     // the temporaries go before the commitments
+    R.multiplicity_ms = ms_since(t_m);
+    commit_columns(made, [](size_t) {});
   }
-  lap(4);
+  // ---- step 1's transform: the instance column to coefficients; step 4 still reads its Lagrange values
+  void instance_to_coefficients() {
+    inst_lagrange = clone(poly.at(P.inst0), 0);
+    check(mi355_intt_fr_dev(poly.at(P.inst0).p, k, dom.omega_inv.data(), dom.ifft_divisor.data())); R.intt++;
+  }
+  // ---- step 4: grand products and running sums, built on the device from the Lagrange values
+  void products_and_sums() {
+    const Fr beta = ch.at(1), gamma = ch.at(2);
+    std::vector<uint32_t> made;
+    {
+      LagrangePlan plan(pk, "step 4", ch, [this](uint32_t p) { return P.is_instance(p) ? inst_lagrange.p : poly.at(p).p; });
+      Compiler &cmp = plan.cmp;
+      Fr carry = fr_one();
+      for (uint32_t c = 0; c < NZ; c++) {
+        const PermChunk &chunk = P.perm[c]; const uint32_t cl = (uint32_t)chunk.columns.size();
+        SoP us{Term{fr_one(), {}}}, vs{Term{fr_one(), {}}};
+        cmp.tmp_base = 2; cmp.tmp_next = 0;
+        for (uint32_t j = 0; j < cl; j++) {
+          const PermColumn &pc = chunk.columns[j];
+          SoP uj{Term{fr_one(), {Atom{A_POLY, pc.column, 0}}}, Term{fr_mul(beta, pc.delta_pow), {Atom{A_COMMON, pk.identity_common, 0}}}, Term{gamma, {}}};
+          SoP vj{Term{fr_one(), {Atom{A_POLY, pc.column, 0}}}, Term{beta, {Atom{A_POLY, pc.sigma, 0}}}, Term{gamma, {}}};
+          us = cmp.product(std::move(us), cmp.materialize(uj)); vs = cmp.product(std::move(vs), cmp.materialize(vj));
+        }
+        cmp.emit(0, us); cmp.emit(1, vs);                                                  // TMP[0] = prod_j u_j, TMP[1] = prod_j v_j
+        plan.run();
+        check(mi355_fr_batch_invert_dev(plan.tmp_at(1).p, n));
+        check(mi355_fr_vec_op_dev(2, plan.tmp_at(0).p, plan.tmp_at(0).p, plan.tmp_at(1).p, n));
+        DevicePoly z(n, 0);
+        check(mi355_fr_prefix_product_dev(z.p, plan.tmp_at(0).p, n, nullptr));             // z[0] = 1, z[i + 1] = z[i] prod u / prod v
+        if (c > 0) check(mi355_fr_vec_axpy_dev(z.p, nullptr, z.p, carry.data(), n));       // chunk c starts where chunk c - 1 ended: z_c(1) = z_(c-1)(w^last)
+        if (c + 1 < NZ) check(mi355_buf_download(carry.data(), z.at(u), 32));
+        if (P.blind && !dev_rng) check(mi355_buf_upload(z.at(u + 1), wit.z_blind.at(c).data(), P.blind * 32));
+        poly.at(chunk.z) = std::move(z); made.push_back(chunk.z);
+      }
+      if (dev_rng) draw_blinding(made, RNG_STREAM_Z_BLIND);
+      for (uint32_t l = 0; l < NL; l++) {                                                 // phi[i + 1] = phi[i] + 1 / (I + beta) - m / (T + beta)
+        const Lookup &lk = P.lookups[l];
+        cmp.tmp_base = 4; cmp.tmp_next = 0;
+        SoP tb = cmp.compile(*lk.table); tb.push_back(Term{beta, {}}); Compiler::merge_scalars(tb);
+        SoP ib = cmp.compile(*lk.input); ib.push_back(Term{beta, {}}); Compiler::merge_scalars(ib);
+        cmp.emit(0, tb); cmp.emit(1, ib);
+        const Atom t0{A_TMP, 0, 0}, t1{A_TMP, 1, 0}, mm{A_POLY, lk.m, 0};
+        cmp.emit(2, SoP{Term{fr_one(), {t0, t1}}});
+        cmp.emit(3, SoP{Term{fr_one(), {t0}}, Term{fr_neg(fr_one()), {mm, t1}}});
+        plan.run();
+        check(mi355_fr_batch_invert_dev(plan.tmp_at(2).p, n));
+        check(mi355_fr_vec_op_dev(2, plan.tmp_at(3).p, plan.tmp_at(3).p, plan.tmp_at(2).p, n));
+        DevicePoly phi(n, 0);
+        check(mi355_fr_prefix_sum_dev(phi.p, plan.tmp_at(3).p, n, nullptr));
+        if (P.blind && !dev_rng) check(mi355_buf_upload(phi.at(u + 1), wit.phi_blind.at(l).data(), P.blind * 32));
+        poly.at(lk.phi) = std::move(phi); made.push_back(lk.phi);
+      }
+      if (dev_rng) draw_blinding(std::vector<uint32_t>(made.begin() + NZ, made.end()), RNG_STREAM_PHI_BLIND);
+      std::vector<const void *> ptrs; for (uint32_t r : made) ptrs.push_back(poly.at(r).p);
+      C.commit_group(h_g_lagrange, ptrs, made.size() >= 8 || Committer::small_domain(n), commit_pass());
+      R.gate_launches += plan.launches;
+      inst_lagrange.release();
+    }                                                                                     // step 4's temporaries go before step 5
+  }
   // ---- step 5: the random polynomial of the vanishing argument: one commitment on the coefficient basis, one evaluation later, no transform
-  if (!uploads.empty()) wait_for(uploads.size() - 1);
-  uploaders.join();
-  if (dev_rng) {                                                                        // drawn where it lives: nothing crosses the link.  Waited for, so that random_ms holds the draw
-    const auto t0 = Clock::now();                                                         // (with the block's allocation and whatever the stream still held; the commitment below waits anyway)
-    DevicePoly rp(n, 0); rp.random(rng_key, RNG_STREAM_RANDOM_POLY, 0); check(mi355_synchronize());
-    poly.at(P.random_poly) = std::move(rp);
-    R.random_ms += ms_since(t0);
+  void random_polynomial() {
+    if (!uploads.empty()) wait_for(uploads.size() - 1);
+    up.join();
+    if (dev_rng) {                                                                        // drawn where it lives: nothing crosses the link.  Waited for, so that random_ms holds the draw
+      const auto t0 = Clock::now();                                                         // (with the block's allocation and whatever the stream still held; the commitment below waits anyway)
+      DevicePoly rp(n, 0); rp.random(rng_key, RNG_STREAM_RANDOM_POLY, 0); check(mi355_synchronize());
+      poly.at(P.random_poly) = std::move(rp);
+      R.random_ms += ms_since(t0);
+    }
+    C.commit_one(h_g, poly.at(P.random_poly).p);
+    squeeze_challenges(P.num_challenge[2]);                                               // y
   }
-  commit_one(h_g, poly.at(P.random_poly).p);
-  for (uint32_t i = 0; i < P.num_challenge[2]; i++) ch.push_back(T.squeeze_challenge()); // y
-  lap(5);
   // ---- step 6: every witness polynomial to coefficients, one batched call
-  {
+  void to_coefficients() {
     std::vector<void *> ptrs;
     for (auto &kv : poly) if (kv.first != P.inst0 && kv.first != P.random_poly && !coeff_early.count(kv.first)) ptrs.push_back(kv.second.p);
     if (!ptrs.empty()) check(mi355_ntt_fr_batch_dev(ptrs.data(), (uint32_t)ptrs.size(), k, dom.omega_inv.data(), dom.ifft_divisor.data()));
@@ -873,10 +946,9 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
     for (auto &kv : coeff_early) poly.at(kv.first) = std::move(kv.second);
     coeff_early.clear();
   }
-  lap(6);
-  // ---- step 7: the quotient, coset part by coset part; part q on device q % D (the proving key's cosets of that part live there)
-  DevicePoly h(Q * n, 0);
-  {
+  // ---- step 7: the quotient, coset part by coset part; part q on device q % D (the proving key's cosets of that part live there).  Everything but h goes before step 8
+  void quotient() {
+    h = DevicePoly(Q * n, 0);
     Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, ch);
     cmp.compile_numerator(P.numerator);
     R.plan_launches = (uint32_t)cmp.out.size(); R.plan_terms = cmp.terms_total; R.plan_tmps = cmp.tmps_used(); R.plan_constraints = cmp.constraints; R.plan_prefix_groups = cmp.prefix_groups;
@@ -928,25 +1000,19 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
         }
       } catch (const std::exception &e) { errs[d] = e.what(); }
     };
-    { std::vector<std::thread> th; for (int d = 1; d < D; d++) th.emplace_back(do_parts, d); do_parts(0); for (auto &x : th) x.join(); }
+    { Joiner others; for (int d = 1; d < D; d++) others.th.emplace_back(do_parts, d); do_parts(0); others.join(); }
     for (int d = 0; d < D; d++) { if (!errs[d].empty()) throw Error(MI355_EHIP, "quotient part on device slot " + std::to_string(d) + ": " + errs[d]); R.gate_launches += launches[d]; R.coset_ntt += cosets[d]; }
     { std::vector<const void *> pp(Q); for (uint32_t q = 0; q < Q; q++) pp[q] = hpart[q].p; check(mi355_fr_interleave_dev(h.p, pp.data(), Q, n)); }
     check(mi355_extended_to_coeff_dev(h.p, dom.extended_k, dom.g_coset.data(), dom.g_coset_inv.data(), dom.extended_omega_inv.data(), dom.extended_ifft_divisor.data()));
   }
-  lap(7);
-  if (n > (uint64_t(1) << 22)) { for (uint32_t q = 0; q < Q; q++) commit_one(h_g, h.at((uint64_t)q * n)); }   // step 8, big domains: one commitment per pass (see step 4)
-  else {                                                                                // step 8: the Q pieces of h, one batched pass (at k = 20 / 21 one reduction tail instead of Q)
-    std::vector<const void *> ptrs(Q); std::vector<G1> outs(Q);
-    for (uint32_t q = 0; q < Q; q++) ptrs[q] = h.at((uint64_t)q * n);
-    check(mi355_msm_g1_batch_dev(h_g, 0, ptrs.data(), Q, n, outs.data())); R.msm += Q;
-    for (uint32_t q = 0; q < Q; q++) T.write_point(outs[q]);
+  // ---- step 8: the Q pieces of h, on small domains in one batched pass (at k = 20 / 21 one reduction tail instead of Q); x
+  void commit_quotient() {
+    std::vector<const void *> ptrs(Q); for (uint32_t q = 0; q < Q; q++) ptrs[q] = h.at((uint64_t)q * n);
+    C.commit_group(h_g, ptrs, Committer::small_domain(n), Q);
+    x = T.squeeze_challenge();
   }
-  const Fr x = T.squeeze_challenge();
-  lap(8);
-  auto coeff_ptr = [&](uint32_t p) -> const void * { return P.is_pre(p) ? pk.pre_coeff.at(p).p : poly.at(p).p; };
-  auto rot_point = [&](int32_t rot) { Fr pt = x; if (rot > 0) pt = fr_mul(pt, fr_pow(dom.omega, (uint64_t)rot)); else if (rot < 0) pt = fr_mul(pt, fr_pow(dom.omega_inv, (uint64_t)(-(int64_t)rot))); return pt; };
-  std::map<PolyRot, Fr> evals;
-  {                                                                                     // step 9: the evaluations, in the protocol's order; plus the Q pieces at x (for the combined quotient's value)
+  // ---- step 9: the evaluations, in the protocol's order; plus the Q pieces at x (for the combined quotient's value)
+  void evaluations() {
     std::vector<const void *> ptrs; std::vector<Fr> pts;
     for (const auto &e : P.evaluations) { ptrs.push_back(coeff_ptr(e.poly)); pts.push_back(rot_point(e.rot)); }
     for (uint32_t q = 0; q < Q; q++) { ptrs.push_back(h.at((uint64_t)q * n)); pts.push_back(x); }
@@ -954,87 +1020,86 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
     check(mi355_eval_polynomial_batch_dev(ptrs.data(), (uint32_t)ptrs.size(), n, pts.data(), ev.data()));
     for (size_t i = 0; i < P.evaluations.size(); i++) { evals[P.evaluations[i]] = ev[i]; T.write_scalar(ev[i]); }
     R.evals = (uint32_t)P.evaluations.size();
-    const Fr xn = fr_pow(x, n); Fr f = fr_one(), hx = fr_zero();
-    for (uint32_t q = 0; q < Q; q++) { hx = fr_add(hx, fr_mul(f, ev[P.evaluations.size() + q])); f = fr_mul(f, xn); }
+    const std::vector<Fr> xnpow = powers(fr_pow(x, n), Q); Fr hx = fr_zero();
+    for (uint32_t q = 0; q < Q; q++) hx = fr_add(hx, fr_mul(xnpow[q], ev[P.evaluations.size() + q]));
     evals[{P.quotient_poly, 0}] = hx;
   }
-  lap(9);
-  {                                                                                     // step 10: SHPLONK
+  // ---- step 10: SHPLONK
+  void shplonk() {
     // the vanishing argument opens ONE combined quotient polynomial h_0 + x^n h_1 + ...
     DevicePoly hcomb(n, 0);
-    {
-      const Fr xn = fr_pow(x, n); std::vector<const void *> pp(Q); std::vector<Fr> cs(Q); std::vector<uint32_t> tl_(Q, 1), fp(Q); std::vector<int32_t> fr_(Q, 0);
-      Fr f = fr_one(); for (uint32_t q = 0; q < Q; q++) { pp[q] = h.at((uint64_t)q * n); cs[q] = f; f = fr_mul(f, xn); fp[q] = q; }
-      gate_eval(hcomb.p, pp.data(), Q, cs.data(), tl_.data(), Q, fp.data(), fr_.data(), n, 0); R.gate_launches++;
-    }
-    auto opened = [&](uint32_t p) -> const void * { return p == P.quotient_poly ? hcomb.p : coeff_ptr(p); };
+    { std::vector<const void *> pp(Q); for (uint32_t q = 0; q < Q; q++) pp[q] = h.at((uint64_t)q * n); linear_combination(hcomb.p, pp, powers(fr_pow(x, n), Q), n, false); R.gate_launches++; }
     const Fr ys = T.squeeze_challenge(), v = T.squeeze_challenge();
     const std::vector<RotationSet> sets = rotation_sets(P.queries); const size_t M = sets.size(); R.rotation_sets = (uint32_t)M;
-    std::vector<DevicePoly> Acomb; std::vector<std::vector<Fr>> points(M); std::vector<std::vector<std::vector<Fr>>> rcoef(M);
+    std::vector<std::vector<Fr>> points(M);
+    for (size_t i = 0; i < M; i++) for (int32_t r : sets[i].rots) points[i].push_back(rot_point(r));
+    std::vector<std::vector<Fr>> rem; std::vector<DevicePoly> Acomb;
     DevicePoly H(n, 0), work(n, 0); check(mi355_buf_zero(H.p, n * 32));
     Fr vpow_i = fr_one();
     for (size_t i = 0; i < M; i++) {
       const RotationSet &s = sets[i]; const size_t np = s.polys.size(), m = s.rots.size();
-      for (int32_t r : s.rots) points[i].push_back(rot_point(r));
       // A_i = sum_j y^j P_ij (the j-th polynomial of a set carries y^j: what the reference's released proofs satisfy, tests/test_plonk_protocol.py::test_reference_released_proofs_verify),
-      // and the same combination of the interpolated remainders (m coefficients, on the host)
-      std::vector<Fr> ypow(np, fr_one()); for (size_t j = 1; j < np; j++) ypow[j] = fr_mul(ypow[j - 1], ys);
+      // and the same combination of the interpolated remainders (m coefficients, on the host, while the device works on A_i)
+      const std::vector<Fr> ypow = powers(ys, np);
       DevicePoly Ai(n, 0);
       for (size_t base = 0; base < np; base += 16) {
-        const uint32_t cnt = (uint32_t)std::min<size_t>(16, np - base);
-        std::vector<const void *> pp(cnt); std::vector<Fr> cs(cnt); std::vector<uint32_t> tl_(cnt, 1), fp(cnt); std::vector<int32_t> fr_(cnt, 0);
-        for (uint32_t j = 0; j < cnt; j++) { pp[j] = opened(s.polys[base + j]); cs[j] = ypow[base + j]; fp[j] = j; }
-        gate_eval(Ai.p, pp.data(), cnt, cs.data(), tl_.data(), cnt, fp.data(), fr_.data(), n, base ? 1 : 0); R.gate_launches++;
+        const size_t cnt = std::min<size_t>(16, np - base);
+        std::vector<const void *> pp(cnt); for (size_t j = 0; j < cnt; j++) pp[j] = s.polys[base + j] == P.quotient_poly ? hcomb.p : coeff_ptr(s.polys[base + j]);
+        linear_combination(Ai.p, pp, std::vector<Fr>(ypow.begin() + (long)base, ypow.begin() + (long)(base + cnt)), n, base != 0); R.gate_launches++;
       }
-      std::vector<Fr> rsum(m, fr_zero());
-      for (size_t j = 0; j < np; j++) {
-        std::vector<Fr> vals; for (int32_t r : s.rots) vals.push_back(evals.at({s.polys[j], r}));
-        rcoef[i].push_back(detail::interpolate(points[i], vals));
-        for (size_t t = 0; t < m; t++) rsum[t] = fr_add(rsum[t], fr_mul(ypow[j], rcoef[i][j][t]));
-      }
+      rem.push_back(shplonk_remainder(s, points[i], evals, ys));
       // N_i = A_i - R_i: only the lowest m coefficients change; then N_i / prod (X - point), one kate_division per point, in place (shifting up by one each time)
       check(mi355_buf_copy(work.p, Ai.p, n * 32));
-      { std::vector<Fr> low(m); check(mi355_buf_download(low.data(), work.p, m * 32)); for (size_t t = 0; t < m; t++) low[t] = fr_sub(low[t], rsum[t]); check(mi355_buf_upload(work.p, low.data(), m * 32)); }
+      { std::vector<Fr> low(m); check(mi355_buf_download(low.data(), work.p, m * 32)); for (size_t t = 0; t < m; t++) low[t] = fr_sub(low[t], rem[i][t]); check(mi355_buf_upload(work.p, low.data(), m * 32)); }
       for (size_t t = 0; t < m; t++) check(mi355_fr_kate_division_dev(work.at(t + 1), work.at(t), n - t, points[i][t].data()));
       // H += v^i Q_i (the i-th rotation set carries v^i); Q_i has n - m coefficients at work[m ..]
       check(mi355_fr_vec_axpy_dev(H.p, H.p, work.at(m), vpow_i.data(), n - m));
       vpow_i = fr_mul(vpow_i, v);
       Acomb.push_back(std::move(Ai));
     }
-    commit_one(h_g, H.p);
+    C.commit_one(h_g, H.p);
     const Fr uu = T.squeeze_challenge();
-    std::vector<Fr> super; for (size_t i = 0; i < M; i++) for (const auto &pt : points[i]) if (std::find(super.begin(), super.end(), pt) == super.end()) super.push_back(pt);
-    Fr zt = fr_one(); for (const auto &pt : super) zt = fr_mul(zt, fr_sub(uu, pt));
-    // L = sum_i v^i zd_i (A_i - r_i(u)) - Z_T(u) H, scaled by 1 / zd_0;  L(u) = 0
-    std::vector<Fr> vpow(M, fr_one()); for (size_t i = 1; i < M; i++) vpow[i] = fr_mul(vpow[i - 1], v);
-    std::vector<Fr> lc(M); Fr zd0 = fr_one(), cst = fr_zero();
-    for (size_t i = 0; i < M; i++) {
-      Fr zd = fr_one(); for (const auto &pt : super) if (std::find(points[i].begin(), points[i].end(), pt) == points[i].end()) zd = fr_mul(zd, fr_sub(uu, pt));
-      if (i == 0) zd0 = zd;
-      const size_t np = sets[i].polys.size(); Fr ri = fr_zero();
-      Fr yp = fr_one(); for (size_t j = 0; j < np; j++) { ri = fr_add(ri, fr_mul(yp, detail::horner(rcoef[i][j], uu))); yp = fr_mul(yp, ys); }
-      lc[i] = fr_mul(vpow[i], zd); cst = fr_add(cst, fr_mul(lc[i], ri));
-    }
-    const Fr zi = fr_inv(zd0);
+    const ShplonkLinearisation lin = shplonk_linearisation(points, rem, v, uu);
     DevicePoly Lx(n, 0);
     {
       if (M + 1 > PLAN_MAX_TERMS) throw std::invalid_argument("SHPLONK: more than 15 rotation sets");
-      std::vector<const void *> pp; std::vector<Fr> cs; for (size_t i = 0; i < M; i++) { pp.push_back(Acomb[i].p); cs.push_back(fr_mul(lc[i], zi)); }
-      pp.push_back(H.p); cs.push_back(fr_neg(fr_mul(zt, zi)));
-      std::vector<uint32_t> tl_(M + 1, 1), fp(M + 1); std::vector<int32_t> fr_(M + 1, 0); for (size_t i = 0; i <= M; i++) fp[i] = (uint32_t)i;
-      gate_eval(Lx.p, pp.data(), (uint32_t)(M + 1), cs.data(), tl_.data(), (uint32_t)(M + 1), fp.data(), fr_.data(), n, 0); R.gate_launches++;
-      Fr l0; check(mi355_buf_download(l0.data(), Lx.p, 32)); l0 = fr_sub(l0, fr_mul(cst, zi)); check(mi355_buf_upload(Lx.p, l0.data(), 32));
+      std::vector<const void *> pp; for (size_t i = 0; i < M; i++) pp.push_back(Acomb[i].p);
+      pp.push_back(H.p); std::vector<Fr> cs = lin.a; cs.push_back(lin.h);
+      linear_combination(Lx.p, pp, cs, n, false); R.gate_launches++;
+      Fr l0; check(mi355_buf_download(l0.data(), Lx.p, 32)); l0 = fr_sub(l0, lin.constant); check(mi355_buf_upload(Lx.p, l0.data(), 32));
     }
     check(mi355_buf_zero(work.p, n * 32));
     check(mi355_fr_kate_division_dev(work.p, Lx.p, n, uu.data()));                       // n - 1 coefficients, the top one stays zero
-    commit_one(h_g, work.p);
+    C.commit_one(h_g, work.p);
   }
-  check(mi355_synchronize());
-  lap(10);
-  R.total_ms = ms_since(t_start);
-  R.proof = std::move(T.proof); R.sparse_columns = sparse_cols.load(); R.packed_columns = packed_cols.load(); R.witness_link_bytes = link_bytes.load();
-  { uint64_t fr_ = 0, tot = 0; check(mi355_mem_info(0, &fr_, &tot, nullptr, nullptr, nullptr)); R.peak_hbm_bytes = tot - fr_; R.hbm_total_bytes = tot; }
-  return R;
+  ProofResult result() {
+    R.total_ms = ms_since(t_start);
+    R.proof = std::move(T.proof); R.sparse_columns = sparse_cols.load(); R.packed_columns = packed_cols.load(); R.witness_link_bytes = link_bytes.load();
+    { uint64_t fr_ = 0, tot = 0; check(mi355_mem_info(0, &fr_, &tot, nullptr, nullptr, nullptr)); R.peak_hbm_bytes = tot - fr_; R.hbm_total_bytes = tot; }
+    return std::move(R);
+  }
+};
+}  // namespace detail
+
+inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const ProvingKey &pk, const Circuit &wit, const ProofOptions &opt) {
+  const Protocol &P = *pk.P;
+  // resident coset parts were placed by keygen at q % pk.devices: the gate kernel on device d must find part q on d, so the proof runs on the key's device count
+  // (ADVICE r5: a differing opt.devices would read a coset that sits on another device)
+  if (pk.resident_cosets && pk.devices != std::max(1, opt.devices)) throw std::invalid_argument("create_proof: ProofOptions::devices (" + std::to_string(opt.devices) + ") differs from the proving key's (" + std::to_string(pk.devices) + ") while its coset parts are resident");
+  if (opt.check_witness) { CheckOptions co; co.threads = opt.threads; std::vector<VerifyFailure> bad = check_witness(pk, wit, co); if (!bad.empty()) throw WitnessError(std::move(bad)); }
+  detail::ProofRun run(h_g, h_g_lagrange, pk, wit, opt);                                // the clock starts; the transcript takes the key's scalar and the instance values
+  if (run.dev_rng) for (uint32_t i = 0; i < run.A; i++) if (wit.advice.at(i).size() < P.usable + 1) throw std::invalid_argument("create_proof: advice column " + std::to_string(i) + " has fewer than the usable rows + 1");
+  if (run.dev_m && !run.dev_rng && wit.m_blind.size() != run.NL) throw std::invalid_argument("create_proof: device_multiplicities needs the blinding values of every multiplicity column (Circuit::m_blind)");
+  run.witness_commits(); run.lap(2);            // steps 1-3; step 3 on the device: device_multiplicities()
+  run.instance_to_coefficients(); run.lap(1);
+  run.products_and_sums(); run.lap(4);
+  run.random_polynomial(); run.lap(5);
+  run.to_coefficients(); run.lap(6);
+  run.quotient(); run.lap(7);
+  run.commit_quotient(); run.lap(8);
+  run.evaluations(); run.lap(9);
+  run.shplonk(); check(mi355_synchronize()); run.lap(10);
+  return run.result();
 }
 
 }  // namespace plonk

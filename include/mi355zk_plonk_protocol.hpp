@@ -276,6 +276,9 @@ struct Protocol {
   }
 };
 
+// omega^r for a rotation r of either sign: a polynomial queried at rotation r is opened at x omega^r (the prover's evaluation points, the verifier's Lagrange and query points)
+inline Fr rot_power(const Fr &omega, const Fr &omega_inv, int32_t r) { return r >= 0 ? fr_pow(omega, (uint64_t)r) : fr_pow(omega_inv, (uint64_t)(-(int64_t)r)); }
+
 // SHPLONK's rotation sets [EXT-recalled halo2_proofs poly/kzg/multiopen/shplonk.rs construct_intermediate_sets]: polynomials opened at the same SET of rotations
 // share one set.  Order: first appearance in `queries`, for the sets and inside a set (snark-verifier's query_sets; the order under which all of the reference's stored proofs verify).
 struct RotationSet { std::vector<int32_t> rots; std::vector<uint32_t> polys; };

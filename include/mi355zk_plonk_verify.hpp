@@ -74,7 +74,6 @@ inline Fr eval_expr(const Expr &e, const std::map<PolyRot, Fr> &evals, const Fr 
   }
   throw std::invalid_argument("verify: unknown expression node");
 }
-inline Fr pow_rot(const Protocol &P, int32_t r) { return r >= 0 ? fr_pow(P.omega, (uint64_t)r) : fr_pow(P.omega_inv, (uint64_t)(-(int64_t)r)); }
 
 // ---- the HOST PART of one verification, in three steps that plonk::verify_proof runs for one proof and plonk::verify_proofs / plonk::aggregate for many:
 //   layout_of     what the proof's length and the key decide before any point is looked at: the transcript, the word counts, every compressed point word
@@ -192,7 +191,7 @@ inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::v
   std::map<int32_t, Fr> lag;
   auto lagrange_at = [&](int32_t i) {   // omega^i (x^n - 1) / (n (x - omega^i))
     auto it = lag.find(i); if (it != lag.end()) return it->second;
-    const Fr wi = vdetail::pow_rot(P, i);
+    const Fr wi = rot_power(P.omega, P.omega_inv, i);
     const Fr val = fr_mul(fr_mul(fr_mul(wi, xn_minus_1), P.n_inv), fr_inv(fr_sub(x, wi)));
     lag[i] = val; return val;
   };
@@ -205,7 +204,7 @@ inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::v
   evals[{P.quotient_poly, 0}] = fr_mul(numer, fr_inv(xn_minus_1));
 
   // ---- SHPLONK: the (scalars, points) list
-  auto rot_pt = [&](int32_t r) { return fr_mul(x, vdetail::pow_rot(P, r)); };
+  auto rot_pt = [&](int32_t r) { return fr_mul(x, rot_power(P.omega, P.omega_inv, r)); };
   const std::vector<RotationSet> sets = rotation_sets(P.queries);
   std::vector<Fr> super_pts;
   for (const auto &s : sets) for (int32_t r : s.rots) { const Fr pt = rot_pt(r); if (std::find(super_pts.begin(), super_pts.end(), pt) == super_pts.end()) super_pts.push_back(pt); }
