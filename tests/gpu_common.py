@@ -18,11 +18,59 @@ def rand_fr(rng, n, full=True):
 
 
 def rand_points(rng, n):
-    """n random curve points [n,8] through the oracle (slow: use for n <= ~4096)."""
+    """n random curve points [n,8] through the oracle (slow, ~0.4 ms each: use for n <= ~4096; device_points below makes any number)."""
     G = cref.g1_generator()
     sc = rand_fr(rng, n, full=False)
     jac = np.stack([cref.g1_mul(G, sc[i]) for i in range(n)])
     return cref.g1_to_affine(jac)
+
+
+def device_points(zk, n, seed, sample=64):
+    """n independent curve points k_i G made by the library's fixed-base kernel (any n: 2^21 points take well under a second), verified through the
+    oracle before anything relies on them: EVERY point satisfies y^2 = x^3 + 3 (cref.f_mul_vec over Fq), and `sample` of them -- indices 0, 16383,
+    16384 and n - 1 among them -- equal the oracle's own k_i G.  -> (points [n,8], the scalars k_i [n,4])"""
+    import torch
+    lib, check, ptr = zk._capi.lib(), zk._capi.check, zk._capi.ptr
+    rng = np.random.default_rng(seed)
+    ks = rand_fr(rng, n, full=False)
+    ks_dev = torch.from_numpy(ks.view(np.int64)).cuda()
+    pts_dev = torch.empty((n, 8), dtype=torch.int64, device="cuda")
+    check(lib.mi355_g1_fixed_base_mul_dev(ptr(pts_dev), ptr(ks_dev), n))
+    check(lib.mi355_synchronize())
+    pts = pts_dev.cpu().numpy().view(np.uint64).reshape(n, 8)
+    x, y = np.ascontiguousarray(pts[:, :4]), np.ascontiguousarray(pts[:, 4:])
+    three = np.tile(np.array(pyref.to_limbs(3 * pyref.MONT_R % pyref.P_MOD), dtype=np.uint64), (n, 1))
+    rhs = cref.f_add_vec(cref.FQ, cref.f_mul_vec(cref.FQ, cref.f_mul_vec(cref.FQ, x, x), x), three)
+    assert (cref.f_mul_vec(cref.FQ, y, y) == rhs).all(), "a device-made point is not on the curve"
+    idx = np.unique(np.concatenate([[i for i in (0, 16383, 16384, n - 1) if 0 <= i < n], rng.integers(0, n, size=sample)]))
+    assert (pts[idx] == cref.g1_mul_generator_vec(ks[idx])).all(), "a device-made point is not the oracle's multiple of the generator"
+    return pts, ks
+
+
+def witness_like_fr(rng, n):
+    """n scalars as in a witness column: 45 % zero, 45 % one, the rest below 2^16 (canonical values), as Montgomery limbs [n,4]"""
+    v = rng.integers(0, 1 << 16, size=n, dtype=np.uint64)
+    r = rng.random(n)
+    v[r < 0.45] = 0
+    v[(r >= 0.45) & (r < 0.9)] = 1
+    can = np.zeros((n, 4), dtype=np.uint64); can[:, 0] = v
+    return cref.f_from_canonical_vec(cref.FR, can)
+
+
+def class_sums(sc, period):
+    """S_j = sum of sc[i] over i = j mod period, modulo r, as canonical integers (any length: the tail is zero-padded for the fold): the scalars an
+    MSM over `period` bases tiled to len(sc) multiplies each distinct base by.  Vectorised over 16-bit chunks."""
+    sc = np.asarray(sc, dtype=np.uint64).reshape(-1, 4)
+    can = cref.f_to_canonical_vec(cref.FR, sc)
+    pad = (-can.shape[0]) % period
+    can = np.concatenate([can, np.zeros((pad, 4), dtype=np.uint64)]).reshape(-1, period, 4)
+    tot = [0] * period
+    for limb in range(4):
+        for k in range(4):
+            part = ((can[:, :, limb] >> np.uint64(16 * k)) & np.uint64(0xffff)).sum(axis=0, dtype=np.uint64)
+            for j in range(period):
+                tot[j] += int(part[j]) << (64 * limb + 16 * k)
+    return [t % R for t in tot]
 
 
 def affine_of(g1):
