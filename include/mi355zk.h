@@ -112,6 +112,21 @@ int mi355_host_free(void *host_ptr);
  * [REF bin/src/trace_prover.rs:35-36] AND the proving key's extended-coset polynomials resident: the caller budgets window tables
  * (mi355_srs_precompute: W x the basis) against this figure and stays on the table-free schedule when they do not fit.     */
 int mi355_mem_info(int device_slot, uint64_t *free_bytes, uint64_t *total_bytes, uint64_t *live_buf_bytes, uint64_t *pooled_bytes, uint64_t *workspace_bytes);
+/* A limit on the device memory this library holds on one device slot, for a prover that shares its device: a chunk prover process keeps the SRS of three degrees, three
+ * proving keys and one proof's working set in one process [REF integration/src/prove.rs:30-43], [REF bin/src/trace_prover.rs:35-43], 274-278 GiB of 288 (DESIGN.md sections 9
+ * and 13), and a shared device cannot promise all 288.  Every allocation the library makes from HIP is booked in one ledger (csrc/mem_budget.hpp), by class.  With a limit set
+ * (bytes > 0; 0 lifts it), an allocation that would take the held bytes past it is decided ON THE HOST, before any HIP call: first the slot's pooled blocks and free slabs go
+ * back to HIP (what mi355_buf_trim does), then the optional NTT tables (folded coset shifts, divisor-scaled and 2-D inter-level tables: their passes have table-free forms
+ * with the same bits and the tables are rebuilt when there is room again), and if that made no room the call returns MI355_EOOM; mi355_last_error names the limit, the held
+ * bytes by class and the request.  The same order runs on a real out-of-memory error with no limit set.  Window tables (mi355_srs_precompute) belong to the caller's handle:
+ * counted, never reclaimed.  A limit below what is already held refuses new allocations and frees nothing.  No device lock is taken; the slot need not be bound yet.      */
+int mi355_mem_set_limit(int device_slot, uint64_t bytes);
+/* What the ledger holds for one device slot (any pointer may be NULL): held = the sum of the classes; the limit (0: none); the high-water mark of held since
+ * mi355_mem_reset_peak (the measure plonk::plan_residency's figures [DESIGN.md section 9] are checked against); class_bytes[0 .. n_classes): 0 slabs and direct mi355_buf
+ * blocks (live, pooled or free ranges), 1 the workspace arena, 2 required NTT tables, 3 optional NTT tables, 4 SRS shards and mi355_srs_downsize results, 5 window tables,
+ * 6 the fixed-base and Poseidon tables (entries past 6 read 0); reclaims = how often a reclaim gave something back; refused_bytes = the sum of the refused requests.  */
+int mi355_mem_usage(int device_slot, uint64_t *held_bytes, uint64_t *limit_bytes, uint64_t *high_water_bytes, uint64_t *class_bytes, uint32_t n_classes, uint64_t *reclaims, uint64_t *refused_bytes);
+int mi355_mem_reset_peak(int device_slot);                                      /* high-water := held; one proof's peak is read between two of these            */
 
 /* ---- SRS ownership: ParamsKZG { g, g_lagrange } [halo2_proofs poly/kzg/commitment.rs], held for the process
  *      lifetime by the caller's params_map [REF bin/src/trace_prover.rs:35-43], [REF integration/src/prove.rs:12,26,58].

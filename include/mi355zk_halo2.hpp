@@ -43,6 +43,13 @@ struct Error : std::runtime_error {
 };
 inline void check(int rc) { if (rc != MI355_OK) throw Error(rc, mi355_last_error()); }
 inline void init(int device_id = 0) { check(mi355_init(device_id)); }
+// The memory limit of one device slot (mi355_mem_set_limit: 0 lifts it) and what the library's ledger holds there (mi355_mem_usage; classes as the header numbers them)
+struct MemUsage { uint64_t held = 0, limit = 0, high_water = 0, reclaims = 0, refused = 0; uint64_t by_class[7] = {0};
+                  uint64_t buffers() const { return by_class[0]; } uint64_t workspace() const { return by_class[1]; } uint64_t ntt_required() const { return by_class[2]; } uint64_t ntt_optional() const { return by_class[3]; }
+                  uint64_t srs() const { return by_class[4]; } uint64_t window_tables() const { return by_class[5]; } uint64_t fixed_tables() const { return by_class[6]; } };
+inline void mem_set_limit(int slot, uint64_t bytes) { check(mi355_mem_set_limit(slot, bytes)); }
+inline MemUsage mem_usage(int slot = 0) { MemUsage u; check(mi355_mem_usage(slot, &u.held, &u.limit, &u.high_water, u.by_class, 7, &u.reclaims, &u.refused)); return u; }
+inline void mem_reset_peak(int slot = 0) { check(mi355_mem_reset_peak(slot)); }
 
 // ---- helpers on Fr (host, for constants only)
 namespace detail {

@@ -253,21 +253,24 @@ inline std::set<uint32_t> lagrange_needed(const Protocol &P) {
   return s;
 }
 // HBM a layer's prover needs, from the protocol alone: a dry compile gives the plan's temporaries and the common polynomials
+// coset_group: ProofOptions::coset_group_polys of the proofs to come (0: step 7 holds one coset part of every witness polynomial, and a lean key one of every key polynomial;
+// G: of the G operands of one group of launches)
 struct PkSizes { uint32_t polys, lagrange, commons, plan_tmps; double base_bytes, coset_bytes, lean_tmp_bytes, working_bytes; };
-inline PkSizes pk_sizes(const Protocol &P) {
+inline PkSizes pk_sizes(const Protocol &P, uint32_t coset_group = 0) {
   const double per = (double)P.n * 32; PkSizes s;
   CommonRegistry reg; { Expr id; id.kind = Expr::IDENTITY; reg.id_of(id, true); }
   Compiler cmp(reg, true, std::vector<Fr>(4, fr_one())); cmp.compile_numerator(P.numerator);
   s.commons = (uint32_t)reg.defs.size(); s.plan_tmps = cmp.tmps_used();
   s.polys = P.num_pre + s.commons; s.lagrange = (uint32_t)lagrange_needed(P).size() + 1;
-  s.base_bytes = per * (s.polys + s.lagrange); s.coset_bytes = per * s.polys * P.Q; s.lean_tmp_bytes = per * s.polys;
+  s.base_bytes = per * (s.polys + s.lagrange); s.coset_bytes = per * s.polys * P.Q; s.lean_tmp_bytes = coset_group ? 0.0 : per * s.polys;   // grouped: the key's operands share the G part buffers of step 7
   uint32_t NW = 1; for (auto w : P.num_witness) NW += w;                     // instance + witness polynomials
   uint32_t max_chunk = 0; for (const auto &c : P.perm) max_chunk = std::max<uint32_t>(max_chunk, (uint32_t)c.columns.size());
   // the peak is step 7: every polynomial's coefficients + one coset part of each (the random polynomial has none), the plan's temporaries, h as Q parts and as one
   // vector; step 4 (Lagrange values + 2 + 2 chunk temporaries) and step 10 (one combination per rotation set + H, L, work, the combined quotient) stay below it when
   // the early coefficient copies of a many-column layer are counted (one more copy of every advice column).  Plus the scratch of the 2^(k + e) inverse transform,
   // the MSM workspace (~22 B per entry, up to 13 windows) and fixed overheads.
-  const double step7 = per * (2.0 * NW - 1 + s.plan_tmps + 2.0 * P.Q), step4 = per * (NW + (P.num_advice() >= 8 ? P.num_advice() : 0) + 3.0 + 2.0 * max_chunk), step10 = per * (NW + P.Q + 10.0);
+  const double parts7 = coset_group ? (double)std::min<uint32_t>(coset_group, NW - 1 + s.polys) : (double)(NW - 1);
+  const double step7 = per * (NW + parts7 + s.plan_tmps + 2.0 * P.Q), step4 = per * (NW + (P.num_advice() >= 8 ? P.num_advice() : 0) + 3.0 + 2.0 * max_chunk), step10 = per * (NW + P.Q + 10.0);
   s.working_bytes = std::max(step7, std::max(step4, step10)) + per * P.Q + (double)P.n * 13 * 22 + 0.5 * 1024.0 * 1024 * 1024;
   return s;
 }
@@ -286,11 +289,11 @@ inline double coset_transform_ms(uint32_t k) {
 }
 struct LayerResidency { const Protocol *P; PkSizes sz; bool cosets_resident = false, table_lagrange = false, table_coeff = false; };
 struct ResidencyPlan { std::vector<LayerResidency> layers; double srs_gib = 0, keys_gib = 0, tables_gib = 0, working_gib = 0, total_gib = 0, budget_gib = 0; bool fits = false; };
-inline ResidencyPlan plan_residency(const std::vector<const Protocol *> &protos, double hbm_gib, double reserve_fraction = 0.08) {
+inline ResidencyPlan plan_residency(const std::vector<const Protocol *> &protos, double hbm_gib, double reserve_fraction = 0.08, uint32_t coset_group = 0) {
   const double GiB = 1024.0 * 1024 * 1024;
   ResidencyPlan R; R.budget_gib = hbm_gib * (1.0 - reserve_fraction);
   std::set<uint32_t> degrees;
-  for (const Protocol *p : protos) { LayerResidency L{p, pk_sizes(*p)}; R.working_gib = std::max(R.working_gib, L.sz.working_bytes / GiB); degrees.insert(p->k); R.keys_gib += L.sz.base_bytes / GiB; R.layers.push_back(L); }
+  for (const Protocol *p : protos) { LayerResidency L{p, pk_sizes(*p, coset_group)}; R.working_gib = std::max(R.working_gib, L.sz.working_bytes / GiB); degrees.insert(p->k); R.keys_gib += L.sz.base_bytes / GiB; R.layers.push_back(L); }
   for (uint32_t k : degrees) R.srs_gib += 2.0 * (double)(uint64_t(64) << k) / GiB;                       // two bases of 64-byte points
   // Which keys keep their coset parts (round 6): the subset that SAVES THE MOST PROOF TIME and fits -- a resident key saves one coset transform per polynomial, part and proof
   // (coset_transform_ms: measured, section 5).  Round 5 took "smaller keys first"; by value a chunk prover would rather keep layer 1's 80 GiB (160 transforms of 2^24 = 0.33 s)
@@ -615,6 +618,9 @@ struct ProofOptions { int devices = 1; int threads = 8; uint32_t commit_batch = 
                                                         polynomial is not uploaded and Circuit::random_poly, m_blind, z_blind, phi_blind and the blinding rows of Circuit::advice / m are not read */;
                       uint8_t rng_key[32] = {0} /* the ChaCha20 key of this proof's draws.  One key per proof: a (key, stream, counter) triple must never serve two proofs */;
                       bool rng_key_from_os = false /* with device_randomness: the key is filled from getrandom(2) inside create_proof (rng_key is not read); a failure throws */;
+                      uint32_t coset_group_polys = 0 /* 0: step 7 transforms one coset part of EVERY polynomial the plan reads before it runs the part's launches.  G >= PLAN_MAX_POLYS: the
+                                                        launches run in consecutive groups whose operands number at most G (detail::coset_groups), each group behind ONE batched transform of its
+                                                        operands into a pool of G part buffers; an operand a later group needs again is transformed again (ProofResult::coset_retransforms).  Same proof bytes */;
                       TranscriptKind transcript = TranscriptKind::ByLayer /* the reference's choice for the protocol's layer (reference_transcript below): Poseidon for 0-5, Evm for 6; or name one */; };
 // the transcript the reference proves a layer with: Poseidon for every proof the next layer verifies in-circuit (layers 0-5, [REF integration/src/prove.rs:30-43,67,95-97] -> snark-verifier-sdk
 // gen_snark_shplonk), Keccak in the EVM layout for layer 6 (gen_evm_proof_shplonk: what the released verifier contract reads).  Files without a layer number are the reference's fixtures (layers 2, 4).
@@ -641,6 +647,7 @@ struct ProofResult {
   uint64_t sparse_columns = 0, packed_columns = 0, witness_link_bytes = 0;
   double random_ms = 0;         // device_randomness: the random polynomial's block, its draw and the wait for it (an upper bound of the draw's device time), plus the host time of the blinding-row launches
   double multiplicity_ms = 0;   // device_multiplicities: compression, counting and blinding rows of every lookup (host wall time, the commitments excluded)
+  uint32_t coset_groups = 0 /* groups of launches per coset part (0: the ungrouped route) */, coset_retransforms = 0 /* coset transforms beyond one per operand and part; counted in coset_ntt too */;
   uint32_t msm = 0, intt = 0, coset_ntt = 0, gate_launches = 0, evals = 0, plan_launches = 0, plan_terms = 0, plan_tmps = 0, plan_constraints = 0, plan_prefix_groups = 0, rotation_sets = 0;
 };
 
@@ -725,6 +732,44 @@ struct Committer {
     }
   }
 };
+
+// ProofOptions::coset_group_polys: the compiled quotient plan cut into consecutive runs of launches.  Walking the plan in order, a run is closed as soon as the next launch would
+// take the union of the run's non-temporary operands past G -- witness polynomials and, with a lean key (`lean`: the key's coset parts are not resident), the key's and the common
+// polynomials.  Temporaries live across groups and do not count.  One launch names at most PLAN_MAX_POLYS operands, so any G >= PLAN_MAX_POLYS cuts any plan; a smaller G is
+// refused.  Greedy and order-preserving on purpose: the plan's order is what makes temporaries valid, and the arithmetic is exact, so any cut gives the same quotient.
+constexpr uint32_t COSET_GROUP_ALL = 0xffffffffu;
+struct CosetGroup { size_t first, last; std::vector<uint32_t> witness; std::vector<Atom> key; };   // launches [first, last) of the plan; the operands to transform, ascending
+struct CosetGrouping { std::vector<CosetGroup> groups; uint32_t distinct = 0 /* operands of the whole plan */, retransforms = 0 /* members of all groups beyond `distinct`, per coset part */, max_witness = 0, max_key = 0; };
+inline CosetGrouping coset_groups(const Protocol &P, const std::vector<Launch> &plan, uint32_t G, bool lean) {
+  if (G < PLAN_MAX_POLYS) throw std::invalid_argument("coset_group_polys must be 0 or at least " + std::to_string(PLAN_MAX_POLYS) + " (one launch may name that many operands)");
+  CosetGrouping R; std::set<Atom> all, cur; size_t first = 0;
+  auto close = [&](size_t last) {
+    CosetGroup g{first, last, {}, {}};
+    for (const auto &a : cur) { if (a.kind == A_POLY && !P.is_pre(a.idx)) g.witness.push_back(a.idx); else g.key.push_back(a); }
+    R.max_witness = std::max<uint32_t>(R.max_witness, (uint32_t)g.witness.size()); R.max_key = std::max<uint32_t>(R.max_key, (uint32_t)g.key.size());
+    R.retransforms += (uint32_t)cur.size(); R.groups.push_back(std::move(g)); cur.clear(); first = last;
+  };
+  for (size_t l = 0; l < plan.size(); l++) {
+    std::set<Atom> next = cur;
+    for (const auto &t : plan[l].terms) for (const auto &f : t.f) {
+      if (f.kind == A_TMP) continue;
+      const bool key = f.kind == A_COMMON || P.is_pre(f.idx);
+      if (!key || lean) { next.insert(Atom{f.kind, f.idx, 0}); all.insert(Atom{f.kind, f.idx, 0}); }
+    }
+    if (next.size() > G && l > first) { close(l); l--; continue; }   // the launch opens the next group
+    cur.swap(next);
+  }
+  if (first < plan.size() || R.groups.empty()) close(plan.size());
+  R.distinct = (uint32_t)all.size(); R.retransforms -= R.distinct;
+  return R;
+}
+// the largest G whose part buffers fit `bytes_for_parts` (what the caller can spare for step 7's coset parts): 0 = no grouping needed, everything fits; never below PLAN_MAX_POLYS
+inline uint32_t suggest_coset_group(const Protocol &P, bool lean, double bytes_for_parts) {
+  const PkSizes sz = pk_sizes(P); uint32_t NW = 1; for (auto w : P.num_witness) NW += w;
+  const double per = (double)P.n * 32; const uint32_t all = NW - 1 + (lean ? sz.polys : 0);
+  if (bytes_for_parts >= per * all) return 0;
+  return std::max<uint32_t>(PLAN_MAX_POLYS, (uint32_t)std::max(0.0, bytes_for_parts / per));
+}
 
 // The state of one proof; the steps are SURVEY 3.2's, numbered as the replay record's step_ms and rust_shim/create_proof_resident.rs number them.
 struct ProofRun {
@@ -946,7 +991,8 @@ struct ProofRun {
     for (auto &kv : coeff_early) poly.at(kv.first) = std::move(kv.second);
     coeff_early.clear();
   }
-  // ---- step 7: the quotient, coset part by coset part; part q on device q % D (the proving key's cosets of that part live there).  Everything but h goes before step 8
+  // ---- step 7: the quotient, coset part by coset part; part q on device q % D (the proving key's cosets of that part live there).  Everything but h goes before step 8.
+  // ProofOptions::coset_group_polys = G runs a part's launches in the groups of detail::coset_groups: G part buffers instead of one per polynomial the plan reads
   void quotient() {
     h = DevicePoly(Q * n, 0);
     Compiler cmp(const_cast<CommonRegistry &>(pk.commons), false, ch);
@@ -958,16 +1004,54 @@ struct ProofRun {
     std::vector<std::map<uint32_t, DevicePoly>> part_on(D), coeff_on(D); std::vector<std::map<Atom, DevicePoly>> pkpart_on(D);
     std::vector<std::vector<DevicePoly>> tmp_on(D); std::vector<DevicePoly> hq_on(D);
     std::vector<DevicePoly> hpart; for (uint32_t q = 0; q < Q; q++) hpart.emplace_back(n, 0);
+    // coset_group_polys: the part buffers are a pool per device, as many as the largest group needs (at most G in all); no per-polynomial part, no coefficient copies on the other devices
+    const bool grouped = opt.coset_group_polys != 0;
+    CosetGrouping CG; std::vector<std::vector<DevicePoly>> wpool(D), kpool(D);
+    if (grouped) { CG = coset_groups(P, cmp.out, opt.coset_group_polys, !pk.resident_cosets); R.coset_groups = (uint32_t)CG.groups.size(); R.coset_retransforms = CG.retransforms * Q; }
     for (int d = 0; d < D; d++) {
-      for (uint32_t r : wrefs) part_on[d][r] = DevicePoly(n, d);
+      if (!grouped) for (uint32_t r : wrefs) part_on[d][r] = DevicePoly(n, d);
+      else { for (uint32_t i = 0; i < CG.max_witness; i++) wpool[d].emplace_back(n, d); for (uint32_t i = 0; i < CG.max_key; i++) kpool[d].emplace_back(n, d); }
       tmp_on[d].resize(cmp.tmp_max);
       for (const auto &L : cmp.out) if (L.dst >= 0 && !tmp_on[d][(size_t)L.dst].p) tmp_on[d][(size_t)L.dst] = DevicePoly(n, d);   // only the ids the plan writes
-      if (d > 0) { hq_on[d] = DevicePoly(n, d); for (uint32_t r : wrefs) { coeff_on[d][r] = DevicePoly(n, d); check(mi355_buf_copy(coeff_on[d][r].p, poly.at(r).p, n * 32)); } }
+      if (d > 0) { hq_on[d] = DevicePoly(n, d); if (!grouped) for (uint32_t r : wrefs) { coeff_on[d][r] = DevicePoly(n, d); check(mi355_buf_copy(coeff_on[d][r].p, poly.at(r).p, n * 32)); } }
     }
-    std::vector<std::string> errs(D); std::vector<uint32_t> launches(D, 0), cosets(D, 0);
+    std::vector<std::string> errs(D); std::vector<int> codes(D, MI355_EHIP); std::vector<uint32_t> launches(D, 0), cosets(D, 0);
+    // one coset part by groups: per group ONE batched transform of its operands (witness and, lean, key) into the pool, then its launches; the temporaries and the part's
+    // accumulator carry over from group to group.  Everything of a device runs on its compute stream, which orders the reuse of a pool buffer behind the launches that read it
+    auto grouped_part = [&](int d, uint32_t q) {
+      const Fr factor = part_factor(dom, q);
+      const Fr tq_inv = fr_inv(fr_sub(fr_pow(factor, n), fr_one()));
+      void *hq = d == 0 ? hpart[q].p : hq_on[d].p;
+      bool first = true;
+      for (const CosetGroup &grp : CG.groups) {
+        std::map<uint32_t, const void *> wat; std::map<Atom, const void *> kat;
+        std::vector<void *> dst; std::vector<const void *> src;
+        auto stage = [&](void *buf, const void *coeff) {   // another device: the coefficients are copied into the part buffer first, then transformed in place
+          if (d != 0) { check(mi355_buf_copy(buf, coeff, n * 32)); coeff = buf; }
+          dst.push_back(buf); src.push_back(coeff);
+        };
+        for (size_t i = 0; i < grp.witness.size(); i++) { void *b = wpool[d].at(i).p; stage(b, poly.at(grp.witness[i]).p); wat[grp.witness[i]] = b; }
+        for (size_t i = 0; i < grp.key.size(); i++) { void *b = kpool[d].at(i).p; stage(b, pk.coeff(grp.key[i]).p); kat[grp.key[i]] = b; }
+        if (!dst.empty()) check(mi355_coset_ntt_fr_batch_dev(dst.data(), src.data(), (uint32_t)dst.size(), k, factor.data(), dom.omega.data()));
+        cosets[d] += (uint32_t)dst.size();
+        auto resolve = [&](const Atom &a) -> const void * {
+          if (a.kind == A_TMP) return tmp_on[d].at(a.idx).p;
+          if (a.kind == A_COMMON || P.is_pre(a.idx)) { const DevicePoly *c = pk.coset(a, q); return c ? c->p : kat.at(a); }
+          return wat.at(a.idx);
+        };
+        for (size_t l = grp.first; l < grp.last; l++) {
+          const Launch &L = cmp.out[l];
+          if (L.dst >= 0) run_launch(L, tmp_on[d].at((size_t)L.dst).p, n, fr_one(), L.accumulate, resolve);
+          else { run_launch(L, hq, n, tq_inv, !first, resolve); first = false; }
+          launches[d]++;
+        }
+      }
+      if (d != 0) check(mi355_buf_copy(hpart[q].p, hq, n * 32));
+    };
     auto do_parts = [&](int d) {
       try {
         for (uint32_t q = (uint32_t)d; q < Q; q += (uint32_t)D) {
+          if (grouped) { grouped_part(d, q); continue; }
           const Fr factor = part_factor(dom, q);
           std::vector<void *> dst(NP); std::vector<const void *> src(NP);
           for (uint32_t i = 0; i < NP; i++) { dst[i] = part_on[d].at(wrefs[i]).p; src[i] = d == 0 ? poly.at(wrefs[i]).p : coeff_on[d].at(wrefs[i]).p; }
@@ -998,10 +1082,11 @@ struct ProofRun {
           }
           if (d != 0) check(mi355_buf_copy(hpart[q].p, hq, n * 32));
         }
-      } catch (const std::exception &e) { errs[d] = e.what(); }
+      } catch (const Error &e) { errs[d] = e.what(); codes[d] = e.code; }   // the library's own code travels on: MI355_EOOM under a memory limit stays MI355_EOOM
+      catch (const std::exception &e) { errs[d] = e.what(); }
     };
     { Joiner others; for (int d = 1; d < D; d++) others.th.emplace_back(do_parts, d); do_parts(0); others.join(); }
-    for (int d = 0; d < D; d++) { if (!errs[d].empty()) throw Error(MI355_EHIP, "quotient part on device slot " + std::to_string(d) + ": " + errs[d]); R.gate_launches += launches[d]; R.coset_ntt += cosets[d]; }
+    for (int d = 0; d < D; d++) { if (!errs[d].empty()) throw Error(codes[d], "quotient part on device slot " + std::to_string(d) + ": " + errs[d]); R.gate_launches += launches[d]; R.coset_ntt += cosets[d]; }
     { std::vector<const void *> pp(Q); for (uint32_t q = 0; q < Q; q++) pp[q] = hpart[q].p; check(mi355_fr_interleave_dev(h.p, pp.data(), Q, n)); }
     check(mi355_extended_to_coeff_dev(h.p, dom.extended_k, dom.g_coset.data(), dom.g_coset_inv.data(), dom.extended_omega_inv.data(), dom.extended_ifft_divisor.data()));
   }
@@ -1086,6 +1171,7 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
   // resident coset parts were placed by keygen at q % pk.devices: the gate kernel on device d must find part q on d, so the proof runs on the key's device count
   // (a differing opt.devices would read a coset that sits on another device)
   if (pk.resident_cosets && pk.devices != std::max(1, opt.devices)) throw std::invalid_argument("create_proof: ProofOptions::devices (" + std::to_string(opt.devices) + ") differs from the proving key's (" + std::to_string(pk.devices) + ") while its coset parts are resident");
+  if (opt.coset_group_polys != 0 && opt.coset_group_polys < PLAN_MAX_POLYS) throw std::invalid_argument("create_proof: ProofOptions::coset_group_polys must be 0 or at least " + std::to_string(PLAN_MAX_POLYS));
   if (opt.check_witness) { CheckOptions co; co.threads = opt.threads; std::vector<VerifyFailure> bad = check_witness(pk, wit, co); if (!bad.empty()) throw WitnessError(std::move(bad)); }
   detail::ProofRun run(h_g, h_g_lagrange, pk, wit, opt);                                // the clock starts; the transcript takes the key's scalar and the instance values
   if (run.dev_rng) for (uint32_t i = 0; i < run.A; i++) if (wit.advice.at(i).size() < P.usable + 1) throw std::invalid_argument("create_proof: advice column " + std::to_string(i) + " has fewer than the usable rows + 1");

@@ -78,6 +78,9 @@ extern "C" {
     pub fn mi355_host_alloc(bytes: u64, host_ptr_out: *mut *mut c_void) -> c_int;
     pub fn mi355_host_free(host_ptr: *mut c_void) -> c_int;
     pub fn mi355_mem_info(device_slot: c_int, free_bytes: *mut u64, total_bytes: *mut u64, live_buf_bytes: *mut u64, pooled_bytes: *mut u64, workspace_bytes: *mut u64) -> c_int;
+    pub fn mi355_mem_set_limit(device_slot: c_int, bytes: u64) -> c_int;
+    pub fn mi355_mem_usage(device_slot: c_int, held_bytes: *mut u64, limit_bytes: *mut u64, high_water_bytes: *mut u64, class_bytes: *mut u64, n_classes: u32, reclaims: *mut u64, refused_bytes: *mut u64) -> c_int;
+    pub fn mi355_mem_reset_peak(device_slot: c_int) -> c_int;
     pub fn mi355_msm_g1_dev(srs: u64, base_offset: u64, scalars_dev: *const c_void, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g1_batch_dev(srs: u64, base_offset: u64, scalars_dev: *const *const c_void, batch: u32, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g2_adhoc_host(bases_g2affine_host: *const c_void, scalars_host: *const c_void, n: u64, out_g2affine_host: *mut c_void) -> c_int;

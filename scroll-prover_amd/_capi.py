@@ -36,6 +36,9 @@ SIGNATURES = {
     "mi355_host_alloc": (_int, [_u64, C.POINTER(_vp)]),
     "mi355_host_free": (_int, [_vp]),
     "mi355_mem_info": (_int, [_int, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "mi355_mem_set_limit": (_int, [_int, _u64]),
+    "mi355_mem_usage": (_int, [_int, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _u32, C.POINTER(_u64), C.POINTER(_u64)]),
+    "mi355_mem_reset_peak": (_int, [_int]),
     "mi355_srs_register_host": (_int, [_vp, _u64, C.POINTER(_u64)]),
     "mi355_srs_register_dev": (_int, [_vp, _u64, _int, C.POINTER(_u64)]),
     "mi355_srs_register_prefix": (_int, [_u64, _u64, C.POINTER(_u64)]),

@@ -98,7 +98,7 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
 
 
-CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check", "test_verify_proof", "test_verify_proofs", "test_device_randomness", "test_device_transcripts")
+CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check", "test_verify_proof", "test_verify_proofs", "test_device_randomness", "test_device_transcripts", "test_hbm_budget")
 
 
 def build_cpp(name: str) -> str:
@@ -111,7 +111,7 @@ def build_cpp(name: str) -> str:
     orc = os.path.join(root, "oracle")
     h = hashlib.sha256()
     inc = os.path.join(root, "include")
-    for f in [src, os.path.join(HERE, "csrc", "fp.hpp"), os.path.join(HERE, "csrc", "fp_asm.hpp"), os.path.join(HERE, "csrc", "fp_asm_gen.inc"), os.path.join(HERE, "csrc", "frrand.hpp"), os.path.join(HERE, "csrc", "slab_ranges.hpp"), os.path.join(orc, "bn254_oracle.c")] + sorted(os.path.join(inc, x) for x in os.listdir(inc)):
+    for f in [src, os.path.join(HERE, "csrc", "fp.hpp"), os.path.join(HERE, "csrc", "fp_asm.hpp"), os.path.join(HERE, "csrc", "fp_asm_gen.inc"), os.path.join(HERE, "csrc", "frrand.hpp"), os.path.join(HERE, "csrc", "slab_ranges.hpp"), os.path.join(HERE, "csrc", "mem_budget.hpp"), os.path.join(orc, "bn254_oracle.c")] + sorted(os.path.join(inc, x) for x in os.listdir(inc)):
         with open(f, "rb") as fh:
             h.update(fh.read())
     tag = exe + ".srchash"

@@ -313,7 +313,7 @@ int mi355_srs_downsize(uint64_t g_handle, uint32_t k, const void *omega_inv, con
   for (int sl = 1; sl < g_ndev; sl++) { CHK(bind_ctx(sl)); HIPCHK(hipStreamSynchronize(g.stream)); }
   CHK(bind_ctx(0));
   const g1_affine_t *src; CHK(srs_gather_to_primary(*sp, n, &src));
-  g1_affine_t *res; CHK(dev_malloc((void **)&res, n * sizeof(g1_affine_t), "srs_downsize"));
+  g1_affine_t *res; CHK(dev_malloc((void **)&res, n * sizeof(g1_affine_t), "srs_downsize", mi355zk::MEM_SRS));
   int rc = g1fft_impl(src, 0, res, 0, k, omega_inv, n_inv);
   if (rc == MI355_OK) rc = finish_async();
   if (rc == MI355_OK && hipStreamSynchronize(g.stream) != hipSuccess) rc = fail(MI355_EHIP, "srs_downsize: stream synchronize failed");
@@ -322,7 +322,7 @@ int mi355_srs_downsize(uint64_t g_handle, uint32_t k, const void *omega_inv, con
     if (plan_shards(n).size() == 1) { Shard one; one.slot = 0; one.lo = 0; one.n = n; one.dev = res; one.owned = true; s.mem->sh.push_back(one); res = nullptr; }
     else rc = srs_scatter_from_primary(*s.mem, res, n, false);
   }
-  if (res) { (void)bind_ctx(0); (void)hipFree(res); }
+  if (res) { (void)bind_ctx(0); dev_free(res); }
   if (rc != MI355_OK) return rc;
   *g_lagrange_handle_out = srs_insert(s); return MI355_OK;
   });
@@ -738,7 +738,7 @@ int mi355_poseidon_transcripts_host(const void *words_host, const uint64_t *word
   if (fresh) {
     const std::vector<fe_t> &t = poseidon_tables();
     const hipError_t e = hipMemcpyAsync(tab, t.data(), t.size() * sizeof(fe_t), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { g.ws.erase("poseidon.tables"); (void)hipFree(tab); HIPCHK(e); }
+    if (e != hipSuccess) { g.ws.erase("poseidon.tables"); dev_free(tab); HIPCHK(e); }
   }
   WsLayout L;
   const uint64_t off_words = L.take(n_words * sizeof(fe_t)), off_woff = L.take(((uint64_t)jobs + 1) * 8), off_soff = L.take(((uint64_t)jobs + 1) * 8), off_sq = L.take(n_sq * 4),

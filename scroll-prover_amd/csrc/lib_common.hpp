@@ -26,10 +26,13 @@
 #include "ntt_types.hpp"
 #include "ws_layout.hpp"
 #include "knobs.hpp"
+#include "mem_budget.hpp"
 
 namespace mi355 {
 using namespace zk;
 using mi355zk::WsLayout;
+using mi355zk::MemClass;
+using mi355zk::MemMode;
 
 extern thread_local std::string g_err;
 int fail(int code, const std::string &msg);
@@ -67,6 +70,9 @@ struct NttPlan {
   // twiddles as w * 2^261 mod r in 29-bit limbs (SoA) for the kernels of ntt29.hpp; tw29_s_lo[l] of a big level is the 2^log_s-entry table [k][column]
   Tw29 tw29_m[3] = {}, tw29_s_lo[2] = {}, tw29_s_hi[2] = {};
   std::vector<void *> owned;
+  // which of `owned` are optional (csrc/mem_budget.hpp, MEM_NTT_OPTIONAL): the s2d + in tables of `coset`, the tables of `scaled`, the 2-D level tables of direct2.  They can be
+  // given back at any time no transform is in flight (ntt_reclaim_optional): every pass has its table-free form with the same bits
+  std::vector<void *> optional;
 };
 struct Prof { double ms = 0; uint64_t launches = 0; };
 
@@ -97,6 +103,7 @@ struct Ctx : mi355zk::Knobs {
   int last_chunks = 1;
   std::map<std::string, Buf> ws;           // grow-only workspace arena, keyed by role
   std::map<std::string, NttPlan> ntt_plans;  // key = log_n | omega bytes
+  int ntt_pins = 0;             // transforms in flight on the calling thread that hold pointers into ntt_plans: the optional tables are not reclaimed meanwhile (PlanPin, lib_ntt.hip)
   g1_affine_t *fixed_base_table = nullptr;
   bool profiling = false;
   std::vector<Span> spans;      // profiling: (name, start, stop) event pairs resolved after the stream is idle
@@ -139,17 +146,29 @@ extern std::unordered_map<uint64_t, Srs> &g_srs;   // heap-allocated, never dest
 extern uint64_t g_next_handle;
 extern int g_last_devices; extern const char *g_last_exchange;
 
+// t_slots_held: bit s is set while the CALLING THREAD works under slot s's lock -- it took the lock through one of the guards below, or it is a worker thread of a call
+// that did (SlotHeld).  mi355_buf_alloc, the one allocation path that runs without the lock, reads it to know whether reclaiming the optional NTT tables needs the lock first.
+extern thread_local uint32_t t_slots_held;
+struct SlotHeld {   // a worker thread of an entry point that holds `slot`'s lock on its behalf
+  const uint32_t bit, was;
+  explicit SlotHeld(int slot) : bit(1u << slot), was(t_slots_held & (1u << slot)) { t_slots_held |= bit; }
+  ~SlotHeld() { if (!was) t_slots_held &= ~bit; }
+  SlotHeld(const SlotHeld &) = delete; SlotHeld &operator=(const SlotHeld &) = delete;
+};
 struct DevGuard {   // one device slot
-  std::unique_lock<std::mutex> lk;
-  explicit DevGuard(int slot) : lk(g_ctx_mu[slot]) {}
+  std::unique_lock<std::mutex> lk; const uint32_t bit;
+  explicit DevGuard(int slot) : lk(g_ctx_mu[slot]), bit(1u << slot) { t_slots_held |= bit; }
+  ~DevGuard() { t_slots_held &= ~bit; }
 };
 struct AllGuard {   // every slot, ascending
   std::unique_lock<std::mutex> lk[MAX_DEV];
-  AllGuard() { for (int i = 0; i < MAX_DEV; i++) lk[i] = std::unique_lock<std::mutex>(g_ctx_mu[i]); }
+  AllGuard() { for (int i = 0; i < MAX_DEV; i++) lk[i] = std::unique_lock<std::mutex>(g_ctx_mu[i]); t_slots_held = (1u << MAX_DEV) - 1; }
+  ~AllGuard() { t_slots_held = 0; }
 };
 struct MsmGuard {   // slot 0, plus every other bound slot when the process drives several devices
-  std::unique_lock<std::mutex> lk[MAX_DEV];
-  MsmGuard() { lk[0] = std::unique_lock<std::mutex>(g_ctx_mu[0]); for (int i = 1; i < g_ndev && i < MAX_DEV; i++) lk[i] = std::unique_lock<std::mutex>(g_ctx_mu[i]); }
+  std::unique_lock<std::mutex> lk[MAX_DEV]; uint32_t bits = 1;
+  MsmGuard() { lk[0] = std::unique_lock<std::mutex>(g_ctx_mu[0]); for (int i = 1; i < g_ndev && i < MAX_DEV; i++) { lk[i] = std::unique_lock<std::mutex>(g_ctx_mu[i]); bits |= 1u << i; } t_slots_held |= bits; }
+  ~MsmGuard() { t_slots_held &= ~bits; }
 };
 
 // One pooled mi355_buf block, back in the pool when its owner leaves scope -- on every exit path, so the body of an entry point uses HIPCHK / CHK and plain returns.  Declare it
@@ -192,8 +211,18 @@ struct CallTrace {
 };
 
 int ws_get(const char *role, size_t bytes, void **out);
-// hipMalloc on the current context's device; on out-of-memory the device's pooled (free) mi355_buf blocks go back to HIP and the call is retried once
-int dev_malloc(void **out, size_t bytes, const char *what);
+// The one pair through which the library takes device memory from HIP and gives it back (csrc/mem_budget.hpp is the ledger they keep).  dev_malloc allocates on the current
+// context's device: under a limit (mi355_mem_set_limit) the ledger decides BEFORE any HIP call; a request that does not fit, and a real out-of-memory error, first get the
+// slot's pooled blocks and free slabs back, then the optional NTT tables, and only then MI355_EOOM.  cls: what the ledger books the bytes under.  mode: what may be reclaimed
+// for the request and whether a refusal is reported (MemMode).  slot_locked: the calling thread works under the slot's lock -- true everywhere but in mi355_buf_alloc.
+// dev_free takes any pointer dev_malloc returned (nullptr is ignored) and returns its size; the caller has bound the owning device and drained the streams that may still use it.
+int dev_malloc(void **out, size_t bytes, const char *what, MemClass cls, MemMode mode = MemMode::Required, bool slot_locked = true);
+size_t dev_free(void *p);
+// min(free HBM, limit - held) of the current context's device: what a builder of optional tables may count on (0 when the runtime cannot say); *total_out: the device's HBM
+size_t dev_room(size_t *total_out);
+// lib_ntt.hip: gives the optional tables of every plan of `c` back (after draining its compute and auxiliary streams); returns the bytes freed, 0 while a transform is in
+// flight.  Called under c's slot lock only, with c's device bound.
+size_t ntt_reclaim_optional(Ctx &c);
 
 // ---- profiling: a list of (name, start, stop) event pairs per context, resolved after the stream is idle
 struct Scope {

@@ -7,6 +7,7 @@
 
 #include "lib_common.hpp"
 #include "buf_registry.hpp"
+#include "mem_budget.hpp"
 
 namespace mi355 {
 
@@ -28,12 +29,13 @@ std::unordered_map<uint64_t, Srs> &g_srs = *new std::unordered_map<uint64_t, Srs
 uint64_t g_next_handle = 1;
 int g_last_devices = 1; const char *g_last_exchange = "none";
 thread_local MsmOpts t_opts;
+thread_local uint32_t t_slots_held = 0;
 Rccl g_rccl;
 
 void free_shards(std::vector<Shard> &sh) {
   for (auto &x : sh) {
     if (x.slot < g_ndev && g_ctx[x.slot].inited) (void)hipSetDevice(g_ctx[x.slot].device);
-    if (x.owned && x.dev) (void)hipFree(x.dev);
+    if (x.owned && x.dev) dev_free(x.dev);
     x.dev = nullptr;
   }
   sh.clear();
@@ -41,7 +43,7 @@ void free_shards(std::vector<Shard> &sh) {
 SrsTables::~SrsTables() {
   for (size_t i = 0; i < pre.size(); i++) if (pre[i]) {
     if (slot[i] < g_ndev && g_ctx[slot[i]].inited) { (void)hipSetDevice(g_ctx[slot[i]].device); (void)hipStreamSynchronize(g_ctx[slot[i]].stream); }
-    (void)hipFree(pre[i]);
+    dev_free(pre[i]);
   }
 }
 
@@ -58,23 +60,69 @@ int need_init(int slot) {
 }
 
 static size_t pool_release_slot(int slot);
-// hipMalloc on the current context's device.  HBM may be full of blocks that only sit in the library's own buffer pool (mi355_buf_free keeps
-// them for reuse): before reporting MI355_EOOM the pooled blocks of THIS device go back to HIP and the allocation is tried once more
-// (ws_get, the twiddle tables and mi355_srs_precompute used to fail while gigabytes of free pooled blocks sat idle).
-int dev_malloc(void **out, size_t bytes, const char *what) {
+// ------------------------------------------------------------------------------------------------ device memory: the ledger and the one allocation pair
+// csrc/mem_budget.hpp (plain C++, model-checked on the host) is the bookkeeping and the order of the reclaims; this file keeps what calls HIP, and g_mem_mu, the one mutex
+// every ledger call runs under.  No other function of the library names the allocator.
+static std::mutex g_mem_mu;
+static mi355zk::MemLedger &g_mem = *new mi355zk::MemLedger();   // heap-allocated, never destroyed (as g_srs)
+// one reclaim of `step` on behalf of a request on `slot`; returns the bytes that went back to HIP.
+// LOCK RULE.  Step 1 (the pool) is pool_release_slot: registry state and thread-safe HIP calls only, so it runs with or without the slot's lock (comment there).  Step 2 (the
+// optional NTT tables) changes Ctx::ntt_plans, which the slot's lock protects: it runs only on a thread that works under that lock.  Every caller of dev_malloc does -- the compute
+// entry points, ws_get, the plan builders, SRS management under AllGuard, and their worker threads, which run under the lock their entry point holds -- except mi355_buf_alloc,
+// which therefore passes slot_locked = false unless t_slots_held says its thread holds the lock already (the auxiliary entry points allocate their pooled workspace through
+// PoolBlock AFTER their DevGuard, the params loader under AllGuard: taking the lock again there would deadlock).  Without the lock, it is taken for this step alone, and only
+// after step 1 made no room.  The tables are freed after sync_streams(SYNC_COMPUTE | SYNC_AUX) (ntt_reclaim_optional), and never while a transform of the calling thread holds
+// pointers into the plans (Ctx::ntt_pins).
+static size_t reclaim_step(int slot, mi355zk::MemStep step, bool slot_locked) {
+  size_t freed = 0;
+  if (step == mi355zk::MemStep::ReclaimPool) freed = pool_release_slot(slot);
+  else if (slot_locked) freed = ntt_reclaim_optional(g_ctx[slot]);
+  else { std::lock_guard<std::mutex> lk(g_ctx_mu[slot]); SlotHeld held(slot); freed = ntt_reclaim_optional(g_ctx[slot]); }
+  std::lock_guard<std::mutex> ml(g_mem_mu); g_mem.reclaimed(slot, freed);
+  return freed;
+}
+int dev_malloc(void **out, size_t bytes, const char *what, MemClass cls, MemMode mode, bool slot_locked) {
   *out = nullptr;
+  const int slot = g.slot;
+  for (int stage = 0;;) {   // the ledger first: under a limit nothing is asked of HIP that the limit does not allow
+    mi355zk::MemStep st; std::string refusal;
+    { std::lock_guard<std::mutex> ml(g_mem_mu); st = g_mem.reserve_step(slot, cls, bytes, stage, mode); if (st == mi355zk::MemStep::Refused && mode != MemMode::Spare) refusal = g_mem.describe_refusal(slot, bytes, what); }
+    if (st == mi355zk::MemStep::Charged) break;
+    if (st == mi355zk::MemStep::Refused) return mode == MemMode::Spare ? MI355_EOOM : fail(MI355_EOOM, refusal);
+    (void)reclaim_step(slot, st, slot_locked); stage++;
+  }
   hipError_t e = hipMalloc(out, bytes);
-  if (e == hipErrorOutOfMemory) {
+  for (int stage = 0; e == hipErrorOutOfMemory;) {   // HBM may be full of what the library itself could give back (pooled blocks; ADVICE r6: tables built for an earlier, smaller layer)
     (void)hipGetLastError();
-    if (pool_release_slot(g.slot) > 0) e = hipMalloc(out, bytes);
+    const mi355zk::MemStep st = mi355zk::MemLedger::oom_step(stage++, mode);
+    if (st == mi355zk::MemStep::Refused) break;
+    if (reclaim_step(slot, st, slot_locked) > 0) e = hipMalloc(out, bytes);
   }
   if (e != hipSuccess) {
     (void)hipGetLastError(); *out = nullptr;
+    { std::lock_guard<std::mutex> ml(g_mem_mu); g_mem.cancel(slot, cls, bytes); }
+    if (mode == MemMode::Spare) return MI355_EOOM;
     char b[256]; snprintf(b, sizeof b, "%s: hipMalloc of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
     return fail(e == hipErrorOutOfMemory ? MI355_EOOM : MI355_EHIP, b);
   }
+  { std::lock_guard<std::mutex> ml(g_mem_mu); g_mem.bind(*out, slot, cls, bytes); }
   return MI355_OK;
 }
+size_t dev_free(void *p) {
+  if (!p) return 0;
+  mi355zk::MemLedger::Rec r{0, 0, mi355zk::MEM_BUF};
+  { std::lock_guard<std::mutex> ml(g_mem_mu); (void)g_mem.release(p, &r); }
+  (void)hipFree(p);
+  return (size_t)r.bytes;
+}
+size_t dev_room(size_t *total_out) {
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (total_out) *total_out = tot;
+  std::lock_guard<std::mutex> ml(g_mem_mu);
+  return (size_t)g_mem.room(g.slot, fr);
+}
+static MemClass ws_class(const char *role) { return strcmp(role, "poseidon.tables") == 0 ? mi355zk::MEM_FIXED_TABLES : mi355zk::MEM_WORKSPACE; }
 
 hipError_t sync_streams(Ctx &c, unsigned which) {
   hipError_t first = hipSuccess;
@@ -89,11 +137,11 @@ int ws_get(const char *role, size_t bytes, void **out) {
   if (b.cap < bytes) {
     if (b.p) {   // every stream that may still touch the old block: compute, the two auxiliary streams, and the copy stream (host-pointer entry points stage through workspace blocks)
       HIPCHK(sync_streams(g, SYNC_COMPUTE | SYNC_AUX | SYNC_COPY));
-      HIPCHK(hipFree(b.p)); b.p = nullptr; b.cap = 0;
+      dev_free(b.p); b.p = nullptr; b.cap = 0;
     }
     size_t cap = bytes + bytes / 8 + 256;
-    // the head-room is a convenience (fewer regrowths), not a requirement: near the HBM limit the exact size is tried as well
-    if (dev_malloc(&b.p, cap, role) != MI355_OK) { cap = bytes; CHK(dev_malloc(&b.p, cap, role)); }
+    // the head-room is a convenience (fewer regrowths), not a requirement: near the HBM limit, or the caller's, the exact size is tried as well
+    if (dev_malloc(&b.p, cap, role, ws_class(role), MemMode::Headroom) != MI355_OK) { cap = bytes; CHK(dev_malloc(&b.p, cap, role, ws_class(role))); }
     b.cap = cap;
   }
   *out = b.p; return MI355_OK;
@@ -168,7 +216,7 @@ static size_t retire_blocks(int slot, const std::vector<BufBlock> &blocks, Retir
   size_t freed = 0;
   for (const auto &b : blocks) {
     if (b.free_ev) { if (how == Retire::ToSlab) (void)hipEventSynchronize((hipEvent_t)b.free_ev); (void)hipEventDestroy((hipEvent_t)b.free_ev); }
-    if (how == Retire::ToHip && !b.arena && b.p) { (void)hipFree(b.p); freed += b.bytes; }
+    if (how == Retire::ToHip && !b.arena && b.p) { dev_free(b.p); freed += b.bytes; }
   }
   if (how == Retire::ToSlab && !blocks.empty()) {
     (void)sync_streams(g_ctx[slot], SYNC_COPY);
@@ -186,7 +234,7 @@ static void arena_recycle_pool(int slot) {
 static size_t arena_release_free_slabs(int slot) {
   std::vector<uintptr_t> drop; size_t freed = 0;
   { std::lock_guard<std::mutex> bl(g_buf_mu); freed = g_reg.arena[slot].take_whole_slabs(drop); }
-  for (uintptr_t q : drop) (void)hipFree((void *)q);
+  for (uintptr_t q : drop) dev_free((void *)q);
   return freed;
 }
 
@@ -231,8 +279,8 @@ int pick_replica_slot() {
 }
 // give the pooled (free) blocks of one device slot back to HIP.  Returns bytes freed.  Callers: dev_malloc on an out-of-memory retry -- reached WITH the slot's lock from the
 // compute entry points and WITHOUT it from mi355_buf_alloc.  The invariant that makes both safe: this function touches only state under g_buf_mu (the registry) plus
-// thread-safe HIP calls (stream synchronisation, hipFree) on the calling thread's bound device; it must never read or write Ctx members that the slot's lock protects
-// (g.ws, the event rings, the plans).
+// thread-safe HIP calls (stream synchronisation, dev_free) on the calling thread's bound device; it must never read or write Ctx members that the slot's lock protects
+// (g.ws, the event rings, the plans).  What does touch such state -- giving back the optional NTT tables -- is the next step of the reclaim order and has its own rule: reclaim_step.
 static size_t pool_release_slot(int slot) {
   std::vector<BufBlock> drop;
   { std::lock_guard<std::mutex> bl(g_buf_mu); drop = g_reg.take_pooled(slot, false); if (drop.empty() && !g_reg.holds_carved(slot)) return 0; }
@@ -246,7 +294,7 @@ static void buf_release_all_locked() {   // shutdown: every slot's lock and g_bu
     const std::vector<BufBlock> all = g_reg.take_all(d);
     if ((!all.empty() || !g_reg.arena[d].slabs.empty()) && d < g_ndev && g_ctx[d].inited) (void)hipSetDevice(g_ctx[d].device);
     retire_blocks(d, all, Retire::ToHip);
-    for (auto &sl : g_reg.arena[d].slabs) (void)hipFree((void *)sl.base);
+    for (auto &sl : g_reg.arena[d].slabs) dev_free((void *)sl.base);
     g_reg.arena[d].clear();
   }
 }
@@ -282,11 +330,11 @@ static void destroy_ctx(int slot) {
   if (g.device < 0) return;                 // never reached hipSetDevice: nothing was created
   (void)hipSetDevice(g.device);
   (void)sync_streams(g, (g.stream ? SYNC_COMPUTE : 0u) | SYNC_COPY);
-  for (auto &kv : g.ws) if (kv.second.p) (void)hipFree(kv.second.p);
+  for (auto &kv : g.ws) if (kv.second.p) dev_free(kv.second.p);
   g.ws.clear();
-  for (auto &kv : g.ntt_plans) for (void *q : kv.second.owned) (void)hipFree(q);
+  for (auto &kv : g.ntt_plans) for (void *q : kv.second.owned) dev_free(q);
   g.ntt_plans.clear();
-  if (g.fixed_base_table) { (void)hipFree(g.fixed_base_table); g.fixed_base_table = nullptr; }
+  if (g.fixed_base_table) { dev_free(g.fixed_base_table); g.fixed_base_table = nullptr; }
   if (g.comm && g_rccl.CommDestroy) { (void)g_rccl.CommDestroy(g.comm); g.comm = nullptr; }
   for (const CtxStream &cs : ctx_streams(g)) if (*cs.s) { (void)hipStreamDestroy(*cs.s); *cs.s = nullptr; }   // a failed init_ctx leaves the later ones null
   for (hipEvent_t *e : ctx_events(g)) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
@@ -324,7 +372,7 @@ int srs_alloc(SrsMem &mem, uint64_t n) {
   mem.sh = plan_shards(n);
   for (auto &sh : mem.sh) {
     CHK(bind_ctx(sh.slot));
-    CHK(dev_malloc((void **)&sh.dev, sh.n * sizeof(g1_affine_t), "srs shard")); sh.owned = true;
+    CHK(dev_malloc((void **)&sh.dev, sh.n * sizeof(g1_affine_t), "srs shard", mi355zk::MEM_SRS)); sh.owned = true;
   }
   return bind_ctx(0);
 }
@@ -334,7 +382,7 @@ int srs_scatter_from_primary(SrsMem &mem, const g1_affine_t *src_dev, uint64_t n
   for (auto &sh : mem.sh) {
     if (sh.slot == 0 && alias_shard0) { sh.dev = const_cast<g1_affine_t *>(src_dev) + sh.lo; sh.owned = false; continue; }
     CHK(bind_ctx(sh.slot));
-    CHK(dev_malloc((void **)&sh.dev, sh.n * sizeof(g1_affine_t), "srs shard")); sh.owned = true;
+    CHK(dev_malloc((void **)&sh.dev, sh.n * sizeof(g1_affine_t), "srs shard", mi355zk::MEM_SRS)); sh.owned = true;
     if (sh.slot == 0 || g_ctx[sh.slot].device == g_ctx[0].device) HIPCHK(hipMemcpyAsync(sh.dev, src_dev + sh.lo, sh.n * sizeof(g1_affine_t), hipMemcpyDeviceToDevice, g.stream));
     else HIPCHK(hipMemcpyPeerAsync(sh.dev, g.device, src_dev + sh.lo, g_ctx[0].device, sh.n * sizeof(g1_affine_t), g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
@@ -574,6 +622,7 @@ int mi355_buf_alloc(uint64_t bytes, int device_slot, void **dev_ptr_out) {
   CHK(need_init(device_slot));
   const size_t want = ((size_t)bytes + 255) & ~(size_t)255;
   const mi355zk::SlabPolicy &pol = slab_policy();
+  const bool locked = (t_slots_held >> device_slot & 1u) != 0;   // an internal caller under the slot's lock (PoolBlock), or the lock-free public path: reclaim_step
   std::unique_lock<std::mutex> bl(g_buf_mu);
   for (bool recycled = false, slab_added = false;;) {
     const mi355zk::AllocStep st = g_reg.alloc_step(device_slot, want, recycled, pol);
@@ -585,12 +634,12 @@ int mi355_buf_alloc(uint64_t bytes, int device_slot, void **dev_ptr_out) {
       case mi355zk::AllocStep::Recycle: arena_recycle_pool(device_slot); recycled = true; bl.lock(); break;
       case mi355zk::AllocStep::Slab:
         // near the HBM limit the head-room of a shared slab is given up and the request gets exactly its size (dev_malloc frees whole slabs and retries before failing)
-        if (got > want && dev_malloc(&base, got, "buf_alloc (slab)") != MI355_OK) { base = nullptr; got = want; }
-        if (!base) CHK(dev_malloc(&base, got, "buf_alloc"));
+        if (got > want && dev_malloc(&base, got, "buf_alloc (slab)", mi355zk::MEM_BUF, MemMode::Headroom, locked) != MI355_OK) { base = nullptr; got = want; }
+        if (!base) CHK(dev_malloc(&base, got, "buf_alloc", mi355zk::MEM_BUF, MemMode::Required, locked));
         bl.lock(); g_reg.add_slab(device_slot, base, got, st.dedicated, pol); slab_added = true;   // carved under the same hold of the mutex: no other thread can take the new range
         break;
       default:   // Direct (slabs off): the pool of this device is given back to the allocator before giving up
-        CHK(dev_malloc(&base, want, "buf_alloc"));
+        CHK(dev_malloc(&base, want, "buf_alloc", mi355zk::MEM_BUF, MemMode::Required, locked));
         bl.lock(); g_reg.adopt(device_slot, base, want, false);
         *dev_ptr_out = base; return MI355_OK;
     }
@@ -757,6 +806,34 @@ int mi355_mem_info(int device_slot, uint64_t *free_bytes, uint64_t *total_bytes,
   for (const auto &kv : g.ws) ws += kv.second.cap;
   if (free_bytes) *free_bytes = fr; if (total_bytes) *total_bytes = tot; if (live_buf_bytes) *live_buf_bytes = live;
   if (pooled_bytes) *pooled_bytes = pooled; if (workspace_bytes) *workspace_bytes = ws;
+  return MI355_OK;
+  });
+}
+
+// ---- the memory limit (csrc/mem_budget.hpp).  No device lock: the ledger has its own mutex, and a limit only decides later allocations
+int mi355_mem_set_limit(int device_slot, uint64_t bytes) {
+  return guarded([&]() -> int {
+  if (device_slot < 0 || device_slot >= MAX_DEV) return fail(MI355_EBADARG, "mem_set_limit: device slot out of range");
+  std::lock_guard<std::mutex> ml(g_mem_mu); g_mem.set_limit(device_slot, bytes);
+  return MI355_OK;
+  });
+}
+int mi355_mem_usage(int device_slot, uint64_t *held_bytes, uint64_t *limit_bytes, uint64_t *high_water_bytes, uint64_t *class_bytes, uint32_t n_classes, uint64_t *reclaims, uint64_t *refused_bytes) {
+  return guarded([&]() -> int {
+  if (device_slot < 0 || device_slot >= MAX_DEV) return fail(MI355_EBADARG, "mem_usage: device slot out of range");
+  if (n_classes && !class_bytes) return fail(MI355_EBADARG, "mem_usage: null class array");
+  std::lock_guard<std::mutex> ml(g_mem_mu);
+  const mi355zk::MemSlot &m = g_mem.slot[device_slot];
+  if (held_bytes) *held_bytes = m.held; if (limit_bytes) *limit_bytes = m.limit; if (high_water_bytes) *high_water_bytes = m.high_water;
+  for (uint32_t c = 0; c < n_classes; c++) class_bytes[c] = c < (uint32_t)mi355zk::MEM_CLASSES ? m.by_class[c] : 0;
+  if (reclaims) *reclaims = m.reclaims; if (refused_bytes) *refused_bytes = m.refused_bytes;
+  return MI355_OK;
+  });
+}
+int mi355_mem_reset_peak(int device_slot) {
+  return guarded([&]() -> int {
+  if (device_slot < 0 || device_slot >= MAX_DEV) return fail(MI355_EBADARG, "mem_reset_peak: device slot out of range");
+  std::lock_guard<std::mutex> ml(g_mem_mu); g_mem.reset_peak(device_slot);
   return MI355_OK;
   });
 }

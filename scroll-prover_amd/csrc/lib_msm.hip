@@ -734,7 +734,7 @@ int mi355_srs_precompute(uint64_t handle, uint64_t n_hint, int c) {
     if (sh.lo >= sp->n) continue;
     const uint64_t cnt = std::min(sh.n, sp->n - sh.lo);   // a prefix view tabulates only its own points
     CHK(bind_ctx(sh.slot));
-    CHK(dev_malloc((void **)&tab->pre[i], (size_t)W * cnt * sizeof(g1_affine_t), "srs_precompute (window table)"));
+    CHK(dev_malloc((void **)&tab->pre[i], (size_t)W * cnt * sizeof(g1_affine_t), "srs_precompute (window table)", mi355zk::MEM_WINDOW_TABLES));
     tab->stride[i] = cnt;
     hipLaunchKernelGGL(k_srs_precompute, dim3(ceil_div(cnt, 256)), dim3(256), 0, g.stream, sh.dev, tab->pre[i], cnt, (uint32_t)W, (uint32_t)c);
     HIPCHK(hipGetLastError());
@@ -784,6 +784,7 @@ static int msm_multi(const std::vector<Piece> &pieces, const fe_t *const *polys,
   }
   auto work = [&](int slot) {
     t_opts = opts; t_opts.normalise = false;            // partials are folded (and normalised once) after the exchange
+    SlotHeld held(slot);                                // the entry point's MsmGuard holds this slot's lock on the worker's behalf
     auto body = [&]() -> int {
       CHK(bind_ctx(slot));
       g1_jac_t *send; CHK(ws_get("xchg.send", (size_t)M * sizeof(g1_jac_t), (void **)&send));
@@ -1109,7 +1110,7 @@ int mi355_msm_g2_batch_dev(const void *bases_g2affine_dev, const void *const *sc
 // ---- synthetic SRS
 static int ensure_fixed_base_table() {
   if (g.fixed_base_table) return MI355_OK;
-  CHK(dev_malloc((void **)&g.fixed_base_table, 32 * 256 * sizeof(g1_affine_t), "fixed-base table"));
+  CHK(dev_malloc((void **)&g.fixed_base_table, 32 * 256 * sizeof(g1_affine_t), "fixed-base table", mi355zk::MEM_FIXED_TABLES));
   hipLaunchKernelGGL(k_fixed_base_table, dim3(1), dim3(256), 0, g.stream, g.fixed_base_table);
   HIPCHK(hipGetLastError());
   return MI355_OK;

@@ -20,38 +20,64 @@ constexpr uint32_t NTT_DIRECT_TW_MAX_LOG = 20;   // 2^20 x 36 B = 38 MB per tabl
 std::string plan_key(uint32_t log_n, const void *omega) { std::string k((const char *)omega, 32); k.push_back((char)log_n); return k; }
 
 // The one owner of a plan's tables: the three device arrays (SoA) of a `count`-entry table, registered in p.owned only when all three exist.
-// TableMem::pooled: dev_malloc -- the device's pooled blocks are given back and the allocation retried before MI355_EOOM is reported (the small power tables:
-// failure is an error); TableMem::spare: plain hipMalloc and a quiet MI355_EOOM (the big optional tables: the caller then takes the table-free form of the pass).
+// TableMem::pooled: a required table (the small power tables) -- everything the library can give back is reclaimed before MI355_EOOM is reported: failure is an error;
+// TableMem::spare: an optional table (MEM_NTT_OPTIONAL: nothing is reclaimed for it, a quiet MI355_EOOM, and the caller then takes the table-free form of the pass); it is
+// listed in p.optional, from where ntt_reclaim_optional gives it back when something else needs the memory.
 enum class TableMem { pooled, spare };
 static int alloc_plan_table(NttPlan &p, uint64_t count, TableMem mem, Soa29 *out) {
   void *a[3] = {nullptr, nullptr, nullptr}; const size_t bytes[3] = {count * 16, count * 16, count * 4};
   int rc = MI355_OK;
   for (int i = 0; i < 3 && rc == MI355_OK; i++) {
-    if (mem == TableMem::pooled) rc = dev_malloc(&a[i], bytes[i], "ntt twiddles");
-    else if (hipMalloc(&a[i], bytes[i]) != hipSuccess) { (void)hipGetLastError(); a[i] = nullptr; rc = MI355_EOOM; }
+    if (mem == TableMem::pooled) rc = dev_malloc(&a[i], bytes[i], "ntt twiddles", mi355zk::MEM_NTT_REQUIRED);
+    else rc = dev_malloc(&a[i], bytes[i], "ntt tables (optional)", mi355zk::MEM_NTT_OPTIONAL, MemMode::Spare);
   }
-  if (rc != MI355_OK) { for (void *q : a) if (q) (void)hipFree(q); return rc; }
+  if (rc != MI355_OK) { for (void *q : a) dev_free(q); return rc; }
   p.owned.insert(p.owned.end(), a, a + 3);
+  if (mem == TableMem::spare) p.optional.insert(p.optional.end(), a, a + 3);
   *out = Soa29{(uint4 *)a[0], (uint4 *)a[1], (uint32_t *)a[2]};
   return MI355_OK;
 }
 // gives back the tables registered from index `from` of p.owned on (0: all of them), once the stream that may still be building them has drained
 static void free_plan_tables(NttPlan &p, size_t from = 0) {
   (void)hipStreamSynchronize(g.stream);
-  for (size_t i = from; i < p.owned.size(); i++) (void)hipFree(p.owned[i]);
+  for (size_t i = from; i < p.owned.size(); i++) { p.optional.erase(std::remove(p.optional.begin(), p.optional.end(), p.owned[i]), p.optional.end()); dev_free(p.owned[i]); }
   p.owned.resize(from);
+}
+// A transform in flight holds pointers into the plan cache (the plan, a scaled table, a coset pair) from its first look-up to its last launch; its own workspace
+// allocations in between must not pull the tables away under it.  Nests (a coset entry point pins, then ntt_dev_impl pins again); under the slot's lock, as the plans.
+struct PlanPin { Ctx &c; PlanPin() : c(g) { c.ntt_pins++; } ~PlanPin() { c.ntt_pins--; } PlanPin(const PlanPin &) = delete; PlanPin &operator=(const PlanPin &) = delete; };
+// Step 2 of the reclaim order (csrc/mem_budget.hpp; the lock rule is at reclaim_step in lib_core.hip): the coset and scaled entries go with their memory; a plan that took
+// direct2 goes whole, so that its next use rebuilds it and build_plan chooses again.  Every pass has its table-free form (k_distribute_powers first; the lo x hi pair; the
+// divisor as a multiplication in the closing pass) with the same bits.
+size_t ntt_reclaim_optional(Ctx &c) {
+  if (c.ntt_pins > 0) return 0;
+  bool any = false; for (const auto &kv : c.ntt_plans) any = any || !kv.second.optional.empty();
+  if (!any) return 0;
+  (void)sync_streams(c, SYNC_COMPUTE | SYNC_AUX);   // a transform queued earlier may still read them
+  size_t freed = 0;
+  for (auto it = c.ntt_plans.begin(); it != c.ntt_plans.end();) {
+    NttPlan &p = it->second;
+    if (p.optional.empty()) { ++it; continue; }
+    const bool whole = p.direct2[0] || p.direct2[1];
+    const std::vector<void *> drop = whole ? p.owned : p.optional;
+    for (void *q : drop) { freed += dev_free(q); p.owned.erase(std::remove(p.owned.begin(), p.owned.end(), q), p.owned.end()); }
+    if (whole) { it = c.ntt_plans.erase(it); continue; }
+    p.optional.clear(); p.coset.clear(); p.scaled.clear();
+    ++it;
+  }
+  return freed;
 }
 // big twiddle tables (256 MB and more) are only built into HBM that is really spare: the table plus max(16 GiB, 1/12 of the device) must be free -- a multi-layer prover process
 // that peaks at 274 GiB of 288 builds none of them and takes the table-free form of the same pass (the lo x hi product, or the separate coset shift)
 static bool hbm_spare_for_table(uint64_t entries) {
   if (entries * 36 < (256ull << 20)) return true;
-  size_t fr = 0, tot = 0;
-  if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return false; }
+  size_t tot = 0; const size_t fr = dev_room(&tot);   // min(free HBM, limit - held): under mi355_mem_set_limit the margin is kept below the limit
+  if (!tot) return false;
   return fr >= entries * 36 + std::max<size_t>((size_t)16 << 30, tot / 12);
 }
 
-int pow_table29(NttPlan &p, Tw29 *out, const fe_t &base, uint64_t step, uint32_t count) {
-  Soa29 t; CHK(alloc_plan_table(p, count, TableMem::pooled, &t));
+int pow_table29(NttPlan &p, Tw29 *out, const fe_t &base, uint64_t step, uint32_t count, TableMem mem = TableMem::pooled) {
+  Soa29 t; CHK(alloc_plan_table(p, count, mem, &t));
   hipLaunchKernelGGL(k_pow_table29, dim3(ceil_div(count, 256)), dim3(256), 0, g.stream, t.lo, t.hi, t.top, base, step, count);
   HIPCHK(hipGetLastError());
   *out = t;
@@ -64,8 +90,9 @@ int launch_pow_table(fe_t *out, const fe_t &base, uint64_t step, uint32_t count)
   return MI355_OK;
 }
 
+static bool plan_is_multi_pass(uint32_t log_n) { return log_n > 8; }   // build_plan below: one workgroup of the closing pass up to 2^8
 static int build_plan(NttPlan &p, uint32_t log_n, const void *omega) {
-  if (log_n <= 8) { p.levels = 1; p.log_m[0] = log_n; }
+  if (!plan_is_multi_pass(log_n)) { p.levels = 1; p.log_m[0] = log_n; }
   else if (log_n <= g.ntt_two_level_max_log) { p.levels = 2; p.log_m[0] = (log_n + 1) / 2; p.log_m[1] = log_n / 2; }   // two passes up to 2^18 (2^20 as an A/B knob: 1024-point columns, two adjacent columns per tile)
   else { p.levels = 3; p.log_m[0] = (log_n + 2) / 3; p.log_m[1] = (log_n + 1) / 3; p.log_m[2] = log_n / 3; }
   fe_t w; memcpy(&w, omega, 32);
@@ -150,7 +177,7 @@ static const NttPlan::CosetTw *coset_fold_tables(NttPlan *p, uint32_t log_n, con
   if (!hbm_spare_for_table(cnt) || alloc_plan_table(*p, cnt, TableMem::spare, &s2d) != MI355_OK) return nullptr;
   hipLaunchKernelGGL(k_pow_table29_2d, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, g.stream, s2d.lo, s2d.hi, s2d.top, w, log_t, cnt, f, 1);   // level 0: w_S = omega (S = N)
   // a failed build keeps nothing: tables left in p->owned without an entry in p->coset would be allocated again by every later call with this factor
-  if (hipGetLastError() != hipSuccess || pow_table29(*p, &T.in, Fr::pow_u64(f, 1ull << log_t), 1, 1u << lm) != MI355_OK) { free_plan_tables(*p, mark); return nullptr; }
+  if (hipGetLastError() != hipSuccess || pow_table29(*p, &T.in, Fr::pow_u64(f, 1ull << log_t), 1, 1u << lm, TableMem::spare) != MI355_OK) { free_plan_tables(*p, mark); return nullptr; }
   T.s2d = s2d;
   return &p->coset.emplace(key, T).first->second;
 }
@@ -227,14 +254,16 @@ int ntt_dev_impl(const fe_t *src, uint64_t src_len, fe_t *dst, uint32_t log_n, c
     if (post3_host) { HIPCHK(hipMemcpyAsync(c + 3, post3_host, 3 * sizeof(fe_t), hipMemcpyHostToDevice, s)); post3 = c + 3; }
     HIPCHK(hipStreamSynchronize(s));  // the host copies may be stack temporaries of the caller
   }
+  // every workspace block and the plan itself (its required tables) BEFORE the pin: these allocations may still reclaim optional tables; from the pin on only spare ones follow
+  fe_t *scratch = nullptr;
+  if (plan_is_multi_pass(log_n)) CHK(ws_get("ntt.scratch", N * sizeof(fe_t), (void **)&scratch));
   NttPlan *p; CHK(get_plan(log_n, omega, &p));
+  PlanPin pin;
   const Tw29 *fold_tw = nullptr;
   CHK(fold_divisor(p, log_n, pre3_host, post3_host, &fold_tw, &post3));
   if (coset && (p->levels < 2 || fold_tw || pre3)) return fail(MI355_EBADARG, "ntt: a folded coset shift needs a multi-pass plan and no other scaling");
   CallTrace tr("ntt_fr", N, 64.0);
   Scope total("ntt_total");
-  fe_t *scratch = nullptr;
-  if (p->levels > 1) CHK(ws_get("ntt.scratch", N * sizeof(fe_t), (void **)&scratch));
   CHK(enqueue_passes(*p, PassVectors::single(src, src_len, pre3, scratch, dst), post3, fold_tw, coset));
   total.close();
   tr.done();
@@ -247,6 +276,16 @@ int transform_in_place(fe_t *data, uint32_t log_n, const void *omega, const void
   return ntt_dev_impl(data, 1ull << log_n, data, log_n, omega, nullptr, post);
 }
 
+// when a list of cnt transforms of 2^log_n elements runs as batched launches, and over how many vectors at a time: at most 1 GiB of scratch, and gridDim.y <= 65535
+static bool batch_applies(size_t cnt, uint32_t log_n) { return cnt >= 2 && log_n <= g.ntt_batch_max_log && log_n <= 28 && plan_is_multi_pass(log_n); }
+static size_t batch_chunk(size_t cnt, uint64_t N) { return std::min<size_t>(std::min<size_t>(cnt, 65535), std::max<size_t>(1, (size_t)((1ull << 30) / (N * sizeof(fe_t))))); }
+// The workspace a coset transform of `cnt` vectors will ask for, taken by its entry point BEFORE it looks up the plan and pins it: the workspace arena only grows, so the
+// transform's own requests then allocate nothing, and whatever these allocate here may still reclaim the optional tables.
+static int reserve_transform_ws(size_t cnt, uint32_t log_n) {
+  void *x; const uint64_t N = 1ull << log_n;
+  if (batch_applies(cnt, log_n)) { CHK(ws_get("ntt.scratch.batch", batch_chunk(cnt, N) * N * sizeof(fe_t), &x)); return ws_get("ntt.batch.ptrs", 3 * cnt * sizeof(void *), &x); }
+  return plan_is_multi_pass(log_n) ? ws_get("ntt.scratch", N * sizeof(fe_t), &x) : MI355_OK;
+}
 // `data.size()` in-place transforms of 2^log_n elements (optionally times a divisor) as batched launches: blockIdx.y = vector.  Used by the batch entry
 // points for small transforms; falls back to the loop of single transforms where the batched kernels do not apply.  Same results.
 // srcs / coset: data[i] = transform of srcs[i][j] f^j (the folded coset shift; srcs[i] is only read, so it may be the coefficient vector itself)
@@ -259,27 +298,28 @@ int ntt_batch_inplace(const std::vector<fe_t *> &data, uint32_t log_n, const voi
     }
     return MI355_OK;
   };
-  if (cnt < 2 || log_n > g.ntt_batch_max_log || log_n > 28) return single_loop();
-  NttPlan *p; CHK(get_plan(log_n, omega, &p));
-  if (p->levels < 2) return single_loop();
+  if (!batch_applies(cnt, log_n)) return single_loop();
+  // in-place transforms of ONE buffer listed twice must run one after the other (the serial loop applied the transform twice; concurrent passes would race)
+  { std::vector<const void *> seen(data.begin(), data.end()); std::sort(seen.begin(), seen.end()); if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return single_loop(); }
   const uint64_t N = 1ull << log_n;
   hipStream_t s = g.stream;
+  // the workspace blocks and the plan before the pin (as ntt_dev_impl)
+  fe_t *consts = nullptr; if (divisor) CHK(ws_get("ntt.consts", 6 * sizeof(fe_t), (void **)&consts));
+  const size_t chunk = batch_chunk(cnt, N);
+  fe_t *scratch; CHK(ws_get("ntt.scratch.batch", chunk * N * sizeof(fe_t), (void **)&scratch));
+  const fe_t **dtab; CHK(ws_get("ntt.batch.ptrs", 3 * cnt * sizeof(void *), (void **)&dtab));
+  NttPlan *p; CHK(get_plan(log_n, omega, &p));
+  PlanPin pin;
   fe_t post_host[3]; fe_t *post3 = nullptr; const Tw29 *fold_tw = nullptr;
   if (divisor) {
     post3_from_divisor(post_host, divisor);
-    fe_t *c; CHK(ws_get("ntt.consts", 6 * sizeof(fe_t), (void **)&c));
-    HIPCHK(hipMemcpyAsync(c + 3, post_host, 3 * sizeof(fe_t), hipMemcpyHostToDevice, s)); HIPCHK(hipStreamSynchronize(s));
-    post3 = c + 3;
+    HIPCHK(hipMemcpyAsync(consts + 3, post_host, 3 * sizeof(fe_t), hipMemcpyHostToDevice, s)); HIPCHK(hipStreamSynchronize(s));
+    post3 = consts + 3;
     CHK(fold_divisor(p, log_n, nullptr, post_host, &fold_tw, &post3));
   }
-  // in-place transforms of ONE buffer listed twice must run one after the other (the serial loop applied the transform twice; concurrent passes would race)
-  { std::vector<const void *> seen(data.begin(), data.end()); std::sort(seen.begin(), seen.end()); if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return single_loop(); }
-  const size_t chunk = std::min<size_t>(std::min<size_t>(cnt, 65535), std::max<size_t>(1, (size_t)((1ull << 30) / (N * sizeof(fe_t)))));   // at most 1 GiB of scratch, and gridDim.y <= 65535
-  fe_t *scratch; CHK(ws_get("ntt.scratch.batch", chunk * N * sizeof(fe_t), (void **)&scratch));
   // pointer tables for the whole list: data[i] and the scratch slot of i (slots repeat chunk by chunk; the stream orders their reuse)
   std::vector<const fe_t *> tab(3 * cnt);
   for (size_t i = 0; i < cnt; i++) { tab[i] = data[i]; tab[cnt + i] = scratch + (i % chunk) * N; tab[2 * cnt + i] = coset ? (*srcs)[i] : data[i]; }   // [destination | scratch slot | first-pass source]
-  const fe_t **dtab; CHK(ws_get("ntt.batch.ptrs", 3 * cnt * sizeof(void *), (void **)&dtab));
   HIPCHK(hipMemcpyAsync(dtab, tab.data(), 3 * cnt * sizeof(void *), hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));   // `tab` is a stack-lifetime vector
   CallTrace tr("ntt_fr_batch", N * cnt, 64.0);
@@ -526,10 +566,14 @@ int mi355_coset_ntt_fr_dev(void *dst_dev, const void *coeffs_dev, uint32_t log_n
   int slot; CHK(common_slot({dst_dev, coeffs_dev}, &slot, "coset_ntt")); DevGuard lk(slot);
   CHK(need_init(slot)); CHK(check_ntt_args(dst_dev, log_n, omega));
   if (!coeffs_dev || !coset_factor) return fail(MI355_EBADARG, "coset_ntt: null pointer");
+  CHK(reserve_transform_ws(1, log_n));
   NttPlan *p; CHK(get_plan(log_n, omega, &p));
-  if (const NttPlan::CosetTw *ct = coset_fold_tables(p, log_n, omega, coset_factor)) {
-    CHK(ntt_dev_impl((const fe_t *)coeffs_dev, 1ull << log_n, (fe_t *)dst_dev, log_n, omega, nullptr, nullptr, ct));   // the shift rides on the first pass: no k_distribute_powers
-    return finish_async();
+  {
+    PlanPin pin;   // ct points into the plan
+    if (const NttPlan::CosetTw *ct = coset_fold_tables(p, log_n, omega, coset_factor)) {
+      CHK(ntt_dev_impl((const fe_t *)coeffs_dev, 1ull << log_n, (fe_t *)dst_dev, log_n, omega, nullptr, nullptr, ct));   // the shift rides on the first pass: no k_distribute_powers
+      return finish_async();
+    }
   }
   CHK(distribute_powers_locked(dst_dev, 1ull << log_n, coset_factor, coeffs_dev));   // dst = coeffs[i] * factor^i (one pass, no copy first)
   CHK(ntt_dev_impl((const fe_t *)dst_dev, 1ull << log_n, (fe_t *)dst_dev, log_n, omega, nullptr, nullptr));
@@ -584,10 +628,14 @@ int mi355_coset_ntt_fr_batch_dev(void *const *dst_dev, const void *const *coeffs
     std::vector<const void *> src; std::vector<void *> dst;
     for (uint32_t i : idx) { src.push_back(coeffs_dev[i]); dst.push_back(dst_dev[i]); }
     std::vector<fe_t *> list; for (void *d : dst) list.push_back((fe_t *)d);
+    CHK(reserve_transform_ws(list.size(), log_n));
     NttPlan *p; CHK(get_plan(log_n, omega, &p));
-    if (const NttPlan::CosetTw *ct = coset_fold_tables(p, log_n, omega, coset_factor)) {   // round 6: the shift rides on the first pass of every transform of the list
-      std::vector<const fe_t *> from; for (const void *q : src) from.push_back((const fe_t *)q);
-      return ntt_batch_inplace(list, log_n, omega, nullptr, &from, ct);
+    {
+      PlanPin pin;   // ct points into the plan
+      if (const NttPlan::CosetTw *ct = coset_fold_tables(p, log_n, omega, coset_factor)) {   // round 6: the shift rides on the first pass of every transform of the list
+        std::vector<const fe_t *> from; for (const void *q : src) from.push_back((const fe_t *)q);
+        return ntt_batch_inplace(list, log_n, omega, nullptr, &from, ct);
+      }
     }
     CHK(distribute_powers_batch_locked(src, dst, 1ull << log_n, coset_factor));
     return ntt_batch_inplace(list, log_n, omega, nullptr);

@@ -230,6 +230,28 @@ def mem_info(slot: int = 0) -> dict:
     return dict(zip(("free", "total", "live_buffers", "pooled", "workspace"), (x.value for x in v)))
 
 
+MEM_CLASSES = ("buffers", "workspace", "ntt_required", "ntt_optional", "srs", "window_tables", "fixed_tables")
+
+
+def mem_set_limit(bytes_: int, slot: int = 0) -> None:
+    """A limit on the device memory the library holds on one device slot (mi355_mem_set_limit; 0 lifts it).  An allocation that would pass it is decided on the host, before
+    any HIP call: the pool and the free slabs go back first, then the optional NTT tables, then the call raises Mi355Error(EOOM) naming the limit."""
+    check(lib().mi355_mem_set_limit(slot, int(bytes_)))
+
+
+def mem_usage(slot: int = 0) -> dict:
+    """What the library's ledger holds on one device slot (mi355_mem_usage), in bytes: held (the sum of the classes), limit (0: none), high_water since mem_reset_peak,
+    classes {name: bytes} in the order of MEM_CLASSES, reclaims, refused."""
+    held, limit, peak, reclaims, refused = (C.c_uint64() for _ in range(5))
+    cls = (C.c_uint64 * len(MEM_CLASSES))()
+    check(lib().mi355_mem_usage(slot, C.byref(held), C.byref(limit), C.byref(peak), cls, len(MEM_CLASSES), C.byref(reclaims), C.byref(refused)))
+    return {"held": held.value, "limit": limit.value, "high_water": peak.value, "classes": dict(zip(MEM_CLASSES, (int(x) for x in cls))), "reclaims": reclaims.value, "refused": refused.value}
+
+
+def mem_reset_peak(slot: int = 0) -> None:
+    check(lib().mi355_mem_reset_peak(slot))
+
+
 def fr_vec_op(op: str, dst, a, b):
     """element-wise add / sub / mul of device-resident Fr vectors (pointwise steps of the quotient construction)."""
     n = a.numel() * a.element_size() // 32

@@ -195,3 +195,29 @@ def run_device_randomness(layer: int, key: bytes, k: int | None = None, out_dir:
             with open(p, "rb") as f:
                 rec[name] = f.read()
     return rec
+
+
+def run_hbm_budget(layer: int, k: int | None = None, out_dir: str | None = None, args=(), env=None, timeout: int = 1800, protocol_file: str | None = None, **shape) -> dict:
+    """tests/cpp/test_hbm_budget.cpp: one layer's instance proven in ONE process by the ungrouped route and with ProofOptions::coset_group_polys ("--group G|all"), each
+    proof's high-water mark read from the library's ledger (mi355_mem_usage).  Returns the program's record with `proof_ungrouped`, `proof_grouped`, `vk` and `instances`.
+    args: "--pk-cosets on-the-fly", "--devices D", "--device-multiplicities", "--fit" (the limit set midway between the two peaks: record["fit"]), "--bench N --groups 0,all,64"."""
+    from . import build
+    out_dir = out_dir or tempfile.mkdtemp(prefix=f"mi355_hbm_budget_l{layer}_")
+    os.makedirs(out_dir, exist_ok=True)
+    proto = write_protocol(layer, out_dir, k, protocol_file, **shape)
+    e = dict(os.environ)
+    e.update(env or {})
+    t0 = time.perf_counter()
+    out = subprocess.run([build.build_cpp("test_hbm_budget"), "--protocol", proto, "--out", out_dir] + list(args), capture_output=True, text=True, timeout=timeout, env=e)
+    line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
+    rec = {"layer": layer, "ok": False, "returncode": out.returncode, "out_dir": out_dir, "protocol_path": proto, "process_wall_s": time.perf_counter() - t0}
+    if out.returncode != 0 or line is None:
+        rec["error"] = (out.stdout + out.stderr)[-1200:]
+        return rec
+    rec.update(json.loads(line))
+    for name in ("proof_ungrouped", "proof_grouped", "vk", "instances"):
+        p = os.path.join(out_dir, name + ".bin")
+        if os.path.exists(p):
+            with open(p, "rb") as f:
+                rec[name] = f.read()
+    return rec
