@@ -538,8 +538,9 @@ static int distribute_powers_locked(void *data_dev, uint64_t n, const void *fact
   HIPCHK(hipGetLastError());
   return MI355_OK;
 }
-// the coset shift of `cnt` polynomials in one launch: dst[i][j] = src[i][j] * factor^j.  The pointer tables travel through a workspace buffer; the
-// caller synchronises the stream before `ptrs` (host) goes away (the batch entry points end with a stream synchronisation).
+// the coset shift of `cnt` polynomials in one launch: dst[i][j] = src[i][j] * factor^j.  The pointer tables travel through a workspace buffer that every
+// slice reuses; the stream is synchronised after every slice, the last included: `src` and `dst` are the caller's vectors, and on the way through the loop of
+// single transforms (single-pass plans, sizes above MI355_NTT_BATCH_MAX_LOG) nothing else waits for the copies before those vectors go away.
 static int distribute_powers_batch_locked(const std::vector<const void *> &src, const std::vector<void *> &dst, uint64_t n, const void *factor) {
   const size_t cnt = src.size();
   if (cnt == 0 || n == 0) return MI355_OK;
@@ -550,7 +551,7 @@ static int distribute_powers_batch_locked(const std::vector<const void *> &src, 
     HIPCHK(hipMemcpyAsync(tab + cnt, dst.data() + base, c * sizeof(void *), hipMemcpyHostToDevice, g.stream));
     hipLaunchKernelGGL(k_distribute_powers_batch, dim3(ceil_div(n, (uint64_t)EVAL_RUN * 256), (uint32_t)c), dim3(256), 0, g.stream, (const fe_t *const *)tab, (fe_t *const *)(tab + cnt), n, dist_factors(factor));
     HIPCHK(hipGetLastError());
-    if (base + c < cnt) HIPCHK(hipStreamSynchronize(g.stream));   // the table is reused by the next slice
+    HIPCHK(hipStreamSynchronize(g.stream));   // the table is reused by the next slice; the host arrays belong to the caller
   }
   return MI355_OK;
 }

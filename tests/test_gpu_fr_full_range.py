@@ -383,7 +383,8 @@ def test_coset_extension_over_the_whole_field(zk, k, j):
 def test_batched_transforms_over_the_whole_field(zk, k):
     """mi355_ntt_fr_batch_dev (with and without a divisor) and mi355_coset_ntt_fr_batch_dev on each side of the smallest batched launch: single-pass
     plans (k <= 8) run the loop of single transforms, larger ones one launch per pass with blockIdx.y = polynomial.  (Above the upper limit,
-    MI355_NTT_BATCH_MAX_LOG, the same loop runs: test_ntt_plan_knobs sets it to 0.)"""
+    MI355_NTT_BATCH_MAX_LOG, the same loop runs: test_ntt_plan_knobs sets it to 0.)  Batches larger than one scratch chunk or one gridDim.y slice are in
+    tests/test_gpu_ntt_batch_sweep.py."""
     h2 = zk.halo2
     lib, check, ptr = zk._capi.lib(), zk._capi.check, zk._capi.ptr
     n = 1 << k
