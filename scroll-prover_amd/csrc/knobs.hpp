@@ -22,7 +22,7 @@
   X(seg_fill, 40, "MI355_SEG_FILL", Range, 2, 100, "share (%) of the launched accumulate threads the entries are spread over, per-bucket fix-up (above 100 the segments would not cover the entries)") \
   X(seg_fill_segfix, 40, "MI355_SEG_FILL_SEGFIX", Range, 2, 100, "the same share with the segmented fix-up") \
   X(seg_min, 16, "MI355_SEG_MIN", Range, 1, 4096, "shortest accumulate segment (entries per thread) when few digits are non-zero") \
-  X(fixup_mode, 2, "MI355_FIXUP_MODE", FirstChar, 0, 2, "2: fix-up by shape (msm_enqueue); 0: per-bucket kernels; 1: one segmented reduction over the partial sums (k_msm_segfix)") \
+  X(fixup_mode, 2, "MI355_FIXUP_MODE", FirstChar, 0, 2, "2: fix-up by shape (plan_pass, msm_plan.hpp); 0: per-bucket kernels; 1: one segmented reduction over the partial sums (k_msm_segfix)") \
   X(fixup_huge_min, 2048, "MI355_FIXUP_HUGE_MIN", RangeLong, 2048, 0x7fffffffL, "bucket spans from this many accumulate threads on are summed by several workgroups") \
   X(fixup_serial_max, 32, "MI355_FIXUP_SERIAL_MAX", Range, 1, 1024, "bucket spans (in accumulate threads) above this go to the workgroup-per-bucket fix-up") \
   X(fixup_lanes_max_log, 17, "MI355_FIXUP_LANES_MAX_LOG", Range, 0, 31, "bucket sets up to 2^this records take the four-lanes-per-bucket fix-up") \

@@ -26,6 +26,7 @@
 #include "ntt_types.hpp"
 #include "ws_layout.hpp"
 #include "knobs.hpp"
+#include "msm_plan.hpp"
 #include "mem_budget.hpp"
 
 namespace mi355 {
@@ -76,6 +77,13 @@ struct NttPlan {
 };
 struct Prof { double ms = 0; uint64_t launches = 0; };
 
+// How the last MSM ran: window bits, windows, sorted entries (all passes of the call), one shared bucket set (window tables), point-range slices of the host-pointer schedule,
+// device slots that took part and how their partials were exchanged ("none" | "rccl_allgather" | "device_copy").  begin() where a top-level call starts on a device
+// (msm_run, lib_msm.hip); every pass adds itself.
+struct MsmRunRecord {
+  int c = 0, windows = 0; uint64_t entries = 0; bool shared = false; int host_slices = 1, devices = 1; const char *exchange = "none";
+  void begin() { entries = 0; host_slices = 1; devices = 1; exchange = "none"; }
+};
 struct MsmSlot { int id = 0; hipEvent_t sorted = nullptr, acc_done = nullptr, red_done = nullptr; bool used = false; };   // per-chunk buffers + events of the pipelined MSM
 
 struct Span { std::string name; hipEvent_t a, b; };
@@ -88,7 +96,7 @@ struct Ctx : mi355zk::Knobs {
   // streams (ctx_streams below lists the owned ones once, for init_ctx / destroy_ctx / sync_streams).  `stream` is the compute stream: own_stream, or the caller's (mi355_set_stream)
   hipStream_t own_stream = nullptr, stream = nullptr;
   hipStream_t aux_stream[2] = {nullptr, nullptr};   // side streams of the pipelined MSM (sort | reduction); the accumulation stays on `stream`
-  hipStream_t copy_stream = nullptr;   // the chunked copy of the host-pointer MSM (msm_host_single) and the resident-buffer uploads (mi355_buf_upload)
+  hipStream_t copy_stream = nullptr;   // the chunked copy of the host-pointer MSM (msm_host_sliced) and the resident-buffer uploads (mi355_buf_upload)
   // events (ctx_events below lists them once), all without timing
   MsmSlot msm_slot[2];
   hipEvent_t ev_fork = nullptr;
@@ -100,7 +108,6 @@ struct Ctx : mi355zk::Knobs {
   void *comm = nullptr;         // ncclComm_t of this device (mi355_init_multi with distinct devices)
   std::vector<const fe_t *> polys_stage;
   uint32_t msm_chunk_min_log = 23;   // mi355_msm_set_pipeline
-  int last_chunks = 1;
   std::map<std::string, Buf> ws;           // grow-only workspace arena, keyed by role
   std::map<std::string, NttPlan> ntt_plans;  // key = log_n | omega bytes
   int ntt_pins = 0;             // transforms in flight on the calling thread that hold pointers into ntt_plans: the optional tables are not reclaimed meanwhile (PlanPin, lib_ntt.hip)
@@ -108,7 +115,7 @@ struct Ctx : mi355zk::Knobs {
   bool profiling = false;
   std::vector<Span> spans;      // profiling: (name, start, stop) event pairs resolved after the stream is idle
   std::map<std::string, Prof> prof;
-  int last_c = 0, last_w = 0; uint64_t last_entries = 0; bool last_shared = false; int last_host_slices = 1;
+  MsmRunRecord run;             // how the last MSM on this slot ran (mi355_msm_last_plan / _last_run read slot 0's)
 };
 // The streams a context owns, in creation order, and every event it owns: init_ctx creates from these lists and destroy_ctx destroys from them, so a new member is named once.
 enum : unsigned { SYNC_COMPUTE = 1, SYNC_AUX = 2, SYNC_COPY = 4 };
@@ -144,7 +151,6 @@ extern thread_local Ctx *g_cur;
 #define g (*::mi355::g_cur)
 extern std::unordered_map<uint64_t, Srs> &g_srs;   // heap-allocated, never destroyed (no HIP calls from static destruction)
 extern uint64_t g_next_handle;
-extern int g_last_devices; extern const char *g_last_exchange;
 
 // t_slots_held: bit s is set while the CALLING THREAD works under slot s's lock -- it took the lock through one of the guards below, or it is a worker thread of a call
 // that did (SlotHeld).  mi355_buf_alloc, the one allocation path that runs without the lock, reads it to know whether reclaiming the optional NTT tables needs the lock first.
@@ -302,9 +308,6 @@ int launch_pow_table(fe_t *out, const fe_t &base, uint64_t step, uint32_t count)
 int launch_g1_decompress(const void *bytes_dev, void *affine_out_dev, uint64_t n, uint64_t base, unsigned long long *err_dev);
 // the two G2 points of a Processed params file, decoded on the host (64 bytes -> 128-byte G2Affine); false for a word that is no point of the twist
 bool g2_decode_host(const uint8_t in[64], void *g2affine_out);
-// window-cost model shared by the MSM launch code and mi355_srs_precompute
-constexpr int MSM_SCALAR_BITS = 255, MSM_MAX_C = 24;   // hard limit of the sorter (23 key bits); the automatic choices stop at g_proc.msm_auto_max_c
-double msm_cost(uint64_t n, int c, bool shared);
 
 // ---- small helpers shared by the transform entry points (lib_ntt.hip, lib_aux.hip)
 inline int check_ntt_args(const void *data, uint32_t log_n, const void *omega) {

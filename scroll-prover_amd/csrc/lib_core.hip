@@ -27,7 +27,6 @@ thread_local Ctx *g_cur = &g_ctx[0];
 // static destruction, after the HIP runtime's own exit handlers.  Device memory is only ever freed by mi355_srs_release / mi355_shutdown.
 std::unordered_map<uint64_t, Srs> &g_srs = *new std::unordered_map<uint64_t, Srs>();
 uint64_t g_next_handle = 1;
-int g_last_devices = 1; const char *g_last_exchange = "none";
 thread_local MsmOpts t_opts;
 thread_local uint32_t t_slots_held = 0;
 Rccl g_rccl;

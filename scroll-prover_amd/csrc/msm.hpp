@@ -31,6 +31,7 @@
 #include "fp_asm.hpp"
 #include "g1_29.hpp"
 #include "frscan.hpp"
+#include "msm_plan.hpp"   // the limits the launch planner shares with these kernels: MSM_SCALAR_BITS, SCAN_*, SORT_MAX_BINS, SORT_SPLIT_TMAX, FIXUP_HUGE_MIN, FIXUP_SLICES, TREE_PER_THREAD
 
 namespace zk {
 
@@ -242,7 +243,6 @@ __global__ void __launch_bounds__(256) k_msm_digits(PolyPtrs inl, const fe_t *co
 }
 
 // ---- 2. exclusive scan (three small kernels; the array has W * 2^(c-1) + 1 entries)
-constexpr uint32_t SCAN_BLOCK = 1024, SCAN_ITEMS = 4;  // 4096 per workgroup
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *lds, uint32_t &total) {
   // wave-level inclusive scan by shuffles, then across the 16 waves through LDS
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -298,8 +298,6 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_final(const uint32_t *__res
 //            -> pairs[] = (fine key << 32 | point index | sign), grouped by coarse region
 //   level 2: tiles inside each coarse region, bin = fine key (2^fb bins)             -> exact bucket offsets + sorted[]
 // Order inside a bucket is arbitrary (group addition commutes), so nothing needs to be stable.
-constexpr uint32_t SORT_MAX_BINS = 4096;
-constexpr uint32_t SORT_SPLIT_TMAX = 128;   // entries of the block-start table of k_sort_l1_scatter_split (coarse bins >> spare key bits, at most 2048 >> 4)
 struct SortPlan { uint32_t n, windows /* batch * W */, wpp /* W */, nb, fb, cb_bits, t1, t2, regions, shared, nshift /* ceil(log2 n): table row of an entry = payload >> nshift */; };   // shared = 1: all windows feed ONE bucket set (precomputed 2^(cw) P tables)
 
 // Per-tile bin bookkeeping shared by both scatter kernels (1024 threads): lstart[] = exclusive scan of the tile histogram,
@@ -562,7 +560,7 @@ __global__ void __launch_bounds__(256) k_msm_accumulate(const g1_affine_t *__res
 // ---- 5. fix-up of buckets that straddle thread boundaries.  Small spans are summed by one lane; a bucket that spans more than
 //         FIXUP_SERIAL_MAX accumulate-threads (skewed scalars: zeros/ones/small values, or the short top window) is queued and
 //         reduced by a whole workgroup (wavefront-shuffle tree + LDS) in k_msm_fixup_big.
-constexpr uint32_t FIXUP_SERIAL_MAX = 32, FIXUP_HUGE_MIN = 2048, FIXUP_SLICES = 64;   // SLICES <= 64: one wavefront folds the slice sums
+constexpr uint32_t FIXUP_SERIAL_MAX = 32;
 // The fix-up and the whole reduction tail stay in the 29-bit field (g1_xyzz29_add / _dbl): no conversion of the 144-byte records to the
 // saturated form (4 multiplications each) and the faster multiplier; records always hold valid accumulators (g1_29.hpp invariants).
 template <int Q = 1> __device__ __forceinline__ void fixup_take29(g1_xyzz29_t &acc, const g1_xyzz29_t *__restrict__ part, const int32_t *__restrict__ part_id, uint32_t t, uint32_t b) {
@@ -733,7 +731,6 @@ template <class G, int Q> __global__ void __launch_bounds__(128) k_msm_bucket_re
 // ---- 6b. per bucket set: tree-sum of the chunk results.  grid = (blocks, sets); a block of 256 lanes = 256 / Q logical threads folds up
 //          to (256 / Q) * TREE_PER_THREAD inputs (wavefront shuffles, then LDS across the 4 waves) into one output; launched repeatedly
 //          until one value per set is left.
-constexpr uint32_t TREE_PER_THREAD = 4;
 template <class G, int Q> __global__ void __launch_bounds__(256) k_msm_tree_sum(const typename G::rec_t *__restrict__ in, uint32_t in_per_set, typename G::rec_t *__restrict__ out, uint32_t out_per_set) {
   using rec_t = typename G::rec_t;
   __shared__ rec_t lds[4];

@@ -128,7 +128,7 @@ def test_g2_msm_at_size(zk, tiled, log_n, kind):
     sums = _class_sums(sc, PERIOD)
     want = expected(tiled, np.stack([cref.fr_mont(s) for s in sums]))
     assert (got == want).all()
-    if log_n == 20:   # a real windowed schedule: W = ceil(255 / c), the G1 plan rule (msm_shape); one entry per (scalar, window)
+    if log_n == 20:   # a real windowed schedule: W = ceil(255 / c), the G1 plan rule (plan_pass); one entry per (scalar, window)
         c, w, e = C.c_int(), C.c_int(), C.c_uint64()
         zk._capi.check(zk._capi.lib().mi355_msm_last_plan(C.byref(c), C.byref(w), C.byref(e)))
         assert c.value >= 8 and w.value == -(-255 // c.value) and e.value == n * w.value

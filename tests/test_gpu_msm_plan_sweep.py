@@ -5,7 +5,7 @@ Between 2^11 and 2^21 points the plan a caller gets by default changes its windo
 bins appear), the form of the per-bucket fix-up (quad -> four lanes -> one lane), the form of the running sums (quad -> one lane) and the number
 of level-1 sorter tiles.  The older tests reach those kernel forms by forcing c at n = 2048 (a nearly empty bucket set) or at powers of two.  Here:
 
-  * the window choice is restated below (msm_cost / choose_c / msm_shape); the lengths of the sweep are GENERATED from it -- both sides of every
+  * the window choice is restated in tests/msm_plan_common.py (msm_cost / choose_c / plan); the lengths of the sweep are GENERATED from it -- both sides of every
     length at which c changes -- and after every device run mi355_msm_last_plan / _last_run must report the restated (c, W, entries, shared);
   * the bases are independent points k_i G made on the device and verified through the oracle (gpu_common.device_points), with points whose
     coordinate words are adversarial at the sorter's tile edges and at the last index of every length, two identities and a pair P, -P;
@@ -36,83 +36,9 @@ P = pyref.P_MOD
 RINV_P = pow(pyref.MONT_R, -1, P)
 
 # ------------------------------------------------------------------------------------------------ the plan, restated
-# lib_msm.hip: msm_cost, choose_c, msm_shape, the fix-up choice of msm_enqueue and the chunking of msm_reduce_tail, with the defaults of
-# csrc/knobs.hpp.  A retune of the library changes THIS block; every length below follows from it.
-SCALAR_BITS, AUTO_MAX_C, SORT_FB, RECORD_BYTES, L1_TILE = 255, 22, 11, 144, 16384
-TAIL_COOP_MAX, FIXUP_LANES_MAX_LOG, REDUCE_CHAINS, REDUCE_MIN_CHUNK = 65536, 17, 131072, 4
-
-
-def windows(c):
-    return (SCALAR_BITS + c - 1) // c
-
-
-def log2_ceil(n):
-    return (n - 1).bit_length()
-
-
-def msm_cost(n, c, shared):
-    """in units of one bucket addition: the entries' share, the bucket reduction, the Horner tail a table-free MSM waits for"""
-    W, nb = float(windows(c)), float(1 << (c - 1))
-    return 1.18 * W * float(n) + 8.2 * nb * (1.0 if shared else W) + (0.0 if shared else 3.0e7)
-
-
-def choose_c(n):
-    best, best_c = 1e300, 8
-    for c in range(4, AUTO_MAX_C + 1):
-        if windows(c) * float(1 << (c - 1)) * RECORD_BYTES > 6.0e9:
-            continue
-        cost = msm_cost(n, c, False)
-        if cost < best:
-            best, best_c = cost, c
-    return best_c
-
-
-def table_c(n_hint):
-    """mi355_srs_precompute(handle, 0, 0): the cheapest shared-bucket window for MSMs of n_hint points"""
-    best, best_c = 1e300, 0
-    for c in range(4, AUTO_MAX_C + 1):
-        cost = msm_cost(n_hint, c, True)
-        if cost < best:
-            best, best_c = cost, c
-    return best_c
-
-
-def plan(n, M=1, tab_c=None):
-    """msm_shape for M polynomials of n scalars; tab_c: the window of the basis' tables (None: no tables, or tables switched off)"""
-    c, shared = choose_c(n), False
-    if tab_c is not None and msm_cost(n, tab_c, True) <= msm_cost(n, c, False) and (windows(tab_c) << log2_ceil(n)) < (1 << 31):
-        c, shared = tab_c, True
-    W, kb = windows(c), c - 1
-    fb = min(kb, SORT_FB)
-    if kb - fb > 11:
-        fb = kb - 11
-    sets = M * (1 if shared else W)
-    buckets = sets << kb
-    fixup = "quad" if buckets * 4 <= TAIL_COOP_MAX else "four lanes" if buckets <= (1 << FIXUP_LANES_MAX_LOG) else "one lane"
-    nb, chunk = 1 << kb, 64
-    while chunk > nb:
-        chunk >>= 1
-    while chunk > REDUCE_MIN_CHUNK and (nb // chunk) * sets < REDUCE_CHAINS:
-        chunk >>= 1
-    sums = "quad" if (nb // chunk) * sets <= TAIL_COOP_MAX else "one lane"
-    return {"n": n, "c": c, "W": W, "entries": M * n * W, "shared": shared, "fb": fb, "cb_bits": kb - fb, "buckets": buckets, "fixup": fixup,
-            "sums": sums, "tiles1": -(-n // L1_TILE)}
-
-
-def boundaries(lo, hi):
-    """every n in (lo, hi] with choose_c(n) != choose_c(n - 1) (the choice is a step function of n: bisection between the steps)"""
-    out, n = [], lo
-    while choose_c(n) != choose_c(hi):
-        a, b = n, hi
-        while b - a > 1:
-            m = (a + b) // 2
-            if choose_c(m) == choose_c(n):
-                a = m
-            else:
-                b = m
-        out.append(b); n = b
-    return out
-
+# tests/msm_plan_common.py restates csrc/msm_plan.hpp (and tests/test_msm_plan_on_host.py holds it against the C++ on the CPU).  A retune of the library changes THAT
+# module; every length below follows from it.
+from tests.msm_plan_common import L1_TILE, boundaries, choose_c, log2_ceil, plan, table_c, windows  # noqa: E402
 
 BOUNDARIES = boundaries(1 << 11, 1 << 19)            # both sides of each run under three scalar kinds
 BIG_BOUNDARIES = boundaries(1 << 19, 1 << 21)        # one case each: the oracle needs seconds there

@@ -1,4 +1,4 @@
-"""time one commitment with window tables for every table width c: calibration of msm_cost() in capi.hip.
+"""time one commitment with window tables for every table width c: calibration of msm_cost() in csrc/msm_plan.hpp.
     python tools/bench_window_choice.py [k ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
