@@ -437,6 +437,84 @@ int mi355_g_to_lagrange_dev(const void *g_affine_dev, void *g_lagrange_affine_de
 int mi355_srs_downsize(uint64_t g_handle, uint32_t k, const void *omega_inv, const void *n_inv, uint64_t *g_lagrange_handle_out);
 int mi355_srs_read_host(uint64_t handle, uint64_t offset, uint64_t n, void *out_affine_host);
 
+/* ---- the prover and the verifier behind the C-ABI: what the operators above exist for, one FFI call each.  The reference reaches halo2_proofs::plonk::create_proof once
+ * per layer and verifies what comes out [REF integration/src/prove.rs:36-43,50-53,67,75-80,95-97]; a `halo2_proofs` fork calls the entry points below instead of transcribing
+ * that flow into Rust (rust_shim/create_proof_ffi.rs; INTEGRATION.md "tier C without a transcription").  They wrap the C++ of include/mi355zk_plonk*.hpp, mi355zk_transcript.hpp
+ * and mi355zk_plonk_verify.hpp -- plonk::keygen, create_proof, check_witness, verify_proof, verify_proofs, aggregate -- unchanged: the same device calls, the same bytes.
+ *
+ * Objects are uint64_t HANDLES of five kinds: protocol, circuit, proving key, options, record.  Handles come from one counter and a value is never issued twice; a freed,
+ * never-issued or wrong-kind handle is MI355_EBADARG with the expected kind in mi355_last_error(), never a dereference.  mi355_plonk_free takes any kind.  A circuit and a key
+ * KEEP THEIR PROTOCOL ALIVE: freeing the protocol's handle first is allowed (the handle dies at once, the memory with its last user).  A key does not refer to the circuit it
+ * was made from.  Freeing a key returns its device blocks to the pool (mi355_buf_trim gives them back to HIP).  An options handle of 0 means the defaults everywhere.
+ * Errors: no exception crosses; halo2::Error keeps its code, std::bad_alloc is MI355_EOOM, every complaint about an argument, a protocol or a layout is MI355_EBADARG, the
+ * message in the calling thread's mi355_last_error().  The entry points that compute on the device (keygen, create_proof, check_witness, verification without host_only) look
+ * the device up first: without one they are MI355_ENODEVICE whatever their other arguments.
+ * Byte outputs (out, cap, bytes_out): *bytes_out receives the size; cap == 0 asks for the size alone; 0 < cap < size is MI355_EBADARG and nothing is written.
+ * Threading: an object is used by one thread at a time; distinct objects may be used from distinct threads (keygen and proofs of different keys run concurrently as far as the
+ * per-device locks above allow); the verification entry point serialises on one mutex inside the library (the verifier's headers keep their phase clocks in function statics).
+ *
+ * PlonkProtocol: snark-verifier's JSON of a circuit's constraint system, as [REF release-v0.13.1/chunk.protocol] and what `compile` serialises (mi355zk_plonk_protocol.hpp);
+ * from text (len bytes, no terminator needed) or from a file.  Malformed text or a protocol outside the recognised shape: MI355_EBADARG, nothing issued.                     */
+int mi355_plonk_protocol_from_json(const char *json, uint64_t len, uint64_t *protocol_out);
+int mi355_plonk_protocol_from_file(const char *path, uint64_t *protocol_out);
+/* one figure of the protocol by name: k, n, layer (~0 when the file names none), num_preprocessed, num_instance, num_advice, num_lookups, num_perm_columns, num_perm_chunks,
+ * num_gates, num_witness (all phases), num_commitments, blind, usable, quotient_pieces, extended_k, num_evaluations, num_queries, lookup_bits, proof_bytes_poseidon (also the
+ * Blake2b layout), proof_bytes_evm, has_initial_state, has_accumulator.  An unknown field: MI355_EBADARG naming it.                                                          */
+int mi355_plonk_protocol_info(uint64_t protocol, const char *field, uint64_t *value_out);
+int mi355_plonk_free(uint64_t handle);
+/* plonk::Circuit, owned by the library: what keygen assigns and `synthesize` fills in the reference [EXT-recalled halo2_proofs plonk/keygen.rs, plonk/prover.rs].  _new: every
+ * column present and zero, no copy constraints, no instance values.  _synthetic: plonk::build_circuit(protocol, CircuitOptions{seed, blind_seed, fill, assign_density, flags
+ * bit 0 pinned, bit 1 zero_blinding}) -- a satisfying instance for the protocol; the same arguments give the same instance.
+ * _set / _get move one part, named by `what` (index = which column / lookup / permutation chunk; 0 where there is one).  Words are 32-byte Fr, Montgomery, as everywhere here:
+ *   preprocessed  n words, Lagrange values of fixed column `index` (_get also answers for the sigma columns, derived from the copies; _set refuses them)
+ *   advice, m     n words                    m_counts      n x uint32_t, the multiplicities as integers
+ *   m_blind, z_blind, phi_blind   `blind` words (protocol_info)          random_poly   n words, coefficients
+ *   instances     at most num_instance words                             copies        records of four uint64_t (position a, row a, position b, row b): two cells of
+ *                                                                                      the permutation's columns, in the protocol's order, that must be equal; replaces the list
+ * A size that does not match the protocol, an index out of range, a cell outside the permutation: MI355_EBADARG, the circuit unchanged.                                      */
+int mi355_plonk_circuit_new(uint64_t protocol, uint64_t *circuit_out);
+int mi355_plonk_circuit_synthetic(uint64_t protocol, uint64_t seed, uint64_t blind_seed, double fill, double assign_density, uint32_t flags, uint64_t *circuit_out);
+int mi355_plonk_circuit_set(uint64_t circuit, const char *what, uint32_t index, const void *data, uint64_t bytes);
+int mi355_plonk_circuit_get(uint64_t circuit, const char *what, uint32_t index, void *out, uint64_t cap, uint64_t *bytes_out);
+/* plonk::keygen = halo2's keygen_vk + keygen_pk [EXT-recalled halo2_proofs plonk/keygen.rs]: the fixed and sigma columns committed on srs_g_lagrange (a handle of
+ * mi355_srs_register_*), the proving key resident in HBM until its handle is freed.  flags bit 0: the extended-coset parts stay resident too; bit 1: device_sigma (the sigma
+ * columns from one mi355_fr_permutation_sigma_dev call).  devices: as ProofOptions::devices of the proofs to come.  The circuit must belong to `protocol`.
+ * _pk_vk: the verifying key serialised like [REF release-v0.13.1/vk_chunk.vkey] (u32 BE k | u32 BE fixed columns | 32-byte compressed commitments).                          */
+int mi355_plonk_keygen(uint64_t protocol, uint64_t circuit, uint64_t srs_g_lagrange, uint32_t flags, int devices, uint64_t *pk_out);
+int mi355_plonk_pk_vk(uint64_t pk, void *out, uint64_t cap, uint64_t *bytes_out);
+/* the fields of plonk::ProofOptions, VerifyOptions and CheckOptions by name, values as text: integers in decimal, booleans 0 / 1 / true / false, transcript = blake2b |
+ * poseidon | evm | by_layer, rng_key = 64 hexadecimal digits (the 32 key bytes in order), initial_state = 64 hexadecimal digits (a big-endian integer, reduced mod r: the
+ * verifier's first transcript scalar).  Names: devices threads commit_batch upload_threads early_intt sparse_uploads packed_multiplicities device_multiplicities
+ * multiplicity_rule_last check_witness device_randomness rng_key rng_key_from_os coset_group_polys transcript | check_accumulator accumulator host_only device_transcript
+ * initial_state | cap theta_seed.  What is not set keeps the default of its struct.  An unknown name, or a value that does not parse or is out of range: MI355_EBADARG naming it. */
+int mi355_plonk_options_new(uint64_t *opts_out);
+int mi355_plonk_options_set(uint64_t opts, const char *name, const char *value);
+/* halo2_proofs::plonk::create_proof [REF integration/src/prove.rs:37,67,96] = plonk::create_proof over the key and the circuit's witness; srs_g / srs_g_lagrange: the two bases
+ * of ParamsKZG.  The proof (the reference's byte layout, protocol_info's proof_bytes_* long) goes to proof_out; a cap below that size is refused before any work.  record_out
+ * (optional) receives a record handle (mi355_plonk_record_json).  With check_witness set and a failing witness: MI355_EBADARG, the first failure in the message, every failure
+ * in the record, nothing written to proof_out.
+ * _check_witness = MockProver::verify on the device (plonk::check_witness).  A failing witness is NOT an error, as for mi355_fr_copy_check_dev: MI355_OK, the number of
+ * reported failures in *n_failures_out, the failures in the record.                                                                                                          */
+int mi355_plonk_create_proof(uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t pk, uint64_t circuit, uint64_t opts, void *proof_out, uint64_t cap, uint64_t *bytes_out, uint64_t *record_out);
+int mi355_plonk_check_witness(uint64_t pk, uint64_t circuit, uint64_t opts, uint64_t *n_failures_out, uint64_t *record_out);
+/* the verifier of [REF integration/src/prove.rs:50-53,75-80] and the aggregator's native verification behind gen_batch_proof [REF integration/src/prove.rs:67] over n proofs.
+ * mode 0: plonk::verify_proofs (one decompression, one segmented MSM, one pairing call); 1: plonk::verify_proof in a loop; 2: plonk::aggregate with its pairing; 3: aggregate,
+ * fold only (g2 / s_g2 may be NULL).  Per proof i: its protocol handle; vk_bytes[i] / vk_len[i] the .vkey, NULL (or vk_bytes == NULL) = the protocol file's own preprocessed
+ * commitments; instances[i] = n_instances[i] words; proofs[i] = proof_len[i] bytes.  g2, s_g2: 128-byte G2Affine of ParamsKZG; s_g2_is_negated != 0: s_g2 holds -[s]g2 already.
+ * opts applies to every proof.  A REJECTED proof is not an error: MI355_OK, ok_out[i] = 0, the named failure (proof_length, non_canonical_scalar, invalid_point,
+ * accumulator_limb, pairing, ...) in the record.  Modes 2 and 3 judge the proofs together: ok_out[i] = 1 when the aggregation stands and proof i passed its own part.
+ * host_only (modes 0 and 1) stops every proof after its (scalars, points) list and needs no device.                                                                          */
+int mi355_plonk_verify_proofs(uint32_t n, const uint64_t *protocols, const void *const *vk_bytes, const uint64_t *vk_len, const void *const *instances, const uint64_t *n_instances,
+                              const void *const *proofs, const uint64_t *proof_len, const void *g2, const void *s_g2, uint32_t s_g2_is_negated, uint64_t opts, uint32_t mode,
+                              uint8_t *ok_out, uint64_t *record_out);
+/* a record as strict JSON text (no terminator; cap == 0 asks for the size).  "kind": "proof" -- ProofResult: proof_bytes, transcript, total_ms, step_ms {...}, msm, intt,
+ * coset_ntt, gate_launches, evals, rotation_sets, plan_launches / _terms / _tmps / _constraints / _prefix_groups, peak_hbm_bytes, hbm_total_bytes, sparse_columns,
+ * packed_columns, witness_link_bytes, coset_groups, coset_retransforms, random_ms, multiplicity_ms; after a refused witness "ok": false, "error" and "failures".
+ * "kind": "check" -- n_failures, failures [{kind, index, row, count, col_a, col_b, row_b, message}].  "kind": "verify" -- mode, device_calls, proofs [{ok, error, detail,
+ * host_only, challenges, numerator_at_x, msm {scalars, points, result, w_prime}, has_accumulator, pairing}] with field elements and coordinates as 64 hexadecimal digits
+ * (big-endian, canonical), and for modes 2 and 3 "aggregate" {ok, error, detail, accumulators, r, lhs, rhs, limbs, pairing}.                                                 */
+int mi355_plonk_record_json(uint64_t record, char *out, uint64_t cap, uint64_t *bytes_out);
+
 /* ---- measurement hooks (bench.py): HIP-event timing of the kernels of the most recent MSM / NTT call.       */
 int mi355_profile_enable(int on);
 /* name in {"msm_total","msm_digits","msm_sort","msm_accumulate","msm_reduce","ntt_total","ntt_pass","g1_decompress","g1_compress"}; returns the

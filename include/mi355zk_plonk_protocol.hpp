@@ -15,6 +15,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <map>
 #include <sstream>
@@ -51,25 +52,28 @@ struct Value {
 struct Parser {
   const std::string &t; size_t p = 0;
   explicit Parser(const std::string &text) : t(text) {}
+  char cur() const { return p < t.size() ? t[p] : '\0'; }   // past the end reads as NUL: truncated text fails with a message, it is never indexed
   void ws() { while (p < t.size() && (t[p] == ' ' || t[p] == '\n' || t[p] == '\t' || t[p] == '\r')) p++; }
-  [[noreturn]] void fail(const char *what) { throw std::invalid_argument(std::string("json: ") + what + " at offset " + std::to_string(p)); }
-  Value parse() {
+  [[noreturn]] void fail(const char *what) { throw std::invalid_argument(std::string("json: ") + what + " at offset " + std::to_string(std::min(p, t.size()))); }
+  void word(const char *w) { const size_t n = std::strlen(w); if (t.compare(p, n, w) != 0) fail("unexpected character"); p += n; }
+  Value parse(int depth = 0) {
+    if (depth > 4096) fail("nesting too deep");
     ws(); if (p >= t.size()) fail("unexpected end");
     Value v; const char c = t[p];
     if (c == '{') {
       v.type = Value::OBJ; p++; ws();
-      if (t[p] == '}') { p++; return v; }
-      for (;;) { ws(); Value k = parse(); if (k.type != Value::STR) fail("object key"); ws(); if (t[p++] != ':') fail("':'"); v.obj.emplace_back(k.s, parse()); ws(); if (t[p] == ',') { p++; continue; } if (t[p] == '}') { p++; return v; } fail("',' or '}'"); }
+      if (cur() == '}') { p++; return v; }
+      for (;;) { ws(); Value k = parse(depth + 1); if (k.type != Value::STR) fail("object key"); ws(); if (cur() != ':') fail("':'"); p++; v.obj.emplace_back(k.s, parse(depth + 1)); ws(); if (cur() == ',') { p++; continue; } if (cur() == '}') { p++; return v; } fail("',' or '}'"); }
     }
     if (c == '[') {
       v.type = Value::ARR; p++; ws();
-      if (t[p] == ']') { p++; return v; }
-      for (;;) { v.arr.push_back(parse()); ws(); if (t[p] == ',') { p++; continue; } if (t[p] == ']') { p++; return v; } fail("',' or ']'"); }
+      if (cur() == ']') { p++; return v; }
+      for (;;) { v.arr.push_back(parse(depth + 1)); ws(); if (cur() == ',') { p++; continue; } if (cur() == ']') { p++; return v; } fail("',' or ']'"); }
     }
-    if (c == '"') { v.type = Value::STR; p++; while (p < t.size() && t[p] != '"') { if (t[p] == '\\') p++; v.s.push_back(t[p++]); } p++; return v; }
-    if (c == 'n') { p += 4; return v; }
-    if (c == 't') { v.type = Value::BOOL; v.b = true; p += 4; return v; }
-    if (c == 'f') { v.type = Value::BOOL; p += 5; return v; }
+    if (c == '"') { v.type = Value::STR; p++; while (p < t.size() && t[p] != '"') { if (t[p] == '\\') p++; if (p >= t.size()) break; v.s.push_back(t[p++]); } if (p >= t.size()) fail("unterminated string"); p++; return v; }
+    if (c == 'n') { word("null"); return v; }
+    if (c == 't') { v.type = Value::BOOL; v.b = true; word("true"); return v; }
+    if (c == 'f') { v.type = Value::BOOL; word("false"); return v; }
     if (c == '-' || (c >= '0' && c <= '9')) {
       v.type = Value::INT; if (c == '-') { v.negative = true; p++; }
       while (p < t.size() && t[p] >= '0' && t[p] <= '9') v.u = v.u * 10 + (uint64_t)(t[p++] - '0');
@@ -188,10 +192,14 @@ struct Protocol {
   bool is_pre(uint32_t p) const { return p < num_pre; }
   bool is_instance(uint32_t p) const { return p >= inst0 && p < wit0; }
 
-  void load(const std::string &path) {
-    const json::Value file = json::parse_file(path);
+  void load(const std::string &path) { load_value(json::parse_file(path)); }
+  // the same from the text itself (what snark-verifier's `compile` serialises): the caller need not write a file
+  void load_text(const std::string &text) { json::Parser parser(text); const json::Value file = parser.parse(); parser.ws(); if (parser.p < text.size()) parser.fail("text behind the value"); load_value(file); }
+  void load_value(const json::Value &file) {
+    if (file.type != json::Value::OBJ) throw std::invalid_argument("protocol: a JSON object expected");
     const json::Value &root = file.find("protocol") ? file.at("protocol") : file;   // the golden fixtures wrap the protocol with their provenance
     const json::Value &d = root.at("domain");
+    if (d.at("k").u < 2 || d.at("k").u > 28) throw std::invalid_argument("protocol: domain.k must lie in [2, 28]");
     k = (uint32_t)d.at("k").u; n = uint64_t(1) << k;
     omega = fr_from_json(d.at("gen")); omega_inv = fr_from_json(d.at("gen_inv")); n_inv = fr_from_json(d.at("n_inv"));
     { const halo2::EvaluationDomain dom(2, k); if (!(dom.omega == omega) || !(dom.omega_inv == omega_inv) || !(dom.ifft_divisor == n_inv)) throw std::invalid_argument("protocol: domain constants differ from EvaluationDomain::new"); }

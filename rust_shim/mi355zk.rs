@@ -114,6 +114,26 @@ extern "C" {
     pub fn mi355_fr_kate_division_dev(dst_dev: *mut c_void, poly_dev: *const c_void, n: u64, z: *const c_void) -> c_int;
     pub fn mi355_eval_polynomial_batch_dev(polys_dev: *const *const c_void, batch: u32, n: u64, points: *const c_void, out_fr_host: *mut c_void) -> c_int;
     pub fn mi355_eval_polynomial_dev(poly_dev: *const c_void, n: u64, point: *const c_void, out_fr_host: *mut c_void) -> c_int;
+    // ---- the prover and the verifier behind the C-ABI (include/mi355zk.h, mi355_plonk_*): objects are u64 handles; create_proof_ffi.rs is the flow over them
+    pub fn mi355_plonk_protocol_from_json(json: *const c_char, len: u64, protocol_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_protocol_from_file(path: *const c_char, protocol_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_protocol_info(protocol: u64, field: *const c_char, value_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_free(handle: u64) -> c_int;
+    pub fn mi355_plonk_circuit_new(protocol: u64, circuit_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_circuit_synthetic(protocol: u64, seed: u64, blind_seed: u64, fill: f64, assign_density: f64, flags: u32, circuit_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_circuit_set(circuit: u64, what: *const c_char, index: u32, data: *const c_void, bytes: u64) -> c_int;
+    pub fn mi355_plonk_circuit_get(circuit: u64, what: *const c_char, index: u32, out: *mut c_void, cap: u64, bytes_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_keygen(protocol: u64, circuit: u64, srs_g_lagrange: u64, flags: u32, devices: c_int, pk_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_pk_vk(pk: u64, out: *mut c_void, cap: u64, bytes_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_options_new(opts_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_options_set(opts: u64, name: *const c_char, value: *const c_char) -> c_int;
+    pub fn mi355_plonk_create_proof(srs_g: u64, srs_g_lagrange: u64, pk: u64, circuit: u64, opts: u64, proof_out: *mut c_void, cap: u64, bytes_out: *mut u64,
+                                    record_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_check_witness(pk: u64, circuit: u64, opts: u64, n_failures_out: *mut u64, record_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_verify_proofs(n: u32, protocols: *const u64, vk_bytes: *const *const c_void, vk_len: *const u64, instances: *const *const c_void,
+                                     n_instances: *const u64, proofs: *const *const c_void, proof_len: *const u64, g2: *const c_void, s_g2: *const c_void,
+                                     s_g2_is_negated: u32, opts: u64, mode: u32, ok_out: *mut u8, record_out: *mut u64) -> c_int;
+    pub fn mi355_plonk_record_json(record: u64, out: *mut c_char, cap: u64, bytes_out: *mut u64) -> c_int;
 }
 
 /// Offload threshold: below this the PCIe copy + launch latency lose against rayon (env MI355_MSM_MIN_LOGN / MI355_NTT_MIN_LOGN).

@@ -16,3 +16,4 @@ from . import halo2  # noqa: F401
 from . import distributed  # noqa: F401
 from . import protocols  # noqa: F401
 from . import replay  # noqa: F401
+from . import prover  # noqa: F401

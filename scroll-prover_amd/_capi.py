@@ -117,6 +117,24 @@ SIGNATURES = {
     "mi355_debug_ws_read": (_int, [C.c_char_p, _u64, _vp, _u64]),
     "mi355_msm_last_plan": (_int, [C.POINTER(_int), C.POINTER(_int), C.POINTER(_u64)]),
     "mi355_msm_last_run": (_int, [C.POINTER(_int), C.POINTER(C.c_char_p), C.POINTER(_int), C.POINTER(_int)]),
+    # the prover and the verifier behind the C-ABI (prover.py): objects are uint64 handles
+    "mi355_plonk_protocol_from_json": (_int, [C.c_char_p, _u64, C.POINTER(_u64)]),
+    "mi355_plonk_protocol_from_file": (_int, [C.c_char_p, C.POINTER(_u64)]),
+    "mi355_plonk_protocol_info": (_int, [_u64, C.c_char_p, C.POINTER(_u64)]),
+    "mi355_plonk_free": (_int, [_u64]),
+    "mi355_plonk_circuit_new": (_int, [_u64, C.POINTER(_u64)]),
+    "mi355_plonk_circuit_synthetic": (_int, [_u64, _u64, _u64, C.c_double, C.c_double, _u32, C.POINTER(_u64)]),
+    "mi355_plonk_circuit_set": (_int, [_u64, C.c_char_p, _u32, _vp, _u64]),
+    "mi355_plonk_circuit_get": (_int, [_u64, C.c_char_p, _u32, _vp, _u64, C.POINTER(_u64)]),
+    "mi355_plonk_keygen": (_int, [_u64, _u64, _u64, _u32, _int, C.POINTER(_u64)]),
+    "mi355_plonk_pk_vk": (_int, [_u64, _vp, _u64, C.POINTER(_u64)]),
+    "mi355_plonk_options_new": (_int, [C.POINTER(_u64)]),
+    "mi355_plonk_options_set": (_int, [_u64, C.c_char_p, C.c_char_p]),
+    "mi355_plonk_create_proof": (_int, [_u64, _u64, _u64, _u64, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "mi355_plonk_check_witness": (_int, [_u64, _u64, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "mi355_plonk_verify_proofs": (_int, [_u32, C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64), _vp, _vp, _u32, _u64, _u32,
+                                         C.POINTER(C.c_uint8), C.POINTER(_u64)]),
+    "mi355_plonk_record_json": (_int, [_u64, _vp, _u64, C.POINTER(_u64)]),
 }
 
 

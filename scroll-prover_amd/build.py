@@ -1,7 +1,8 @@
 """build.py -- compiles libmi355zk.so for gfx950 with hipcc (in-tree, next to this file).
 
-The library is five translation units (csrc/lib_core|lib_msm|lib_ntt|lib_aux|lib_pairing.hip) compiled in parallel and linked; a change to one
-kernel family rebuilds one unit.  Staleness is decided by CONTENT (sha256 of every file a unit includes + the flags), not by mtimes, so a
+The library is six translation units (csrc/lib_core|lib_msm|lib_ntt|lib_aux|lib_pairing.hip and lib_plonk.cpp) compiled in parallel and linked; a change to one
+kernel family rebuilds one unit.  lib_plonk is host code only (the mi355_plonk_* entry points over include/mi355zk_plonk*.hpp): its hash covers those headers through
+the same include closure, and it is compiled with hidden visibility so that the headers' inline C++ stays private to the library.  Staleness is decided by CONTENT (sha256 of every file a unit includes + the flags), not by mtimes, so a
 copied tree (the GPU box's snapshot) never rebuilds what was built here.
 """
 from __future__ import annotations
@@ -17,7 +18,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libmi355zk.so")
-UNITS = ["lib_core", "lib_msm", "lib_ntt", "lib_aux", "lib_pairing"]
+UNITS = ["lib_core", "lib_msm", "lib_ntt", "lib_aux", "lib_pairing", "lib_plonk"]
+# lib_plonk is HOST code (compiled as plain C++: the public headers then take their host forms, as in the programs under tests/cpp/) and exports its extern "C" functions only:
+# those programs compile the same header-only C++ and must not share its inline functions' statics with the library
+HOST_UNITS = {"lib_plonk": ["-x", "c++", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-pthread"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DNDEBUG", "-Wno-unused-result"]
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
@@ -34,10 +38,18 @@ def _closure(path: str, seen: dict) -> None:
         _closure(os.path.join(os.path.dirname(path), inc), seen)
 
 
+def _unit_source(unit: str) -> str:
+    return os.path.join(CSRC, unit + (".cpp" if unit in HOST_UNITS else ".hip"))
+
+
+def _unit_flags(unit: str) -> list:
+    return [f for f in FLAGS if not f.startswith("--offload-arch")] + HOST_UNITS[unit] if unit in HOST_UNITS else list(FLAGS)
+
+
 def _unit_hash(unit: str, extra_flags) -> str:
     seen: dict = {}
-    _closure(os.path.join(CSRC, unit + ".hip"), seen)
-    h = hashlib.sha256(" ".join(FLAGS + list(extra_flags)).encode())
+    _closure(_unit_source(unit), seen)
+    h = hashlib.sha256(" ".join(_unit_flags(unit) + list(extra_flags)).encode())
     for p in sorted(seen):
         h.update(os.path.relpath(p, HERE).encode()); h.update(seen[p])
     return h.hexdigest()
@@ -75,7 +87,7 @@ def build(force: bool = False, verbose: bool = False, lib: str = LIB, extra_flag
     def compile_unit(unit: str) -> str:
         obj = os.path.join(objdir, unit + ".o")
         if force or _stale(unit, objdir, extra_flags):
-            cmd = [hipcc] + FLAGS + extra_flags + ["-c", os.path.join(CSRC, unit + ".hip"), "-o", obj]
+            cmd = [hipcc] + _unit_flags(unit) + extra_flags + ["-c", _unit_source(unit), "-o", obj]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.check_call(cmd)
