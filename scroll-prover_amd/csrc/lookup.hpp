@@ -22,20 +22,19 @@
 #include "fp.hpp"
 
 namespace zk {
-#ifdef __HIPCC__
-
 constexpr uint32_t LK_EMPTY = 0xffffffffu;   // a free slot (table rows are < 2^32 - 1)
-constexpr uint32_t LK_THREADS = 256;
 constexpr int LK_ROUNDS = 4;                 // ballot-combined groups per 64 rows, after the hot row
+constexpr uint32_t LK_HOT_MIN = 16;          // the smallest group of one block that may become the hot row
 
-__device__ __forceinline__ bool lk_eq(const fe_t &a, const fe_t &b) {
+// host code sees the comparison and the hash too (tests/hostcheck/lookup_hash_main.cpp places keys in chosen slots with them)
+ZK_HD bool lk_eq(const fe_t &a, const fe_t &b) {
   uint32_t d = 0;
 #pragma unroll
   for (int k = 0; k < 8; k++) d |= a.l[k] ^ b.l[k];
   return d == 0;
 }
 // all 256 bits mixed (a range table in Montgomery form differs anywhere in the word), then the splitmix64 finaliser
-__device__ __forceinline__ uint32_t lk_hash(const fe_t &v, uint32_t mask) {
+ZK_HD uint32_t lk_hash(const fe_t &v, uint32_t mask) {
   uint64_t h = ((uint64_t)v.l[1] << 32 | v.l[0]);
   h = (h ^ (h >> 31)) * 0x9E3779B97F4A7C15ull ^ ((uint64_t)v.l[3] << 32 | v.l[2]);
   h = (h ^ (h >> 29)) * 0xBF58476D1CE4E5B9ull ^ ((uint64_t)v.l[5] << 32 | v.l[4]);
@@ -43,6 +42,10 @@ __device__ __forceinline__ uint32_t lk_hash(const fe_t &v, uint32_t mask) {
   h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull; h = (h ^ (h >> 27)) * 0x94D049BB133111EBull; h ^= h >> 31;
   return (uint32_t)h & mask;
 }
+
+#ifdef __HIPCC__
+
+constexpr uint32_t LK_THREADS = 256;
 
 // slots: mask + 1 entries (a power of two >= 2 x rows), LK_EMPTY on entry
 template <bool LAST> __global__ void __launch_bounds__(LK_THREADS) k_lk_insert(const fe_t *__restrict__ table, uint64_t rows, uint32_t *slots, uint32_t mask) {
@@ -90,7 +93,7 @@ __global__ void __launch_bounds__(LK_THREADS) k_lk_probe(const fe_t *__restrict_
       const uint32_t lr = __shfl(row, lead);
       const uint64_t m = __ballot(row == lr) & act;
       const uint32_t c = (uint32_t)__popcll(m);
-      if (c >= 16 && hot_cnt < c) {   // a bigger group than the held one: it becomes the hot row, the old one is added
+      if (c >= LK_HOT_MIN && hot_cnt < c) {   // a bigger group than the held one: it becomes the hot row, the old one is added
         if (hot_cnt && lane == (uint32_t)lead) atomicAdd(&cnt[hot], hot_cnt);
         hot = lr; hot_cnt = c;
       } else if (lane == (uint32_t)lead) atomicAdd(&cnt[lr], c);

@@ -2,7 +2,7 @@
 
   * mi355_fr_permutation_sigma_dev (through halo2.permutation_sigma) against the definition: sigma[j][r] = delta^j' omega^r' for (j', r') = mapping[j][r], the words
     computed from Python integers (tests/perm_common.py sigma_words, oracle.pyref's constants), EVERY word of every column, at (log_n, n_cols) = (1, 1), (4, 3), (10, 7),
-    (13, 2), (16, 5) and once at (20, 8).  Mappings come from halo2::PermutationAssembly (the C++ one, which tests/test_permutation_sigma_surface.py holds equal to
+    (13, 2), (16, 5), (4, 17), (6, 33) (more columns than one tile of k_perm_identity) and once at (20, 8).  Mappings come from halo2::PermutationAssembly (the C++ one, which tests/test_permutation_sigma_surface.py holds equal to
     the Python one): no copies, 2-cycles, cycles of 3 and 17 across columns, one cycle through a whole column, a cycle through (0, 0), (last column, n - 1) and the
     rows next to every power of two (where the high / low split of the omega table could go wrong), lists of 1, 255, 256, 257 and n_cols * n overrides -- every kind
     the size has the cells for.  Two calls give the same words; count == 0 equals distribute_powers of the constant column delta^j.
@@ -100,7 +100,7 @@ def run(dev, n_cols, log_n, mapping, cells=None, images=None, trusted=False):
     return cols, len(cells)
 
 
-SIZES = [(1, 1), (4, 3), (10, 7), (13, 2), (16, 5)]
+SIZES = [(1, 1), (4, 3), (10, 7), (13, 2), (16, 5), (4, 17), (6, 33)]   # the last two: a second and a third column tile of k_perm_identity (PERM_COL_TILE = 16), both clamped
 
 
 @pytest.mark.parametrize("log_n,n_cols", SIZES)
