@@ -41,7 +41,17 @@ def gate_indices(pr):
 
 class Reference:
     def __init__(self, directory):
-        self.inp, self.man = plonk.ProofInputs.load(directory)
+        self._set(*plonk.ProofInputs.load(directory))
+
+    @classmethod
+    def from_inputs(cls, inp):
+        """the same definition over a plonk.ProofInputs that is already in memory (plonk_capi_common.proof_inputs: the columns read back through circuit_get)"""
+        ref = cls.__new__(cls)
+        ref._set(inp, None)
+        return ref
+
+    def _set(self, inp, man):
+        self.inp, self.man = inp, man
         pr = self.pr = self.inp.pr
         n = pr.n
         inst = list(self.inp.instances) + [0] * (n - len(self.inp.instances))
