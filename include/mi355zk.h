@@ -203,6 +203,19 @@ int mi355_msm_g1_segmented_host(const void *bases_affine_host, const void *scala
  * jobs == 0 launches nothing.  No CPU fallback (MI355_ENODEVICE).                                                                                                    */
 int mi355_poseidon_transcripts_host(const void *words_host, const uint64_t *word_offsets_host, const uint32_t *squeeze_at_host, const uint64_t *squeeze_offsets_host,
                                     uint32_t jobs, void *challenges_out_host);
+/* ONE STRAIGHT-LINE PROGRAM OVER Fr, RUN FOR MANY JOBS in one launch: the scalar side of the same batch of verifiers behind gen_batch_proof [REF integration/src/prove.rs:67] --
+ * x^n, the Lagrange values at x, the numerator tree at x, h(x) and the SHPLONK scalars are, for one protocol, one fixed sequence of field operations on the proof's challenges,
+ * evaluations and instances (plonk::verify_proofs / plonk::aggregate with VerifyOptions::device_scalars; include/mi355zk_plonk_scalar.hpp compiles the sequence).
+ * Registers: n_regs words of 32 B (Fr, Montgomery, fully reduced).  [0, n_consts) = consts, shared by every job; [n_consts, n_consts + n_inputs) = job j's inputs
+ * inputs[j * n_inputs ..]; the rest are temporaries, undefined until written.  An instruction is four u32 words (op, dst, a, b): 0 ADD, 1 SUB, 2 MUL (dst = a op b);
+ * 3 SQRN (dst = a^(2^b), b an immediate <= 64); 4 INV (dst = 1 / a; zero gives zero and sets bit 0 of the job's flag word); 5 NZ (sets flag bit b, an immediate in 1 .. 31,
+ * when a == 0; writes no register, dst is ignored).  dst may alias an operand.  outputs[j * n_outputs + t] = register out_regs[t] of job j; flags_out[j] = its flag word.
+ * One lane per job, the program read as wave-uniform data: the call costs one job's latency whatever `jobs` is.  Kernel time reports as "fr_program" in mi355_profile_get.
+ * MI355_EBADARG (before the device is looked at, each with its own message and the offending index): a null pointer; an unknown op; a register >= n_regs; a dst below
+ * n_consts + n_inputs; an immediate out of range; n_regs > 2^16, n_instr > 2^20, jobs > 2^20; a constant or an input that is not below r.  jobs == 0 launches nothing.
+ * No CPU fallback (MI355_ENODEVICE).                                                                                                                                  */
+int mi355_fr_program_host(const uint32_t *code_host, uint32_t n_instr, uint32_t n_regs, const void *consts_host, uint32_t n_consts, const void *inputs_host, uint32_t n_inputs,
+                          uint32_t jobs, const uint32_t *out_regs_host, uint32_t n_outputs, void *outputs_host, uint32_t *flags_out_host);
 /* sum of `n` G1 (Jacobian, any representative) points: the fold `results.iter().fold(identity, |a, b| a + b)` of
  * best_multiexp, used to combine per-GPU partial sums after the RCCL all-gather.                  */
 int mi355_g1_sum_host(const void *g1_points_host, uint64_t n, void *out_g1_host);
@@ -486,7 +499,7 @@ int mi355_plonk_pk_vk(uint64_t pk, void *out, uint64_t cap, uint64_t *bytes_out)
  * poseidon | evm | by_layer, rng_key = 64 hexadecimal digits (the 32 key bytes in order), initial_state = 64 hexadecimal digits (a big-endian integer, reduced mod r: the
  * verifier's first transcript scalar).  Names: devices threads commit_batch upload_threads early_intt sparse_uploads packed_multiplicities device_multiplicities
  * multiplicity_rule_last check_witness device_randomness rng_key rng_key_from_os coset_group_polys transcript | check_accumulator accumulator host_only device_transcript
- * initial_state | cap theta_seed.  What is not set keeps the default of its struct.  An unknown name, or a value that does not parse or is out of range: MI355_EBADARG naming it. */
+ * device_scalars initial_state | cap theta_seed.  What is not set keeps the default of its struct.  An unknown name, or a value that does not parse or is out of range: MI355_EBADARG naming it. */
 int mi355_plonk_options_new(uint64_t *opts_out);
 int mi355_plonk_options_set(uint64_t opts, const char *name, const char *value);
 /* halo2_proofs::plonk::create_proof [REF integration/src/prove.rs:37,67,96] = plonk::create_proof over the key and the circuit's witness; srs_g / srs_g_lagrange: the two bases

@@ -102,6 +102,18 @@ inline std::vector<Fr> poseidon_transcripts(const std::vector<Fr> &words, const 
   check(mi355_poseidon_transcripts_host(words.data(), word_offsets.data(), squeeze_at.data(), squeeze_offsets.data(), (uint32_t)(word_offsets.size() - 1), out.data()));
   return out;
 }
+// one straight-line Fr program for many jobs in one launch (mi355_fr_program_host; the instruction set stands in include/mi355zk.h): code holds four words per instruction,
+// inputs n_inputs words per job; returns n_outputs words per job (register out_regs[t] of job j at [j * n_outputs + t]) and fills `flags` with one word per job.  The scalar
+// sides of a batch of verifiers (plonk::verify_proofs with VerifyOptions::device_scalars).
+inline std::vector<Fr> fr_program(const std::vector<uint32_t> &code, uint32_t n_regs, const std::vector<Fr> &consts, const std::vector<Fr> &inputs, uint32_t n_inputs, uint32_t jobs,
+                                  const std::vector<uint32_t> &out_regs, std::vector<uint32_t> &flags) {
+  if (code.size() % 4) throw std::invalid_argument("fr_program: four words per instruction");
+  if (inputs.size() != (size_t)n_inputs * jobs) throw std::invalid_argument("fr_program: inputs.len() != n_inputs * jobs");
+  std::vector<Fr> out(out_regs.size() * (size_t)jobs); flags.assign(jobs, 0);
+  check(mi355_fr_program_host(code.data(), (uint32_t)(code.size() / 4), n_regs, consts.data(), (uint32_t)consts.size(), inputs.data(), n_inputs, jobs, out_regs.data(),
+                              (uint32_t)out_regs.size(), out.data(), flags.data()));
+  return out;
+}
 inline void best_fft(std::vector<Fr> &a, const Fr &omega, uint32_t log_n) {
   if (a.size() != (size_t(1) << log_n)) throw std::invalid_argument("best_fft: a.len() != 1 << log_n");
   check(mi355_ntt_fr_host(a.data(), log_n, omega.data()));

@@ -14,10 +14,13 @@
 // KZG accumulators into the one the next layer's first twelve instances carry (KzgAs).  Both stand further down, behind verify_proof.
 // VerifyOptions::device_transcript (off by default) moves the Poseidon transcripts of such a batch onto the device: the transcript section of every Poseidon proof is RECORDED
 // (its words and squeeze positions, nothing hashed), ONE mi355_poseidon_transcripts_host call hashes all of them, and the rest of the host part REPLAYS the challenges.
+// VerifyOptions::device_scalars (off by default) moves the scalar side of such a batch onto the device: the proofs that ask for it are grouped by protocol, each group's scalar
+// side is compiled ONCE into a straight-line Fr program (mi355zk_plonk_scalar.hpp) and ONE mi355_fr_program_host call per group runs it for all of the group's proofs.
 #pragma once
 #include <chrono>
 #include "mi355zk_plonk_protocol.hpp"
 #include "mi355zk_transcript.hpp"
+#include "mi355zk_plonk_scalar.hpp"
 
 namespace mi355zk {
 namespace plonk {
@@ -41,6 +44,10 @@ struct VerifyOptions {
   // batch).  Proofs read with the EVM or Blake2b transcript, and host_only ones, take the host path inside the same batch.  Every VerifyResult equals the one with the option off.
   // verify_proof (one proof) IGNORES it: one sponge is a serial chain, and the host is the faster place for it.
   bool device_transcript = false;
+  // verify_proofs / aggregate: run this proof's scalar side (x^n, the Lagrange values, the numerator at x, the SHPLONK scalars) on the device, together with every other proof
+  // of the batch that asks for it and has the same protocol: one more device call per distinct protocol.  host_only proofs take the host path inside the same batch; composes
+  // with device_transcript.  Every VerifyResult equals the one with the option off, failures included.  verify_proof (one proof) IGNORES it, as it ignores device_transcript.
+  bool device_scalars = false;
 };
 struct VerifyResult {
   bool ok = false; std::string error;                       // the name of the first failed check ("" when none); `detail` says more
@@ -58,22 +65,6 @@ inline bool fq_on_curve(const halo2::G1Affine &a) {
   zk::fe_t three = zk::Fq::zero(); three.l[0] = 3; three = zk::Fq::from_canonical(three);
   return zk::Fq::eq(zk::Fq::sqr(y), zk::Fq::add(zk::Fq::mul(zk::Fq::sqr(x), x), three));
 }
-inline Fr eval_expr(const Expr &e, const std::map<PolyRot, Fr> &evals, const Fr *ch, const Fr &x, const std::map<int32_t, Fr> &lag) {
-  auto ev = [&](const Expr &k) { return eval_expr(k, evals, ch, x, lag); };
-  switch (e.kind) {
-    case Expr::CONSTANT: return e.c;
-    case Expr::IDENTITY: return x;
-    case Expr::LAGRANGE: return lag.at(e.i);
-    case Expr::POLY: { auto it = evals.find({(uint32_t)e.i, e.rot}); if (it == evals.end()) throw std::invalid_argument("verify: the numerator names an evaluation the proof does not carry"); return it->second; }
-    case Expr::CHALLENGE: return ch[e.i];
-    case Expr::NEG: return fr_neg(ev(e.kids[0]));
-    case Expr::SUM: return fr_add(ev(e.kids[0]), ev(e.kids[1]));
-    case Expr::PROD: return fr_mul(ev(e.kids[0]), ev(e.kids[1]));
-    case Expr::SCALED: return fr_mul(ev(e.kids[0]), e.c);
-    case Expr::DPOW: { const Fr b = ev(e.kids.back()); Fr acc = ev(e.kids[0]); for (size_t i = 1; i + 1 < e.kids.size(); i++) acc = fr_add(fr_mul(acc, b), ev(e.kids[i])); return acc; }   // Horner, the first expression at the highest power
-  }
-  throw std::invalid_argument("verify: unknown expression node");
-}
 
 // ---- the HOST PART of one verification, in three steps that plonk::verify_proof runs for one proof and plonk::verify_proofs / plonk::aggregate for many:
 //   layout_of     what the proof's length and the key decide before any point is looked at: the transcript, the word counts, every compressed point word
@@ -84,8 +75,9 @@ inline bool failed(VerifyResult &res, const char *name, const std::string &why) 
 inline uint64_t &device_calls() { static uint64_t n = 0; return n; }   // how many C-ABI calls that need a device the verifiers of this header have made (the drivers print it)
 // where the wall time of verify_proofs / aggregate went, in milliseconds, summed over the calls since the caller last cleared it (the drivers' --bench prints it):
 // decode = layouts + the decompression call; record = the recording pass of device_transcript; transcript_call = mi355_poseidon_transcripts_host; host_part = the pass over
-// host_part (the scalar side, the SHPLONK list, the accumulator; with the transcript on the host its hashing as well); msm and pairing = those calls with their packing
-struct PhaseTimes { double decode = 0, record = 0, transcript_call = 0, host_part = 0, msm = 0, pairing = 0; };
+// host_part (the scalar side, the SHPLONK list, the accumulator; with the transcript on the host its hashing as well; with device_scalars the compilation of the programs and
+// what is left of the host part around them); scalar_call = packing the inputs and mi355_fr_program_host, summed over the groups; msm and pairing = those calls with their packing
+struct PhaseTimes { double decode = 0, record = 0, transcript_call = 0, host_part = 0, msm = 0, pairing = 0, scalar_call = 0; };
 inline PhaseTimes &phase_times() { static PhaseTimes t; return t; }
 struct PhaseClock {
   double &into; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -131,9 +123,59 @@ inline void decode_words(const std::vector<halo2::G1Bytes> &words, std::vector<h
 // tape (Poseidon only): null = the transcript hashes on the host.  Otherwise pass = HostPass::Record runs the transcript section alone -- every absorbed word and every squeeze
 // position goes onto the tape, nothing is hashed, the section's named failures are reported as always -- and stops; pass = HostPass::Replay runs everything with the tape's
 // challenges in place of the sponge's.
+// defer (verify_proofs / aggregate with device_scalars): not null = stop where the scalar side begins and hand over what it and the rest need; the caller runs the protocol's
+// program for the whole group and finishes each proof with host_finish.
 enum class HostPass { Whole, Record, Replay };
+// what stands between the transcript section and the scalar side: the program's inputs for this proof (the eight challenges, the evaluations in proof order, the instances) and
+// the points the MSM list takes
+struct ScalarWork { std::vector<Fr> inputs; std::vector<halo2::G1Affine> pieces; std::map<uint32_t, halo2::G1Affine> com; halo2::G1Affine c_h{}, c_w{}; };
+inline void points_of(const std::vector<sdetail::MsmSource> &src, const ScalarWork &w, std::vector<halo2::G1Affine> &out) {
+  using sdetail::MsmSource;
+  halo2::G1Affine gen{}; { zk::fe_t c = zk::Fq::zero(); c.l[0] = 1; const zk::fe_t gx = zk::Fq::from_canonical(c); c.l[0] = 2; const zk::fe_t gy = zk::Fq::from_canonical(c); std::memcpy(gen.data(), &gx, 32); std::memcpy(gen.data() + 4, &gy, 32); }
+  for (const MsmSource &s : src) out.push_back(s.kind == MsmSource::Piece ? w.pieces[s.index] : s.kind == MsmSource::Commitment ? w.com.at(s.index) : s.kind == MsmSource::Generator ? gen : s.kind == MsmSource::H ? w.c_h : w.c_w);
+}
+// the scalar side in Fr itself (sdetail::scalar_side<FrArith>): numerator_at_x and the (scalars, points) list into res
+inline bool scalar_side_on_host(const Protocol &P, size_t n_instances, const ScalarWork &w, VerifyResult &res) {
+  using A = sdetail::FrArith;
+  A ar; sdetail::ScalarInputs<A> in; sdetail::ScalarSide<A> side;
+  const Fr *p = w.inputs.data();
+  for (auto &c : in.ch) c = *p++;
+  in.x = *p++; in.ys = *p++; in.v = *p++; in.u = *p++;
+  in.evals.assign(p, p + P.evaluations.size()); p += P.evaluations.size();
+  in.instances.assign(p, p + n_instances);
+  const bool ok = sdetail::scalar_side(ar, P, in, side);
+  if (side.numerator_set) res.numerator_at_x = side.numerator;
+  res.msm_scalars.insert(res.msm_scalars.end(), side.scalars.begin(), side.scalars.end());
+  points_of(side.sources, w, res.msm_points);
+  return ok || failed(res, side.failure.name, side.failure.detail);
+}
+// the carried accumulator: limbs of 88 bits, three per coordinate, (lhs.x, lhs.y, rhs.x, rhs.y) in the first twelve instances
+inline bool accumulator_part(const std::vector<Fr> &instances, const VerifyOptions &opt, const Protocol &P, VerifyResult &res) {
+  auto failed = [&](const char *name, const std::string &why) { return vdetail::failed(res, name, why); };
+  res.has_accumulator = opt.check_accumulator && (opt.accumulator < 0 ? P.has_accumulator : opt.accumulator != 0);
+  if (res.has_accumulator) {
+    if (instances.size() < 12) return failed("accumulator_limb", "an accumulator needs twelve instance values");
+    uint32_t q[8]; for (int i = 0; i < 8; i++) q[i] = zk::FqP::mod(i);
+    zk::fe_t co[4];
+    for (int cidx = 0; cidx < 4; cidx++) {
+      uint64_t wds[5] = {0, 0, 0, 0, 0};
+      for (int l = 0; l < 3; l++) {
+        const Fr cv = fr_to_canonical(instances[3 * cidx + l]);
+        if (cv[2] || cv[3] || (cv[1] >> 24)) return failed("accumulator_limb", "instance " + std::to_string(3 * cidx + l) + " is an accumulator limb of 2^88 or more");
+        const int bit = 88 * l, wi = bit / 64, sh = bit % 64;
+        wds[wi] |= cv[0] << sh; if (sh) { wds[wi + 1] |= cv[0] >> (64 - sh); } wds[wi + 1] |= cv[1] << sh; if (sh && wi + 2 < 5) wds[wi + 2] |= cv[1] >> (64 - sh);
+      }
+      std::memcpy(&co[cidx], wds, 32);
+      if (wds[4] || zk::Fq::w_geq(co[cidx].l, q)) return failed("accumulator_point", "accumulator coordinate " + std::to_string(cidx) + " is not below q");
+      co[cidx] = zk::Fq::from_canonical(co[cidx]);
+    }
+    std::memcpy(res.acc_lhs.data(), &co[0], 32); std::memcpy(res.acc_lhs.data() + 4, &co[1], 32); std::memcpy(res.acc_rhs.data(), &co[2], 32); std::memcpy(res.acc_rhs.data() + 4, &co[3], 32);
+    if (!vdetail::fq_on_curve(res.acc_lhs) || !vdetail::fq_on_curve(res.acc_rhs)) return failed("accumulator_point", "a point of the carried accumulator is not on the curve");
+  }
+  return true;
+}
 inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const VerifyOptions &opt, const Layout &L,
-                      const halo2::G1Affine *decoded, VerifyResult &res, TranscriptTape *tape = nullptr, HostPass pass = HostPass::Whole) {
+                      const halo2::G1Affine *decoded, VerifyResult &res, TranscriptTape *tape = nullptr, HostPass pass = HostPass::Whole, ScalarWork *defer = nullptr) {
   using halo2::G1Affine;
   auto failed = [&](const char *name, const std::string &why) { return vdetail::failed(res, name, why); };
   const TranscriptKind kind = L.kind; const bool use_vk = L.use_vk; const size_t nb = L.nb, n_ev = L.n_ev, vk0 = L.vk0;
@@ -167,12 +209,12 @@ inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::v
   std::vector<G1Affine> pieces(P.Q);
   for (auto &pc : pieces) if (!read_point(pc, err)) return failed("invalid_point", err);
   const Fr x = T.squeeze_challenge();
-  std::map<PolyRot, Fr> evals;
+  std::vector<Fr> evals(n_ev);   // in the order of P.evaluations
   for (size_t i = 0; i < n_ev; i++) {
     Fr v; const Transcript::Read st = T.read_scalar(proof, pos, v);
     if (st == Transcript::Read::NonCanonical) return failed("non_canonical_scalar", "evaluation " + std::to_string(i) + " of the proof is not below r");
     if (st != Transcript::Read::Ok) return failed("proof_length", "the proof ends inside evaluation " + std::to_string(i));
-    evals[P.evaluations[i]] = v;
+    evals[i] = v;
   }
   const Fr ys = T.squeeze_challenge(), v = T.squeeze_challenge();
   G1Affine c_h, c_w;
@@ -183,87 +225,27 @@ inline bool host_part(const Protocol &P, const VerifyingKeyRef &vk, const std::v
   res.theta = ch[0]; res.beta = ch[1]; res.gamma = ch[2]; res.y = ch[3]; res.x = x; res.shplonk_y = ys; res.shplonk_v = v; res.shplonk_u = uu; res.w_prime = c_w;
   if (pass == HostPass::Record) return true;   // the script is on the tape; the challenges above are placeholders until the replay
 
-  // ---- scalar side
-  const Fr one = fr_one();
-  Fr xn = x; for (uint32_t i = 0; i < P.k; i++) xn = fr_mul(xn, xn);
-  const Fr xn_minus_1 = fr_sub(xn, one);
-  if (fr_is_zero(xn_minus_1)) return failed("x_in_domain", "the evaluation point lies in the domain");
-  std::map<int32_t, Fr> lag;
-  auto lagrange_at = [&](int32_t i) {   // omega^i (x^n - 1) / (n (x - omega^i))
-    auto it = lag.find(i); if (it != lag.end()) return it->second;
-    const Fr wi = rot_power(P.omega, P.omega_inv, i);
-    const Fr val = fr_mul(fr_mul(fr_mul(wi, xn_minus_1), P.n_inv), fr_inv(fr_sub(x, wi)));
-    lag[i] = val; return val;
-  };
-  { std::vector<int32_t> need; collect_lagrange(P.numerator, need); for (int32_t i : need) lagrange_at(i); }
-  { Fr acc = fr_zero(); for (size_t i = 0; i < instances.size(); i++) acc = fr_add(acc, fr_mul(instances[i], lagrange_at((int32_t)i))); for (size_t j = 0; j < P.num_instance.size(); j++) evals[{P.inst0 + (uint32_t)j, 0}] = acc; }
-  { std::vector<std::pair<int32_t, int32_t>> named; collect_polys(P.numerator, named);   // an inconsistent protocol is a named failure here as in the SHPLONK part, never an exception
-    for (const auto &pr : named) if (!evals.count({(uint32_t)pr.first, pr.second})) return failed("protocol", "the numerator names polynomial " + std::to_string(pr.first) + " at rotation " + std::to_string(pr.second) + ", which the proof carries no evaluation for"); }
-  const Fr numer = vdetail::eval_expr(P.numerator, evals, ch, x, lag);
-  res.numerator_at_x = numer;
-  evals[{P.quotient_poly, 0}] = fr_mul(numer, fr_inv(xn_minus_1));
-
-  // ---- SHPLONK: the (scalars, points) list
-  auto rot_pt = [&](int32_t r) { return fr_mul(x, rot_power(P.omega, P.omega_inv, r)); };
-  const std::vector<RotationSet> sets = rotation_sets(P.queries);
-  std::vector<Fr> super_pts;
-  for (const auto &s : sets) for (int32_t r : s.rots) { const Fr pt = rot_pt(r); if (std::find(super_pts.begin(), super_pts.end(), pt) == super_pts.end()) super_pts.push_back(pt); }
-  Fr zt = one; for (const Fr &pt : super_pts) zt = fr_mul(zt, fr_sub(uu, pt));
-  std::vector<uint32_t> term_order; std::map<uint32_t, Fr> terms;
-  Fr r_acc = fr_zero(), zd0 = fr_zero(), vp = one; bool first = true;
-  for (const auto &s : sets) {
-    std::vector<Fr> points; for (int32_t r : s.rots) points.push_back(rot_pt(r));
-    Fr zd = one; for (const Fr &pt : super_pts) if (std::find(points.begin(), points.end(), pt) == points.end()) zd = fr_mul(zd, fr_sub(uu, pt));
-    if (first) { zd0 = zd; first = false; }
-    std::vector<Fr> basis(points.size());   // the Lagrange basis of the set's points at u: r_ij(u) = sum_k eval_k basis_k
-    for (size_t a = 0; a < points.size(); a++) { Fr num = one, den = one; for (size_t b = 0; b < points.size(); b++) if (b != a) { num = fr_mul(num, fr_sub(uu, points[b])); den = fr_mul(den, fr_sub(points[a], points[b])); } basis[a] = fr_mul(num, fr_inv(den)); }
-    const Fr w = fr_mul(vp, zd);
-    Fr inner_r = fr_zero(), yp = one;
-    for (uint32_t p : s.polys) {
-      Fr r_u = fr_zero();
-      for (size_t a = 0; a < points.size(); a++) { auto it = evals.find({p, s.rots[a]}); if (it == evals.end()) return failed("protocol", "polynomial " + std::to_string(p) + " is queried at a rotation the proof carries no evaluation for"); r_u = fr_add(r_u, fr_mul(it->second, basis[a])); }
-      inner_r = fr_add(inner_r, fr_mul(yp, r_u));
-      if (!terms.count(p)) { terms[p] = fr_zero(); term_order.push_back(p); }
-      terms[p] = fr_add(terms[p], fr_mul(w, yp));
-      yp = fr_mul(yp, ys);
-    }
-    r_acc = fr_add(r_acc, fr_mul(w, inner_r));
-    vp = fr_mul(vp, v);
-  }
-  if (fr_is_zero(zd0)) return failed("shplonk_degenerate", "u coincides with an opening point");
-  const Fr zi = fr_inv(zd0);
-  for (uint32_t p : term_order) {
-    const Fr c = fr_mul(terms[p], zi);
-    if (p == P.quotient_poly) { Fr f = one; for (const auto &pc : pieces) { res.msm_scalars.push_back(fr_mul(c, f)); res.msm_points.push_back(pc); f = fr_mul(f, xn); } }
-    else { auto it = com.find(p); if (it == com.end()) return failed("protocol", "no commitment for queried polynomial " + std::to_string(p)); res.msm_scalars.push_back(c); res.msm_points.push_back(it->second); }
-  }
-  G1Affine gen{}; { zk::fe_t c = zk::Fq::zero(); c.l[0] = 1; const zk::fe_t gx = zk::Fq::from_canonical(c); c.l[0] = 2; const zk::fe_t gy = zk::Fq::from_canonical(c); std::memcpy(gen.data(), &gx, 32); std::memcpy(gen.data() + 4, &gy, 32); }
-  res.msm_scalars.push_back(fr_neg(fr_mul(r_acc, zi))); res.msm_points.push_back(gen);
-  res.msm_scalars.push_back(fr_neg(fr_mul(zt, zi))); res.msm_points.push_back(c_h);
-  res.msm_scalars.push_back(uu); res.msm_points.push_back(c_w);
-
-  // ---- the carried accumulator: limbs of 88 bits, three per coordinate, (lhs.x, lhs.y, rhs.x, rhs.y) in the first twelve instances
-  res.has_accumulator = opt.check_accumulator && (opt.accumulator < 0 ? P.has_accumulator : opt.accumulator != 0);
-  if (res.has_accumulator) {
-    if (instances.size() < 12) return failed("accumulator_limb", "an accumulator needs twelve instance values");
-    uint32_t q[8]; for (int i = 0; i < 8; i++) q[i] = zk::FqP::mod(i);
-    zk::fe_t co[4];
-    for (int cidx = 0; cidx < 4; cidx++) {
-      uint64_t wds[5] = {0, 0, 0, 0, 0};
-      for (int l = 0; l < 3; l++) {
-        const Fr cv = fr_to_canonical(instances[3 * cidx + l]);
-        if (cv[2] || cv[3] || (cv[1] >> 24)) return failed("accumulator_limb", "instance " + std::to_string(3 * cidx + l) + " is an accumulator limb of 2^88 or more");
-        const int bit = 88 * l, wi = bit / 64, sh = bit % 64;
-        wds[wi] |= cv[0] << sh; if (sh) { wds[wi + 1] |= cv[0] >> (64 - sh); } wds[wi + 1] |= cv[1] << sh; if (sh && wi + 2 < 5) wds[wi + 2] |= cv[1] >> (64 - sh);
-      }
-      std::memcpy(&co[cidx], wds, 32);
-      if (wds[4] || zk::Fq::w_geq(co[cidx].l, q)) return failed("accumulator_point", "accumulator coordinate " + std::to_string(cidx) + " is not below q");
-      co[cidx] = zk::Fq::from_canonical(co[cidx]);
-    }
-    std::memcpy(res.acc_lhs.data(), &co[0], 32); std::memcpy(res.acc_lhs.data() + 4, &co[1], 32); std::memcpy(res.acc_rhs.data(), &co[2], 32); std::memcpy(res.acc_rhs.data() + 4, &co[3], 32);
-    if (!vdetail::fq_on_curve(res.acc_lhs) || !vdetail::fq_on_curve(res.acc_rhs)) return failed("accumulator_point", "a point of the carried accumulator is not on the curve");
-  }
-  return true;
+  // ---- scalar side: its inputs in the order a program takes them, then either handed over (device_scalars: the caller runs the program and calls host_finish) or run here
+  ScalarWork work;
+  work.inputs = {ch[0], ch[1], ch[2], ch[3], x, ys, v, uu};
+  work.inputs.insert(work.inputs.end(), evals.begin(), evals.end()); work.inputs.insert(work.inputs.end(), instances.begin(), instances.end());
+  work.pieces = std::move(pieces); work.com = std::move(com); work.c_h = c_h; work.c_w = c_w;
+  if (defer) { *defer = std::move(work); return true; }
+  if (!scalar_side_on_host(P, instances.size(), work, res)) return false;
+  return accumulator_part(instances, opt, P, res);
+}
+// the rest of a proof whose scalar side ran on the device: out = the program's outputs for this proof (numerator_at_x, then the MSM scalars), flags = its flag word.  The
+// flag of x_in_domain maps back to that failure; any other flag sends the proof through the host's scalar side, which names what there is to name.
+inline bool host_finish(const Protocol &P, const std::vector<Fr> &instances, const VerifyOptions &opt, const sdetail::ScalarProgram &prog, const ScalarWork &work, const Fr *out,
+                        uint32_t flags, VerifyResult &res) {
+  if (flags & (1u << sdetail::FLAG_BIT_X_IN_DOMAIN)) return failed(res, "x_in_domain", sdetail::x_in_domain_text());
+  // any other flag: a zero went through the shared inverse, so every inverse of this job is zero and its outputs mean nothing -- shplonk_degenerate keeps its numerator_at_x,
+  // and x = 0 is no failure at all, only on the host
+  if (flags) { if (!scalar_side_on_host(P, instances.size(), work, res)) return false; return accumulator_part(instances, opt, P, res); }
+  res.numerator_at_x = out[0];
+  res.msm_scalars.assign(out + 1, out + 1 + prog.sources.size());
+  points_of(prog.sources, work, res.msm_points);
+  return accumulator_part(instances, opt, P, res);
 }
 inline void host_only_done(VerifyResult &res) { res.ok = true; res.error = ""; res.detail = "host-only: stopped before the multi-scalar multiplication and the pairing"; }
 // the verdict over a proof's one or two pairing groups (res.pairing filled)
@@ -284,7 +266,7 @@ inline std::vector<uint32_t> pairing_groups(const std::vector<halo2::G1Affine> &
 }
 }  // namespace vdetail
 
-// one proof: VerifyOptions::device_transcript is ignored here (one sponge is a serial chain; the host runs it faster than one lane does)
+// one proof: VerifyOptions::device_transcript and device_scalars are ignored here (one sponge, one scalar side: serial chains the host runs faster than one lane does)
 inline VerifyResult verify_proof(const Protocol &P, const VerifyingKeyRef &vk, const std::vector<Fr> &instances, const std::vector<uint8_t> &proof, const G2Pair &srs, const VerifyOptions &opt) {
   using halo2::G1Affine;
   VerifyResult res; vdetail::Layout L;
@@ -345,13 +327,44 @@ inline void host_parts(const std::vector<ProofInput> &in, std::vector<VerifyResu
     device_calls()++; const std::vector<Fr> ch = halo2::poseidon_transcripts(w, woff, sq, soff);
     for (size_t j = 0; j < dev.size(); j++) tapes[dev[j]].challenges.assign(ch.begin() + soff[j], ch.begin() + soff[j + 1]);
   }
-  PhaseClock pc(phase_times().host_part);
-  for (size_t i = 0; i < N; i++) {
-    if (!passed[i]) continue;
-    std::vector<G1Affine> own; if (in[i].opt.host_only) decode_words(L[i].words, own, true);
-    const bool replay = std::find(dev.begin(), dev.end(), i) != dev.end();
-    passed[i] = host_part(*in[i].protocol, *in[i].vk, in[i].instances, in[i].proof, in[i].opt, L[i], in[i].opt.host_only ? own.data() : decoded.data() + at[i], res[i],
-                          replay ? &tapes[i] : nullptr, replay ? HostPass::Replay : HostPass::Whole) ? 1 : 0;
+  // device_scalars: the proofs that ask for it stop where the scalar side begins and wait in the group of their (protocol, number of instances), whose program is compiled when
+  // the first of them arrives; a protocol that fails structurally has no program and its proofs run on the host, where that failure is named.  ONE call per group, then the
+  // rest of each proof's host part.  No proof left in a group: no call.
+  struct Group { sdetail::ScalarProgram prog; std::vector<size_t> members; };
+  std::map<std::pair<const Protocol *, size_t>, Group> groups; std::vector<ScalarWork> work(N);
+  {
+    PhaseClock pc(phase_times().host_part);
+    for (size_t i = 0; i < N; i++) {
+      if (!passed[i]) continue;
+      std::vector<G1Affine> own; if (in[i].opt.host_only) decode_words(L[i].words, own, true);
+      const bool replay = std::find(dev.begin(), dev.end(), i) != dev.end();
+      Group *grp = nullptr;
+      if (in[i].opt.device_scalars && !in[i].opt.host_only) {
+        const auto key = std::make_pair(in[i].protocol, in[i].instances.size());
+        auto it = groups.find(key);
+        if (it == groups.end()) { it = groups.emplace(key, Group{}).first; it->second.prog = sdetail::compile_scalar_program(*in[i].protocol, in[i].instances.size()); }
+        if (it->second.prog.usable) grp = &it->second;
+      }
+      passed[i] = host_part(*in[i].protocol, *in[i].vk, in[i].instances, in[i].proof, in[i].opt, L[i], in[i].opt.host_only ? own.data() : decoded.data() + at[i], res[i],
+                            replay ? &tapes[i] : nullptr, replay ? HostPass::Replay : HostPass::Whole, grp ? &work[i] : nullptr) ? 1 : 0;
+      if (passed[i] && grp) grp->members.push_back(i);
+    }
+  }
+  for (auto &kv : groups) {
+    const Group &grp = kv.second; const sdetail::ScalarProgram &prog = grp.prog;
+    if (grp.members.empty()) continue;
+    std::vector<Fr> outputs; std::vector<uint32_t> flags;
+    {
+      PhaseClock pc(phase_times().scalar_call);
+      std::vector<Fr> inputs; inputs.reserve(grp.members.size() * (size_t)prog.n_inputs);
+      for (size_t i : grp.members) inputs.insert(inputs.end(), work[i].inputs.begin(), work[i].inputs.end());
+      device_calls()++; outputs = halo2::fr_program(prog.code, prog.n_regs, prog.consts, inputs, prog.n_inputs, (uint32_t)grp.members.size(), prog.out_regs, flags);
+    }
+    PhaseClock pc(phase_times().host_part);
+    for (size_t j = 0; j < grp.members.size(); j++) {
+      const size_t i = grp.members[j];
+      passed[i] = host_finish(*in[i].protocol, in[i].instances, in[i].opt, prog, work[i], outputs.data() + j * prog.out_regs.size(), flags[j], res[i]) ? 1 : 0;
+    }
   }
 }
 // the lists of the proofs `idx` names, concatenated: one segmented MSM, the sums into msm_result

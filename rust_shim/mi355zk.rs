@@ -52,6 +52,8 @@ extern "C" {
     pub fn mi355_msm_g1_adhoc_host(bases: *const c_void, scalars: *const c_void, n: u64, out_g1_host: *mut c_void) -> c_int;
     pub fn mi355_msm_g1_segmented_host(bases: *const c_void, scalars: *const c_void, offsets: *const u64, segments: u32, out_g1affine_host: *mut c_void) -> c_int;
     pub fn mi355_poseidon_transcripts_host(words: *const c_void, word_offsets: *const u64, squeeze_at: *const u32, squeeze_offsets: *const u64, jobs: u32, challenges_out_host: *mut c_void) -> c_int;
+    pub fn mi355_fr_program_host(code: *const u32, n_instr: u32, n_regs: u32, consts: *const c_void, n_consts: u32, inputs: *const c_void, n_inputs: u32, jobs: u32,
+                                 out_regs: *const u32, n_outputs: u32, outputs_host: *mut c_void, flags_out_host: *mut u32) -> c_int;
     pub fn mi355_g1_batch_normalize_host(g1_points_host: *const c_void, affine_out_host: *mut c_void, n: u64) -> c_int;
     pub fn mi355_g1_decompress_dev(bytes_dev: *const c_void, affine_out_dev: *mut c_void, n: u64, first_bad_out: *mut u64) -> c_int;
     pub fn mi355_g1_decompress_host(bytes_host: *const c_void, affine_out_host: *mut c_void, n: u64, first_bad_out: *mut u64) -> c_int;

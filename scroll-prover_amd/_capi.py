@@ -57,6 +57,7 @@ SIGNATURES = {
     "mi355_msm_g1_adhoc_host": (_int, [_vp, _vp, _u64, _vp]),
     "mi355_msm_g1_segmented_host": (_int, [_vp, _vp, _vp, _u32, _vp]),
     "mi355_poseidon_transcripts_host": (_int, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    "mi355_fr_program_host": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _vp]),
     "mi355_g1_sum_host": (_int, [_vp, _u64, _vp]),
     "mi355_g1_batch_normalize_dev": (_int, [_vp, _vp, _u64]),
     "mi355_g1_batch_normalize_host": (_int, [_vp, _vp, _u64]),

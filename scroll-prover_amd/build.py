@@ -110,7 +110,10 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
 
 
-CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check", "test_verify_proof", "test_verify_proofs", "test_device_randomness", "test_device_transcripts", "test_hbm_budget")
+CPP_PROGRAMS = ("test_halo2_mirror", "test_shim_replay", "test_plonk_replay", "test_prover_process", "test_lookup_multiplicities", "test_g1_codec", "test_permutation_keygen", "test_witness_check", "test_verify_proof", "test_verify_proofs", "test_device_randomness", "test_device_transcripts", "test_device_scalars", "test_hbm_budget")
+
+
+NO_ORACLE = {"test_device_scalars"}   # linked without the oracle's library: nothing of the checker on the link line of a program that is timed
 
 
 def build_cpp(name: str) -> str:
@@ -123,7 +126,7 @@ def build_cpp(name: str) -> str:
     orc = os.path.join(root, "oracle")
     h = hashlib.sha256()
     inc = os.path.join(root, "include")
-    for f in [src, os.path.join(HERE, "csrc", "fp.hpp"), os.path.join(HERE, "csrc", "fp_asm.hpp"), os.path.join(HERE, "csrc", "fp_asm_gen.inc"), os.path.join(HERE, "csrc", "frrand.hpp"), os.path.join(HERE, "csrc", "slab_ranges.hpp"), os.path.join(HERE, "csrc", "mem_budget.hpp"), os.path.join(orc, "bn254_oracle.c")] + sorted(os.path.join(inc, x) for x in os.listdir(inc)):
+    for f in [src, os.path.join(HERE, "csrc", "fp.hpp"), os.path.join(HERE, "csrc", "fp_asm.hpp"), os.path.join(HERE, "csrc", "fp_asm_gen.inc"), os.path.join(HERE, "csrc", "frrand.hpp"), os.path.join(HERE, "csrc", "frprog.hpp"), os.path.join(HERE, "csrc", "slab_ranges.hpp"), os.path.join(HERE, "csrc", "mem_budget.hpp"), os.path.join(orc, "bn254_oracle.c")] + sorted(os.path.join(inc, x) for x in os.listdir(inc)):
         with open(f, "rb") as fh:
             h.update(fh.read())
     tag = exe + ".srchash"
@@ -132,8 +135,9 @@ def build_cpp(name: str) -> str:
     except OSError:
         fresh = False
     if not fresh:
+        oracle = [] if name in NO_ORACLE else ["-L", orc, "-loracle_bn254", f"-Wl,-rpath,{orc}"]
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-Wno-unknown-pragmas", "-I", inc, src, "-o", exe,
-                               "-L", HERE, "-lmi355zk", "-L", orc, "-loracle_bn254", f"-Wl,-rpath,{HERE}", f"-Wl,-rpath,{orc}", "-Wl,-rpath,/opt/rocm/lib"])
+                               "-L", HERE, "-lmi355zk", f"-Wl,-rpath,{HERE}"] + oracle + ["-Wl,-rpath,/opt/rocm/lib"])
         with open(tag, "w") as fh:
             fh.write(h.hexdigest())
     return exe

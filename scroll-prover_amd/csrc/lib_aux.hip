@@ -2,7 +2,7 @@
 // (g1fft.hpp: g_to_lagrange, ParamsKZG::downsize), the multiplicative scans of the permutation / lookup arguments and kate_division
 // (frscan.hpp), Curve::batch_normalize, the one G2 scalar multiple of ParamsKZG::setup (g2.hpp), the multiplicities of the mv-lookup argument
 // (lookup.hpp), the sigma columns of the permutation argument (perm.hpp), the compressed-point codec of G1 (g1codec.hpp), the two reductions of the witness
-// check (check.hpp), the prover's randomness (frrand.hpp), and the Poseidon transcripts of a batch of verifiers (poseidon.hpp).  Host logic only.
+// check (check.hpp), the prover's randomness (frrand.hpp), the Poseidon transcripts of a batch of verifiers (poseidon.hpp) and their scalar sides (frprog.hpp).  Host logic only.
 // The shape of an entry point: guarded([&] { slot + DevGuard; need_init; argument checks; WsLayout names the fields of the workspace; PoolBlock owns it; the body calls
 // HIPCHK / CHK and returns where it fails -- the block goes back to the pool on every path; finish_async() }).  The exception: mi355_buf_upload_packed / _sparse take no
 // DevGuard and do not call finish_async() -- like mi355_buf_upload, which they stand in for, they only queue (see "narrow uploads" below).
@@ -16,6 +16,7 @@
 #include "check.hpp"
 #include "frrand.hpp"
 #include "poseidon.hpp"
+#include "frprog.hpp"
 #include "lib_common.hpp"
 #include <thread>
 
@@ -758,6 +759,45 @@ int mi355_poseidon_transcripts_host(const void *words_host, const uint64_t *word
   HIPCHK(hipStreamSynchronize(s));
   resolve_spans();
   { char buf[64]; snprintf(buf, sizeof buf, " jobs=%u squeezes=%llu", jobs, (unsigned long long)n_sq); tr.done(buf); }
+  return MI355_OK;
+  });
+}
+
+// ---- one straight-line Fr program for many jobs (frprog.hpp: one lane per job).  The argument checks (frprog_check) read host memory only and come before the device is asked
+// for.  Workspace: ONE pooled mi355_buf block (PoolBlock; WsLayout) -- the program, the constants, the inputs, the register file ((n_regs - n_consts) x jobs rounded up to 64
+// words), the output register list, the outputs and the flag words -- back in the pool on every return.  One launch, two downloads, synchronous.
+int mi355_fr_program_host(const uint32_t *code_host, uint32_t n_instr, uint32_t n_regs, const void *consts_host, uint32_t n_consts, const void *inputs_host, uint32_t n_inputs,
+                          uint32_t jobs, const uint32_t *out_regs_host, uint32_t n_outputs, void *outputs_host, uint32_t *flags_out_host) {
+  return guarded([&]() -> int {
+  { std::string why;
+    if (!frprog_check(code_host, n_instr, n_regs, consts_host, n_consts, inputs_host, n_inputs, jobs, out_regs_host, n_outputs, outputs_host, flags_out_host, why)) return fail(MI355_EBADARG, "fr_program: " + why); }
+  const int slot = pick_replica_slot(); DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (jobs == 0) return MI355_OK;   // nothing is launched, nothing is written
+  CallTrace tr("fr_program", (uint64_t)jobs * n_instr, 32.0);
+  const uint64_t stride = frprog_stride(jobs);
+  WsLayout L;
+  const uint64_t off_code = L.take((uint64_t)n_instr * 16), off_consts = L.take((uint64_t)n_consts * sizeof(fe_t)), off_in = L.take((uint64_t)jobs * n_inputs * sizeof(fe_t)),
+                 off_regs = L.take((uint64_t)(n_regs - n_consts) * stride * sizeof(fe_t)), off_oregs = L.take((uint64_t)n_outputs * 4),
+                 off_out = L.take((uint64_t)jobs * n_outputs * sizeof(fe_t)), off_flags = L.take((uint64_t)jobs * 4);
+  PoolBlock ws; CHK(ws.alloc(L.total(), slot));
+  hipStream_t s = g.stream;
+  if (n_instr) HIPCHK(hipMemcpyAsync(ws.at(off_code), code_host, (size_t)n_instr * 16, hipMemcpyHostToDevice, s));
+  if (n_consts) HIPCHK(hipMemcpyAsync(ws.at(off_consts), consts_host, (size_t)n_consts * sizeof(fe_t), hipMemcpyHostToDevice, s));
+  if (n_inputs) HIPCHK(hipMemcpyAsync(ws.at(off_in), inputs_host, (size_t)jobs * n_inputs * sizeof(fe_t), hipMemcpyHostToDevice, s));
+  if (n_outputs) HIPCHK(hipMemcpyAsync(ws.at(off_oregs), out_regs_host, (size_t)n_outputs * 4, hipMemcpyHostToDevice, s));
+  {
+    Scope sp("fr_program", s);
+    hipLaunchKernelGGL(k_fr_program, dim3(ceil_div(jobs, FRP_LANES)), dim3(FRP_LANES), 0, s, (const uint32_t *)ws.at(off_code), n_instr, (const fe_t *)ws.at(off_consts), n_consts,
+                       (const fe_t *)ws.at(off_in), n_inputs, jobs, (fe_t *)ws.at(off_regs), stride, (const uint32_t *)ws.at(off_oregs), n_outputs, (fe_t *)ws.at(off_out),
+                       (uint32_t *)ws.at(off_flags));
+  }
+  HIPCHK(hipGetLastError());
+  if (n_outputs) HIPCHK(hipMemcpyAsync(outputs_host, ws.at(off_out), (size_t)jobs * n_outputs * sizeof(fe_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(flags_out_host, ws.at(off_flags), (size_t)jobs * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  resolve_spans();
+  { char buf[64]; snprintf(buf, sizeof buf, " jobs=%u instructions=%u registers=%u", jobs, n_instr, n_regs); tr.done(buf); }
   return MI355_OK;
   });
 }

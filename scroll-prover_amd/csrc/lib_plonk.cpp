@@ -82,6 +82,7 @@ VerifyOptions verify_options(const capi::Options &o) {
   if (auto v = o.find("accumulator")) p.accumulator = (int)v->i;
   if (auto v = o.find("host_only")) p.host_only = v->i != 0;
   if (auto v = o.find("device_transcript")) p.device_transcript = v->i != 0;
+  if (auto v = o.find("device_scalars")) p.device_scalars = v->i != 0;
   return p;
 }
 CheckOptions check_options(const capi::Options &o) {

@@ -104,6 +104,7 @@ inline const std::vector<OptSpec> &option_specs() {
       {"accumulator", OptType::Int, -1, 1, "VerifyOptions"},
       {"host_only", OptType::Bool, 0, 1, "VerifyOptions"},
       {"device_transcript", OptType::Bool, 0, 1, "VerifyOptions"},
+      {"device_scalars", OptType::Bool, 0, 1, "VerifyOptions"},
       {"initial_state", OptType::Hex32, 0, 0, "VerifyingKeyRef"},
       {"cap", OptType::Uint, 0, 65536, "CheckOptions"},
       {"theta_seed", OptType::Uint, 0, ~uint64_t(0), "CheckOptions"},

@@ -660,16 +660,23 @@ def _run_verify_proofs(cases, mode, g2, s_g2, neg_s_g2, host_only, need_srs, tim
 
 
 def verify_proofs(cases, g2=None, s_g2=None, neg_s_g2=None, host_only: bool = False, one_by_one: bool = False, timeout: int = 600, device_transcript: bool = False,
-                  tile: int = 0) -> list:
+                  tile: int = 0, device_scalars: bool = False, host_only_at=()) -> list:
     """plonk::verify_proofs (include/mi355zk_plonk_verify.hpp) through its compiled driver tests/cpp/test_verify_proofs.cpp: N proofs, ONE point decompression, ONE segmented
     MSM, ONE pairing call.  cases: dictionaries with protocol (path or dict), instances, proof and verify_proof's per-proof keywords (transcript, vk_bytes, preprocessed,
     initial_state, check_accumulator, accumulator); protocols and transcripts may differ.  g2 / s_g2 / neg_s_g2 / host_only as in verify_proof.  Returns verify_proof's record
     per proof, each equal to what verify_proof gives for that proof alone; the last one carries "device_calls" (how many device calls the batch made).
     one_by_one=True runs the unchanged verify_proof in a loop inside the same process instead.  device_transcript=True (VerifyOptions::device_transcript, through
     tests/cpp/test_device_transcripts.cpp): the Poseidon transcripts of the batch are hashed by ONE mi355_poseidon_transcripts_host call -- one device call more, the same
-    records; it needs the device, so it excludes host_only and one_by_one.  tile=N: the driver repeats the cases cyclically up to N proofs (--tile)."""
+    records; it needs the device, so it excludes host_only and one_by_one.  tile=N: the driver repeats the cases cyclically up to N proofs (--tile).
+    device_scalars=True (VerifyOptions::device_scalars, through tests/cpp/test_device_scalars.cpp): the scalar sides of the batch run on the device, ONE mi355_fr_program_host
+    call per distinct protocol -- that many device calls more, the same records; composes with device_transcript.  host_only_at: indices of proofs that get
+    VerifyOptions::host_only inside that batch (they take the host path; their records say host_only)."""
     extra = ["--tile", str(int(tile))] if tile else []
-    if device_transcript:
+    if device_scalars:
+        assert not host_only and not one_by_one, "verify_proofs: device_scalars needs the device and the batched call"
+        extra += (["--device-transcript"] if device_transcript else []) + (["--host-only-at", ",".join(str(int(i)) for i in host_only_at)] if len(host_only_at) else [])
+        recs, summary = _run_verify_proofs(cases, [], g2, s_g2, neg_s_g2, False, True, timeout, extra=extra, driver="test_device_scalars")
+    elif device_transcript:
         assert not host_only and not one_by_one, "verify_proofs: device_transcript needs the device and the batched call"
         recs, summary = _run_verify_proofs(cases, [], g2, s_g2, neg_s_g2, False, True, timeout, extra=extra, driver="test_device_transcripts")
     else:
@@ -680,15 +687,18 @@ def verify_proofs(cases, g2=None, s_g2=None, neg_s_g2=None, host_only: bool = Fa
     return recs
 
 
-def aggregate(cases, g2=None, s_g2=None, neg_s_g2=None, pairing: bool = True, host_only: bool = False, timeout: int = 600, device_transcript: bool = False) -> dict:
+def aggregate(cases, g2=None, s_g2=None, neg_s_g2=None, pairing: bool = True, host_only: bool = False, timeout: int = 600, device_transcript: bool = False,
+              device_scalars: bool = False) -> dict:
     """plonk::aggregate through the same driver (--aggregate): the KZG accumulators of the proofs -- (msm_result, W') of each, its carried accumulator after it -- folded with the
     powers of a Poseidon transcript challenge into the accumulator the next layer's first twelve instances carry.  Returns ok, error, detail, proofs (records), accumulators
     [((x, y), (x, y)), ...], r, lhs, rhs, limbs (12 integers below 2^88), pairing, device_calls.  pairing=False: fold only, no SRS.  host_only=True: no device; the lists'
     sums come from the oracle and the result stops after r (lhs, rhs and limbs are zero).  device_transcript=True: the proofs' Poseidon transcripts are hashed on the device
-    (as in verify_proofs; the aggregation's own transcript, one sponge, stays on the host)."""
-    assert not (device_transcript and host_only), "aggregate: device_transcript needs the device"
-    recs, a = _run_verify_proofs(cases, ["--aggregate"], g2, s_g2, neg_s_g2, host_only, pairing and not host_only, timeout, extra=[] if pairing or host_only else ["--no-pairing"],
-                                 driver="test_device_transcripts" if device_transcript else "test_verify_proofs")
+    (as in verify_proofs; the aggregation's own transcript, one sponge, stays on the host).  device_scalars=True: the proofs' scalar sides run on the device (as in
+    verify_proofs: one more device call per distinct protocol)."""
+    assert not ((device_transcript or device_scalars) and host_only), "aggregate: device_transcript and device_scalars need the device"
+    extra = ([] if pairing or host_only else ["--no-pairing"]) + (["--device-transcript"] if device_scalars and device_transcript else [])
+    recs, a = _run_verify_proofs(cases, ["--aggregate"], g2, s_g2, neg_s_g2, host_only, pairing and not host_only, timeout, extra=extra,
+                                 driver="test_device_scalars" if device_scalars else "test_device_transcripts" if device_transcript else "test_verify_proofs")
     h = lambda s: int(s, 16)
     pt = lambda p: (h(p[0]), h(p[1]))
     a["proofs"] = recs
@@ -706,6 +716,31 @@ def record_transcripts(cases, timeout: int = 600) -> list:
     for r in recs:
         r["words"] = [int(v, 16) for v in r["words"]]; r["challenges"] = [int(v, 16) for v in r["challenges"]]
     return recs
+
+
+def scalar_programs(cases, timeout: int = 600) -> list:
+    """what VerifyOptions::device_scalars compiles for the cases (tests/cpp/test_device_scalars --program-info; no device): per distinct (protocol, number of instances) one
+    dictionary with layer, k, instances, usable, instructions, registers, constants, inputs, outputs, inversions."""
+    recs, summary = _run_verify_proofs(cases, ["--program-info"], None, None, None, False, False, timeout, driver="test_device_scalars", raw=True)
+    assert summary["programs"] == len(recs)
+    return recs
+
+
+def fr_program(code, n_regs: int, consts, inputs, out_regs):
+    """mi355_fr_program_host: ONE straight-line program over Fr for MANY jobs in one launch, a lane per job.  code [n, 4] u32 (op, dst, a, b): 0 ADD, 1 SUB, 2 MUL, 3 SQRN
+    (dst = a^(2^b), b an immediate <= 64), 4 INV (zero gives zero and sets bit 0 of the job's flag word), 5 NZ (sets flag bit b in 1 .. 31 when a == 0).  Registers
+    [0, len(consts)) hold consts [c, 4] u64, the next n_inputs the job's row of inputs [jobs, n_inputs, 4] u64 (Fr, Montgomery, below r), the rest are temporaries.
+    -> (outputs [jobs, len(out_regs), 4] u64, flags [jobs] u32)."""
+    code = np.ascontiguousarray(code, dtype=np.uint32).reshape(-1, 4)
+    consts = np.ascontiguousarray(consts, dtype=np.uint64).reshape(-1, 4)
+    inputs = np.ascontiguousarray(inputs, dtype=np.uint64)
+    assert inputs.ndim == 3 and inputs.shape[2] == 4, "fr_program: inputs is [jobs, n_inputs, 4]"
+    out_regs = np.ascontiguousarray(out_regs, dtype=np.uint32).reshape(-1)
+    jobs, n_inputs = inputs.shape[0], inputs.shape[1]
+    out = np.zeros((jobs, out_regs.shape[0], 4), dtype=np.uint64)
+    flags = np.zeros(jobs, dtype=np.uint32)
+    check(lib().mi355_fr_program_host(ptr(code), code.shape[0], n_regs, ptr(consts), consts.shape[0], ptr(inputs), n_inputs, jobs, ptr(out_regs), out_regs.shape[0], ptr(out), ptr(flags)))
+    return out, flags
 
 
 def msm_g1_segmented(bases, scalars, offsets) -> np.ndarray:

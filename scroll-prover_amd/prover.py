@@ -285,7 +285,7 @@ def _ints(rec: dict) -> dict:
 def verify_proofs(cases, params=None, g2=None, s_g2=None, neg_s_g2=None, options=None, one_by_one: bool = False) -> list:
     """plonk::verify_proofs (or verify_proof in a loop) over cases = [{"protocol": Protocol, "instances": integers, "proof": bytes, "vk_bytes": bytes | None}, ...].
     The SRS side: params (a halo2.ParamsKZG) or g2 + s_g2 | neg_s_g2 (128-byte G2Affine); not needed with host_only.  options: Options or a dict (transcript, host_only,
-    check_accumulator, accumulator, initial_state, device_transcript), applied to every proof.  Returns the records halo2.verify_proofs returns, one per proof; a rejected
+    check_accumulator, accumulator, initial_state, device_transcript, device_scalars), applied to every proof.  Returns the records halo2.verify_proofs returns, one per proof; a rejected
     proof is a record with ok False and the named failure in "error"."""
     ok, rec = _verify_call(cases, MODE_ONE_BY_ONE if one_by_one else MODE_BATCHED, params, g2, s_g2, neg_s_g2, options)
     out = [_ints(r) for r in rec["proofs"]]
