@@ -332,6 +332,20 @@ int mi355_fr_prefix_sum_dev(void *dst_dev, const void *src_dev, uint64_t n, void
  * returns it).  Runs on the library stream of the device that owns m_dev and returns when m is written (the result decides the error).  */
 int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *table_dev, uint64_t table_rows, const void *const *inputs_dev,
                                        uint32_t n_inputs, uint64_t input_rows, uint32_t flags, uint64_t *missing_out);
+/* the permuted columns A' and S' of the classic halo2 lookup argument (upstream PSE / zcash halo2, before the scroll fork's mv-lookup), which halo2
+ * computes inside the prover after theta [EXT-recalled halo2_proofs src/plonk/lookup/prover.rs, `permute_expression_pair`].  All four operands are
+ * DEVICE memory (mi355_buf ranges of at least `rows` words, 16-byte aligned): perm_input and perm_table out, input and table (the theta-compressed
+ * columns) in; rows >= `rows` of the outputs are not touched (the caller's blinding rows).  perm_input is `input` sorted ascending by the canonical
+ * integer value (halo2curves' Ord; the Montgomery words are converted before they are compared).  Every row of perm_input that starts a run of equal
+ * values takes the same value in perm_table and uses up one copy of it in the table; the copies of the table left over, in ascending order with
+ * duplicates, fill the other rows from the LAST such row backwards (halo2 pop()s them).  Every output word is a copy of a table word.  An input value
+ * absent from the table: MI355_EBADARG, *missing_out (optional) = the smallest row of `input`, in its original order, with such a value, outputs
+ * unspecified; otherwise *missing_out = ~0.  MI355_EBADARG with the reason in mi355_last_error(), before the device is asked for, for rows >= 2^31, a
+ * null or misaligned pointer, a range that leaves its block, outputs that overlap each other or an input, and operands on different devices.
+ * rows == 0 writes nothing.  Workspace: one pooled mi355_buf block of 52 .. 60 B per row (mi355_mem_info counts it, mi355_buf_trim returns it,
+ * mi355_mem_set_limit applies: MI355_EOOM).  Runs on the library stream of the device that owns the outputs and returns when they are written; the
+ * same operands give the same bytes on every run.                                                                                                  */
+int mi355_fr_lookup_permute_dev(void *perm_input, void *perm_table, const void *input, const void *table, uint64_t rows, uint64_t *missing_out);
 /* sigma columns of the permutation argument from the copy mapping [EXT-recalled halo2_proofs src/plonk/permutation/keygen.rs, build_pk / build_vk:
  * permutations[i][j] = delta^i' omega^j' for mapping[i][j] = (i', j'), which halo2 fills on the CPU from a num_cols x n table].  sigma_dev: host array of
  * n_cols device pointers, each n = 2^log_n words out (Lagrange basis); delta, omega: 32-byte words on the host.  A cell is the integer column * n + row
@@ -472,7 +486,7 @@ int mi355_plonk_protocol_from_json(const char *json, uint64_t len, uint64_t *pro
 int mi355_plonk_protocol_from_file(const char *path, uint64_t *protocol_out);
 /* one figure of the protocol by name: k, n, layer (~0 when the file names none), num_preprocessed, num_instance, num_advice, num_lookups, num_perm_columns, num_perm_chunks,
  * num_gates, num_witness (all phases), num_commitments, blind, usable, quotient_pieces, extended_k, num_evaluations, num_queries, lookup_bits, proof_bytes_poseidon (also the
- * Blake2b layout), proof_bytes_evm, has_initial_state, has_accumulator.  An unknown field: MI355_EBADARG naming it.                                                          */
+ * Blake2b layout), proof_bytes_evm, has_initial_state, has_accumulator, lookup_permuted (1: the classic halo2 lookup argument, 0: mv-lookup).  An unknown field: MI355_EBADARG naming it.                                                          */
 int mi355_plonk_protocol_info(uint64_t protocol, const char *field, uint64_t *value_out);
 int mi355_plonk_free(uint64_t handle);
 /* plonk::Circuit, owned by the library: what keygen assigns and `synthesize` fills in the reference [EXT-recalled halo2_proofs plonk/keygen.rs, plonk/prover.rs].  _new: every
@@ -482,6 +496,8 @@ int mi355_plonk_free(uint64_t handle);
  *   preprocessed  n words, Lagrange values of fixed column `index` (_get also answers for the sigma columns, derived from the copies; _set refuses them)
  *   advice, m     n words                    m_counts      n x uint32_t, the multiplicities as integers
  *   m_blind, z_blind, phi_blind   `blind` words (protocol_info)          random_poly   n words, coefficients
+ *   perm_blind    2 x (blind + 1) words, lz_blind  `blind` words: protocols with the classic (permuted) lookup argument only (protocol_info "lookup_permuted"), per lookup --
+ *                 the rows from the l_last row on of A', then of S'; the last rows of the lookup's grand product.  Such protocols have no m, m_counts, m_blind, phi_blind
  *   instances     at most num_instance words                             copies        records of four uint64_t (position a, row a, position b, row b): two cells of
  *                                                                                      the permutation's columns, in the protocol's order, that must be equal; replaces the list
  * A size that does not match the protocol, an index out of range, a cell outside the permutation: MI355_EBADARG, the circuit unchanged.                                      */

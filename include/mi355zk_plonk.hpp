@@ -776,7 +776,7 @@ struct ProofRun {
   using Clock = std::chrono::steady_clock;
   static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
   const uint64_t h_g, h_g_lagrange; const ProvingKey &pk; const Circuit &wit; const ProofOptions &opt; const Protocol &P; const EvaluationDomain &dom;
-  const uint32_t k, Q; const uint64_t n, u; const uint32_t A, NL, NZ; const int D; const bool dev_m, dev_rng;
+  const uint32_t k, Q; const uint64_t n, u; const uint32_t A, NL, NZ; const int D; const bool permuted /* the classic lookup argument: steps 3 and 4 make A', S' and the lookups' z */, dev_m, dev_rng;
   const uint32_t batch_cap; const bool batch_cols, early_intt;   // steps 2 and 3: commitments per pass as the columns arrive; their coefficient copies made pass by pass
   ProofResult R; const Clock::time_point t_start; Clock::time_point tl; Transcript T; Committer C;
   halo2::RngKey rng_key; std::vector<Fr> ch; Fr x;
@@ -792,7 +792,7 @@ struct ProofRun {
 
   ProofRun(uint64_t h_g_, uint64_t h_g_lagrange_, const ProvingKey &pk_, const Circuit &wit_, const ProofOptions &opt_)
       : h_g(h_g_), h_g_lagrange(h_g_lagrange_), pk(pk_), wit(wit_), opt(opt_), P(*pk_.P), dom(*pk_.dom), k(P.k), Q(P.Q), n(P.n), u(P.usable), A(P.num_advice()), NL((uint32_t)P.lookups.size()),
-        NZ((uint32_t)P.perm.size()), D(std::max(1, std::min<int>(opt_.devices, (int)Q))), dev_m(opt_.device_multiplicities && NL > 0), dev_rng(opt_.device_randomness),
+        NZ((uint32_t)P.perm.size()), D(std::max(1, std::min<int>(opt_.devices, (int)Q))), permuted(P.permuted_lookups()), dev_m(opt_.device_multiplicities && NL > 0 && !permuted), dev_rng(opt_.device_randomness),
         batch_cap(opt_.commit_batch ? opt_.commit_batch : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (uint64_t(1) << 25) / n))), batch_cols(A >= 16 && batch_cap > 1),
         early_intt(opt_.early_intt < 0 ? A >= 8 : opt_.early_intt != 0), t_start(Clock::now()), tl(t_start),
         T(opt_.transcript == TranscriptKind::ByLayer ? reference_transcript(P) : opt_.transcript), C{T, R.msm, n} {
@@ -856,14 +856,14 @@ struct ProofRun {
   // ---- steps 1-3: the uploads start; commitments as the columns arrive; theta; the multiplicities; beta, gamma
   void witness_commits() {
     for (uint32_t i = 0; i < A; i++) uploads.push_back({P.phase0[0] + i, &wit.advice[i]});
-    if (!dev_m) for (uint32_t l = 0; l < NL; l++) uploads.push_back({P.phase0[1] + l, &wit.m[l]});
+    if (!dev_m && !permuted) for (uint32_t l = 0; l < NL; l++) uploads.push_back({P.phase0[1] + l, &wit.m[l]});
     if (!dev_rng) uploads.push_back({P.random_poly, &wit.random_poly});                   // step 5's polynomial (coefficients): needed last, crosses last
     for (const auto &up_ : uploads) poly[up_.first];
     poly[P.random_poly];
     poly[P.inst0];
-    for (uint32_t l = 0; l < NL; l++) poly[P.phase0[1] + l];
+    for (uint32_t l = 0; l < P.num_witness[1]; l++) poly[P.phase0[1] + l];
     for (const auto &c : P.perm) poly[c.z];                                               // every entry exists before the uploaders start: the map's structure does not change under them
-    for (const auto &l : P.lookups) poly[l.phi];
+    for (const auto &l : P.lookups) poly[l.permuted ? l.z : l.phi];
     {                                                                                     // step 1's input, made NOW: the instance column (public values, zero below).  Its few words must
       // cross PCIe before the uploader threads fill the copy stream: that stream is first-in first-out, and queued behind the witness this 1 KiB upload waited for the random polynomial
       // of step 5 (2 GiB at k = 26) -- 33 ms of host time in step 1 of every k = 26 proof until round 6 (17 ms at k = 25).  No device-wide synchronisation either: mi355_buf_upload
@@ -883,7 +883,8 @@ struct ProofRun {
              [this] { std::fill(arrived.begin(), arrived.end(), 1); cv.notify_all(); });
     commit_uploaded(0, A);                                                                // step 2
     squeeze_challenges(P.num_challenge[0]);                                               // theta
-    if (!dev_m) commit_uploaded(A, A + NL);                                               // step 3 (the multiplicities are the caller's: they do not depend on theta for the lookups halo2 compresses)
+    if (permuted) device_permuted_columns();                                              // step 3 of the classic lookup argument: A' and S' exist only on the device
+    else if (!dev_m) commit_uploaded(A, A + NL);                                          // step 3 (the multiplicities are the caller's: they do not depend on theta for the lookups halo2 compresses)
     else device_multiplicities();
     squeeze_challenges(P.num_challenge[1]);                                               // beta, gamma
   }
@@ -905,6 +906,33 @@ struct ProofRun {
         made.push_back(P.phase0[1] + l);
       }
       if (dev_rng) draw_blinding(made, RNG_STREAM_M_BLIND);
+      R.gate_launches += plan.launches;
+    }                                                                                     // the temporaries go before the commitments
+    R.multiplicity_ms = ms_since(t_m);
+    commit_columns(made, [](size_t) {});
+  }
+  // step 3 of upstream halo2's classic lookup argument [EXT-recalled halo2_proofs src/plonk/lookup/prover.rs, `commit_permuted`]: input and table compressed with theta as above,
+  // the permuted columns A' and S' built on the device over the usable rows (mi355_fr_lookup_permute_dev), the rng's blinding values into the rows from the l_last row on
+  // (blind + 1 per column: unlike a grand product, the l_last row is random too), A' then S' committed per lookup.  There is no host route and the circuit carries no column.
+  void device_permuted_columns() {
+    const auto t_m = Clock::now();
+    std::vector<uint32_t> made;
+    {
+      LagrangePlan plan(pk, "step 3", ch, [this](uint32_t p) { return poly.at(p).p; });
+      const uint64_t tail = (uint64_t)P.blind + 1;
+      for (uint32_t l = 0; l < NL; l++) {
+        const Lookup &lk = P.lookups[l];
+        plan.compress_lookup(lk);
+        DevicePoly a(n, 0), s(n, 0);
+        uint64_t missing = ~uint64_t(0);
+        const int rc = mi355_fr_lookup_permute_dev(a.p, s.p, plan.tmp_at(1).p, plan.tmp_at(0).p, u, &missing);
+        if (rc == MI355_EBADARG && missing != ~uint64_t(0)) throw Error(MI355_EBADARG, describe(VerifyFailure{VerifyFailure::Lookup, l, missing, 1, 0, 0, 0}));
+        check(rc);
+        check(mi355_buf_upload(a.at(u), wit.perm_blind.at(l).data(), tail * 32));
+        check(mi355_buf_upload(s.at(u), wit.perm_blind.at(l).data() + tail, tail * 32));
+        { std::lock_guard<std::mutex> lk_(up.mu); poly.at(lk.perm_input) = std::move(a); poly.at(lk.perm_table) = std::move(s); }
+        made.push_back(lk.perm_input); made.push_back(lk.perm_table);
+      }
       R.gate_launches += plan.launches;
     }                                                                                     // the temporaries go before the commitments
     R.multiplicity_ms = ms_since(t_m);
@@ -948,6 +976,24 @@ struct ProofRun {
       for (uint32_t l = 0; l < NL; l++) {                                                 // phi[i + 1] = phi[i] + 1 / (I + beta) - m / (T + beta)
         const Lookup &lk = P.lookups[l];
         cmp.tmp_base = 4; cmp.tmp_next = 0;
+        if (lk.permuted) {                                                                // z[0] = 1, z[i + 1] = z[i] (A + beta)(S + gamma) / ((A' + beta)(S' + gamma))
+          SoP ab = cmp.compile(*lk.input); ab.push_back(Term{beta, {}}); Compiler::merge_scalars(ab);
+          SoP sb = cmp.compile(*lk.table); sb.push_back(Term{gamma, {}}); Compiler::merge_scalars(sb);
+          cmp.emit(0, ab); cmp.emit(1, sb);
+          const Atom t0{A_TMP, 0, 0}, t1{A_TMP, 1, 0}, ap{A_POLY, lk.perm_input, 0}, sp{A_POLY, lk.perm_table, 0};
+          cmp.emit(2, SoP{Term{fr_one(), {t0, t1}}});
+          cmp.emit(3, SoP{Term{fr_one(), {ap, sp}}, Term{gamma, {ap}}, Term{beta, {sp}}, Term{fr_mul(beta, gamma), {}}});
+          plan.run();
+          check(mi355_fr_batch_invert_dev(plan.tmp_at(3).p, n));
+          check(mi355_fr_vec_op_dev(2, plan.tmp_at(2).p, plan.tmp_at(2).p, plan.tmp_at(3).p, n));
+          DevicePoly z(n, 0);
+          check(mi355_fr_prefix_product_dev(z.p, plan.tmp_at(2).p, n, nullptr));
+          Fr end{}; check(mi355_buf_download(end.data(), z.at(u), 32));                   // the product over the usable rows: one for columns that are permutations of the input and the table
+          if (!(end == fr_one())) throw Error(MI355_EBADARG, "create_proof: lookup " + std::to_string(l) + ": the grand product of the permuted columns does not return to one");
+          if (P.blind) check(mi355_buf_upload(z.at(u + 1), wit.lz_blind.at(l).data(), P.blind * 32));
+          poly.at(lk.z) = std::move(z); made.push_back(lk.z);
+          continue;
+        }
         SoP tb = cmp.compile(*lk.table); tb.push_back(Term{beta, {}}); Compiler::merge_scalars(tb);
         SoP ib = cmp.compile(*lk.input); ib.push_back(Term{beta, {}}); Compiler::merge_scalars(ib);
         cmp.emit(0, tb); cmp.emit(1, ib);
@@ -1172,6 +1218,12 @@ inline ProofResult create_proof(uint64_t h_g, uint64_t h_g_lagrange, const Provi
   // (a differing opt.devices would read a coset that sits on another device)
   if (pk.resident_cosets && pk.devices != std::max(1, opt.devices)) throw std::invalid_argument("create_proof: ProofOptions::devices (" + std::to_string(opt.devices) + ") differs from the proving key's (" + std::to_string(pk.devices) + ") while its coset parts are resident");
   if (opt.coset_group_polys != 0 && opt.coset_group_polys < PLAN_MAX_POLYS) throw std::invalid_argument("create_proof: ProofOptions::coset_group_polys must be 0 or at least " + std::to_string(PLAN_MAX_POLYS));
+  if (P.permuted_lookups()) {   // the classic lookup argument: A', S' and the lookups' z are made on the device; what the circuit carries is their blinding values
+    if (opt.device_randomness) throw std::invalid_argument("create_proof: ProofOptions::device_randomness is not available for a protocol with the classic (permuted) lookup argument");
+    if (std::max(1, opt.devices) > 1) throw std::invalid_argument("create_proof: ProofOptions::devices > 1 is not available for a protocol with the classic (permuted) lookup argument");
+    if (wit.perm_blind.size() != P.lookups.size() || wit.lz_blind.size() != P.lookups.size()) throw std::invalid_argument("create_proof: the classic lookup argument needs the blinding values of every lookup (Circuit::perm_blind, Circuit::lz_blind)");
+    for (size_t l = 0; l < P.lookups.size(); l++) if (wit.perm_blind[l].size() != 2 * ((size_t)P.blind + 1) || wit.lz_blind[l].size() != P.blind) throw std::invalid_argument("create_proof: Circuit::perm_blind holds 2 x (blind + 1) words per lookup and Circuit::lz_blind blind words");
+  }
   if (opt.check_witness) { CheckOptions co; co.threads = opt.threads; std::vector<VerifyFailure> bad = check_witness(pk, wit, co); if (!bad.empty()) throw WitnessError(std::move(bad)); }
   detail::ProofRun run(h_g, h_g_lagrange, pk, wit, opt);                                // the clock starts; the transcript takes the key's scalar and the instance values
   if (run.dev_rng) for (uint32_t i = 0; i < run.A; i++) if (wit.advice.at(i).size() < P.usable + 1) throw std::invalid_argument("create_proof: advice column " + std::to_string(i) + " has fewer than the usable rows + 1");

@@ -8,7 +8,8 @@
 //   vertical gates   q (a + a(wX) a(w^2 X) - a(w^3 X)), halo2-base's FlexGate: blocks of four rows, three free inputs, the output computed, q = 1 on the first
 //                    row of every used block (a densely used prefix of the column, the rest zero: how a real halo2-base column looks)
 //   assigned gates   s (P - t): t := P row by row, columns in index order (the synthetic inner circuit)
-//   lookups          inputs are drawn FROM the table (range table 0 .. 2^lookup_bits - 1, or W-column tuples), the multiplicities m counted
+//   lookups          inputs are drawn FROM the table (range table 0 .. 2^lookup_bits - 1, or W-column tuples), the multiplicities m counted; under the classic
+//                    (permuted) lookup argument there is no m: A', S' and z are the prover's, built on the device after theta, and only their blinding values are drawn
 //   copy constraints 2-cycles between free cells of different kinds (gate inputs, lookup-advice cells, fixed constants, instance cells); sigma follows
 //   blinding         the last `blind` rows of every advice / m column are random, as halo2 leaves them; z / phi blinding values and the random
 //                    polynomial of the vanishing argument are drawn here too (in halo2 the prover draws them from its rng during create_proof)
@@ -38,6 +39,8 @@ struct Circuit {
   std::vector<std::vector<uint32_t>> m_counts;   // the multiplicities as the integers they are (rows below the l_last row; the blinding rows of `m` are random field elements)
   std::vector<std::vector<Fr>> m_blind;           // per lookup the blinding rows u + 1 .. n - 1 of `m`: all a prover that counts the multiplicities itself needs of it
   std::vector<std::vector<Fr>> z_blind, phi_blind;
+  // permuted (classic) lookups only, per lookup: perm_blind = the blind + 1 last rows (from the l_last row on) of A', then those of S'; lz_blind = the blind last rows of its z
+  std::vector<std::vector<Fr>> perm_blind, lz_blind;
   Column random_poly;                 // coefficients
   std::vector<CopyPair> pairs; std::vector<PermColumn> pcols; std::vector<Fr> omega_pow;
   uint64_t gates_active = 0, lookup_rows = 0;
@@ -128,6 +131,7 @@ inline std::unique_ptr<Circuit> build_circuit(const Protocol &P, const CircuitOp
   const uint64_t n = P.n, u = P.usable; const uint32_t NI = std::min<uint64_t>(P.num_instance[0], u);
   const ColumnAllocator<Fr> alloc(opt.pinned);
   const uint32_t A = P.num_advice(), L = (uint32_t)P.lookups.size();
+  const bool permuted = P.permuted_lookups();
   auto adv_index = [&](uint32_t poly) -> int { return poly >= P.phase0[0] && poly < P.phase0[0] + A ? (int)(poly - P.phase0[0]) : -1; };
   // ---- roles
   for (const auto &ch : P.perm) for (const auto &c : ch.columns) C->pcols.push_back(c);
@@ -173,7 +177,7 @@ inline std::unique_ptr<Circuit> build_circuit(const Protocol &P, const CircuitOp
   // ---- columns
   C->pre.resize(P.num_pre, Column(alloc));
   for (uint32_t a = 0; a < A; a++) { C->advice.emplace_back(alloc); C->advice.back().assign(n, fr_zero()); }
-  for (uint32_t l = 0; l < L; l++) { C->m.emplace_back(alloc); C->m.back().assign(n, fr_zero()); }
+  if (!permuted) for (uint32_t l = 0; l < L; l++) { C->m.emplace_back(alloc); C->m.back().assign(n, fr_zero()); }
   auto pre_col = [&](uint32_t p) -> Column & { if (C->pre[p].empty()) C->pre[p].assign(n, fr_zero()); return C->pre[p]; };
   Rng top(opt.seed * 0x9E3779B97F4A7C15ull + 12345);
   { Rng g(top.next()); C->instances.resize(NI); for (auto &v : C->instances) v = h2d::from_fe(zk::Fr::from_canonical(h2d::to_fe(Fr{{g.next(), g.next() & 0xffffff, 0, 0}}))); }   // 88-bit values, like the accumulator limbs of the fixtures' instances
@@ -275,7 +279,7 @@ inline std::unique_ptr<Circuit> build_circuit(const Protocol &P, const CircuitOp
     C->parallel(u, [&](uint64_t lo, uint64_t hi) { for (uint64_t i = lo; i < hi; i++) if (!fr_is_zero(sel[i])) t[i] = ev.at(i, n); });
   }
   // ---- multiplicities
-  for (uint32_t l = 0; l < L; l++) {
+  for (uint32_t l = 0; l < L && !permuted; l++) {
     std::vector<uint32_t> cnt(table_rows, 0);
     const auto &ix = idx[lk[l].group];
     for (uint64_t i = 0; i < u; i++) cnt[ix[i]]++;       // rows a selector switches off read the all-zero tuple = table row 0, which idx holds there
@@ -289,8 +293,13 @@ inline std::unique_ptr<Circuit> build_circuit(const Protocol &P, const CircuitOp
   for (uint32_t p = 0; p < P.num_pre; p++) { bool sig = false; for (const auto &c : C->pcols) sig = sig || c.sigma == p; if (!sig) (void)pre_col(p); }
   C->omega_pow.resize(n);
   { const int T = C->threads; std::vector<std::thread> th; for (int t = 0; t < T; t++) th.emplace_back([&, t]() { const uint64_t lo = n * t / T, hi = n * (t + 1) / T; Fr w = fr_pow(P.omega, lo); for (uint64_t i = lo; i < hi; i++) { C->omega_pow[i] = w; w = fr_mul(w, P.omega); } }); for (auto &t : th) t.join(); }
-  { Rng g(blind_stream()); C->z_blind.assign(P.perm.size(), std::vector<Fr>(P.blind)); for (auto &v : C->z_blind) for (auto &x : v) x = opt.zero_blinding ? fr_zero() : g.uniform(); C->phi_blind.assign(L, std::vector<Fr>(P.blind)); for (auto &v : C->phi_blind) for (auto &x : v) x = opt.zero_blinding ? fr_zero() : g.uniform(); }
+  { Rng g(blind_stream()); C->z_blind.assign(P.perm.size(), std::vector<Fr>(P.blind)); for (auto &v : C->z_blind) for (auto &x : v) x = opt.zero_blinding ? fr_zero() : g.uniform(); C->phi_blind.assign(permuted ? 0 : L, std::vector<Fr>(P.blind)); for (auto &v : C->phi_blind) for (auto &x : v) x = opt.zero_blinding ? fr_zero() : g.uniform(); }
   { C->random_poly = Column(alloc); C->random_poly.resize(n); const uint64_t sd = blind_stream();   /* the random polynomial stays random under zero_blinding (its commitment must not be the identity) */ C->parallel(n, [&](uint64_t lo, uint64_t hi) { Rng g(sd + lo * 7919); for (uint64_t i = lo; i < hi; i++) C->random_poly[i] = g.uniform(); }); }
+  if (permuted) {   // behind every other draw of the blinding stream
+    Rng g(blind_stream());
+    C->perm_blind.assign(L, std::vector<Fr>(2 * (P.blind + 1))); C->lz_blind.assign(L, std::vector<Fr>(P.blind));
+    for (uint32_t l = 0; l < L; l++) { for (auto &x : C->perm_blind[l]) x = opt.zero_blinding ? fr_zero() : g.uniform(); for (auto &x : C->lz_blind[l]) x = opt.zero_blinding ? fr_zero() : g.uniform(); }
+  }
   return C;
 }
 
@@ -314,6 +323,10 @@ inline void dump_circuit(const Circuit &C, const std::string &dir, const Fr &tau
   b.clear(); s.clear(); for (const auto &c : C.z_blind) { b.push_back(c.data()); s.push_back(c.size() * 32); } wr("z_blind.bin", b, s);
   b.clear(); s.clear(); for (const auto &c : C.phi_blind) { b.push_back(c.data()); s.push_back(c.size() * 32); } wr("phi_blind.bin", b, s);
   wr("random.bin", {C.random_poly.data()}, {P.n * 32});
+  if (P.permuted_lookups()) {
+    b.clear(); s.clear(); for (const auto &c : C.perm_blind) { b.push_back(c.data()); s.push_back(c.size() * 32); } wr("perm_blind.bin", b, s);
+    b.clear(); s.clear(); for (const auto &c : C.lz_blind) { b.push_back(c.data()); s.push_back(c.size() * 32); } wr("lz_blind.bin", b, s);
+  }
   { std::ifstream in(protocol_path, std::ios::binary); std::ofstream out(dir + "/protocol.json", std::ios::binary); out << in.rdbuf(); }
   const Fr tc = fr_to_canonical(tau); char hex[65];
   std::snprintf(hex, sizeof hex, "%016llx%016llx%016llx%016llx", (unsigned long long)tc[3], (unsigned long long)tc[2], (unsigned long long)tc[1], (unsigned long long)tc[0]);

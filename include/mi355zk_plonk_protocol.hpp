@@ -9,9 +9,12 @@
 // it builds the argument polynomials [EXT-recalled halo2_proofs plonk/permutation/prover.rs, plonk/mv_lookup/prover.rs]:
 //   permutation chunks   l_active (z(wX) prod_j (c_j + beta sigma_j + gamma) - z(X) prod_j (c_j + beta delta^j X + gamma))
 //   lookups              l_active ((T + beta)(I + beta)(phi(wX) - phi(X)) - ((T + beta) - m (I + beta))),  T / I theta-compressed table / input
+//   permuted lookups     l_active (z(wX)(A' + beta)(S' + gamma) - z(X)(A + beta)(S + gamma)), then l_0 (A' - S') and l_active (A' - S')(A' - A'(w^-1 X)): the classic
+//                        halo2 argument of upstream PSE / zcash halo2 [EXT-recalled snark-verifier system/halo2.rs, lookup_constraints]; A / S theta-compressed input / table
 //   gates                everything else, as  selector * (P - target)
 // The quotient itself is NOT built from the recognised structure: mi355zk_plonk.hpp compiles the tree as it stands.  Host-only code, no device calls.
-// Polynomial numbering (snark-verifier): [preprocessed | instance | witness phase 0 (advice) | phase 1 (lookup m) | phase 2 (z.., phi.., random) | quotient].
+// Polynomial numbering (snark-verifier): [preprocessed | instance | witness phase 0 (advice) | phase 1 (lookup m) | phase 2 (z.., phi.., random) | quotient]; with permuted
+// lookups phase 1 holds A'_0, S'_0, A'_1, S'_1, ... and phase 2 the permutation z's, one z per lookup, random.  One protocol holds lookups of one kind.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -163,7 +166,8 @@ inline void flatten_product(const Expr &e, std::vector<const Expr *> &out) { if 
 struct PolyRot { uint32_t poly; int32_t rot; bool operator<(const PolyRot &o) const { return poly != o.poly ? poly < o.poly : rot < o.rot; } bool operator==(const PolyRot &o) const { return poly == o.poly && rot == o.rot; } };
 struct PermColumn { uint32_t column, sigma; Fr delta_pow; };
 struct PermChunk { uint32_t z; std::vector<PermColumn> columns; };
-struct Lookup { uint32_t phi, m; const Expr *table, *input; };          // table / input: the theta-compressed DistributePowers nodes (or a single expression)
+// table / input: the theta-compressed DistributePowers nodes (or a single expression).  mv-lookup: phi, m.  permuted (classic) lookup: z the grand product, perm_input / perm_table = A' / S'
+struct Lookup { uint32_t phi, m; const Expr *table, *input; bool permuted = false; uint32_t z = 0, perm_input = 0, perm_table = 0; };
 struct Gate { const Expr *expr; uint32_t selector; const Expr *p; PolyRot target; bool assignable; };   // selector * (p - target) when assignable
 
 struct Protocol {
@@ -188,6 +192,7 @@ struct Protocol {
 
   uint32_t num_sigma() const { uint32_t s = 0; for (const auto &c : perm) s += (uint32_t)c.columns.size(); return s; }
   uint32_t num_advice() const { return num_witness.at(0); }
+  bool permuted_lookups() const { return !lookups.empty() && lookups[0].permuted; }   // the classic halo2 lookup argument (never mixed with mv-lookups: recognise())
   uint32_t commitments() const { uint32_t s = Q + 2; for (auto w : num_witness) s += w; return s; }
   bool is_pre(uint32_t p) const { return p < num_pre; }
   bool is_instance(uint32_t p) const { return p >= inst0 && p < wit0; }
@@ -235,16 +240,44 @@ struct Protocol {
     last_rot = 0; for (auto l : lag) last_rot = std::min(last_rot, l);
     if (last_rot >= -1) throw std::invalid_argument("protocol: no l_last in the numerator");
     blind = (uint32_t)(-last_rot - 1); usable = n - (uint64_t)(-last_rot);
+    // a permuted lookup's constraint 3 opens it; its constraints 4, l_0 (A' - S'), and 5, l_active (A' - S')(A' - A'(w^-1 X)), must follow and name the same A' and S'
+    int open_stage = 0;   // 0: none open; 1: constraint 4 is due; 2: constraint 5 is due
+    auto is_diff = [](const Expr &e, int32_t p, int32_t q, int32_t q_rot) { return e.kind == Expr::SUM && e.kids[0].is_poly(p, 0) && e.kids[1].kind == Expr::NEG && e.kids[1].kids[0].is_poly(q, q_rot); };
     for (size_t ci = 0; ci + 1 < numerator.kids.size(); ci++) {
       const Expr &c = numerator.kids[ci];
       if (c.kind != Expr::PROD) throw std::invalid_argument("protocol: constraint " + std::to_string(ci) + " is not a product");
       const Expr &a = c.kids[0], &b = c.kids[1];
+      if (open_stage == 1) {
+        const Lookup &lk = lookups.back();
+        if (a.kind != Expr::LAGRANGE || a.i != 0 || !is_diff(b, (int32_t)lk.perm_input, (int32_t)lk.perm_table, 0))
+          throw std::invalid_argument("protocol: permuted lookup " + std::to_string(lookups.size() - 1) + ": constraint l_0 (A' - S') does not follow or names other columns");
+        open_stage = 2; continue;
+      }
+      if (open_stage == 2) {
+        const Lookup &lk = lookups.back();
+        bool common5 = false;
+        if (!(is_common_linear(a, &common5) && common5) || b.kind != Expr::PROD || !is_diff(b.kids[0], (int32_t)lk.perm_input, (int32_t)lk.perm_table, 0) || !is_diff(b.kids[1], (int32_t)lk.perm_input, (int32_t)lk.perm_input, -1))
+          throw std::invalid_argument("protocol: permuted lookup " + std::to_string(lookups.size() - 1) + ": constraint l_active (A' - S')(A' - A'(w^-1 X)) does not follow or names other columns");
+        open_stage = 0; continue;
+      }
       if (a.kind == Expr::LAGRANGE) continue;   // l_0 / l_last boundary constraints: implied by how z and phi are built
       bool common = false;
       if (is_common_linear(a, &common) && common) {
         if (b.kind != Expr::SUM || b.kids[0].kind != Expr::PROD || b.kids[1].kind != Expr::NEG) throw std::invalid_argument("protocol: unrecognised l_active constraint");
         const Expr &l0 = b.kids[0].kids[0], &l1 = b.kids[0].kids[1], &neg = b.kids[1].kids[0];
-        if (l0.kind == Expr::POLY && l0.rot == 1) {           // permutation chunk
+        // (A' + beta)(S' + gamma) behind z(wX): no permutation factor has a polynomial where A' stands (its first summand is a sum)
+        const bool permuted = l0.kind == Expr::POLY && l0.rot == 1 && l1.kind == Expr::PROD && l1.kids[0].kind == Expr::SUM && l1.kids[0].kids[0].kind == Expr::POLY && l1.kids[0].kids[1].is_challenge(1);
+        if (permuted) {                                       // permuted (classic) lookup, constraint 3
+          auto bad = [&]() { throw std::invalid_argument("protocol: unrecognised permuted lookup constraint"); };
+          const Expr &ap = l1.kids[0].kids[0], &sb = l1.kids[1];
+          if (ap.rot != 0 || sb.kind != Expr::SUM || sb.kids[0].kind != Expr::POLY || sb.kids[0].rot != 0 || !sb.kids[1].is_challenge(2)) bad();
+          if (neg.kind != Expr::PROD || !neg.kids[0].is_poly(l0.i, 0) || neg.kids[1].kind != Expr::PROD) bad();
+          const Expr &ab = neg.kids[1].kids[0], &tb = neg.kids[1].kids[1];   // (A + beta), (S + gamma)
+          if (ab.kind != Expr::SUM || tb.kind != Expr::SUM || !ab.kids[1].is_challenge(1) || !tb.kids[1].is_challenge(2)) bad();
+          Lookup lk{0, 0, &tb.kids[0], &ab.kids[0]};
+          lk.permuted = true; lk.z = (uint32_t)l0.i; lk.perm_input = (uint32_t)ap.i; lk.perm_table = (uint32_t)sb.kids[0].i;
+          lookups.push_back(lk); open_stage = 1;
+        } else if (l0.kind == Expr::POLY && l0.rot == 1) {    // permutation chunk
           PermChunk ch; ch.z = (uint32_t)l0.i;
           if (neg.kind != Expr::PROD || !neg.kids[0].is_poly(l0.i, 0)) throw std::invalid_argument("protocol: permutation chunk: z(X) side");
           std::vector<const Expr *> fs, fi; flatten_product(l1, fs); flatten_product(neg.kids[1], fi);
@@ -277,10 +310,20 @@ struct Protocol {
       }
       gates.push_back(g);
     }
+    if (open_stage) throw std::invalid_argument("protocol: permuted lookup " + std::to_string(lookups.size() - 1) + ": the numerator ends before its last constraint");
     if (perm.empty()) throw std::invalid_argument("protocol: no permutation argument recognised");
-    if (num_witness[1] != lookups.size() || num_witness[2] != perm.size() + lookups.size() + 1) throw std::invalid_argument("protocol: num_witness does not match the recognised arguments");
+    size_t n_permuted = 0; for (const auto &l : lookups) n_permuted += l.permuted ? 1 : 0;
+    if (n_permuted && n_permuted != lookups.size()) throw std::invalid_argument("protocol: mv-lookups and permuted lookups in one protocol (" + std::to_string(lookups.size() - n_permuted) + " and " + std::to_string(n_permuted) + "): one kind per protocol is supported");
+    if (n_permuted) {
+      if (num_witness[1] != 2 * lookups.size()) throw std::invalid_argument("protocol: num_witness[1] = " + std::to_string(num_witness[1]) + " does not match " + std::to_string(lookups.size()) + " permuted lookups (A' and S' each: " + std::to_string(2 * lookups.size()) + ")");
+      if (num_witness[2] != perm.size() + lookups.size() + 1) throw std::invalid_argument("protocol: num_witness does not match the recognised arguments");
+    } else if (num_witness[1] != lookups.size() || num_witness[2] != perm.size() + lookups.size() + 1) throw std::invalid_argument("protocol: num_witness does not match the recognised arguments");
     for (size_t c = 0; c < perm.size(); c++) if (perm[c].z != phase0[2] + c) throw std::invalid_argument("protocol: grand products out of order");
-    for (size_t l = 0; l < lookups.size(); l++) if (lookups[l].phi != phase0[2] + perm.size() + l || lookups[l].m != phase0[1] + l) throw std::invalid_argument("protocol: lookup polynomials out of order");
+    for (size_t l = 0; l < lookups.size(); l++) {
+      const Lookup &lk = lookups[l];
+      if (lk.permuted ? lk.z != phase0[2] + perm.size() + l || lk.perm_input != phase0[1] + 2 * l || lk.perm_table != phase0[1] + 2 * l + 1 : lk.phi != phase0[2] + perm.size() + l || lk.m != phase0[1] + l)
+        throw std::invalid_argument("protocol: lookup polynomials out of order");
+    }
   }
 };
 

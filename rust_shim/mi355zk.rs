@@ -105,6 +105,7 @@ extern "C" {
     pub fn mi355_fr_prefix_sum_dev(dst_dev: *mut c_void, src_dev: *const c_void, n: u64, total_out_host: *mut c_void) -> c_int;
     pub fn mi355_fr_lookup_multiplicities_dev(m_dev: *mut c_void, n: u64, table_dev: *const c_void, table_rows: u64, inputs_dev: *const *const c_void,
                                               n_inputs: u32, input_rows: u64, flags: u32, missing_out: *mut u64) -> c_int;
+    pub fn mi355_fr_lookup_permute_dev(perm_input: *mut c_void, perm_table: *mut c_void, input: *const c_void, table: *const c_void, rows: u64, missing_out: *mut u64) -> c_int;
     pub fn mi355_fr_permutation_sigma_dev(sigma_dev: *const *mut c_void, n_cols: u32, log_n: u32, delta: *const c_void, omega: *const c_void,
                                           cells_host: *const u64, images_host: *const u64, count: u64, flags: u32) -> c_int;
     pub fn mi355_fr_nonzero_rows_dev(vecs_dev: *const *const c_void, batch: u32, n: u64, cap: u32, counts_out_host: *mut u64, rows_out_host: *mut u64) -> c_int;

@@ -96,6 +96,7 @@ SIGNATURES = {
     "mi355_fr_prefix_product_dev": (_int, [_vp, _vp, _u64, _vp]),
     "mi355_fr_prefix_sum_dev": (_int, [_vp, _vp, _u64, _vp]),
     "mi355_fr_lookup_multiplicities_dev": (_int, [_vp, _u64, _vp, _u64, C.POINTER(_vp), _u32, _u64, _u32, C.POINTER(_u64)]),
+    "mi355_fr_lookup_permute_dev": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "mi355_fr_permutation_sigma_dev": (_int, [C.POINTER(_vp), _u32, _u32, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64), _u64, _u32]),
     "mi355_fr_nonzero_rows_dev": (_int, [C.POINTER(_vp), _u32, _u64, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "mi355_fr_copy_check_dev": (_int, [C.POINTER(_vp), _u32, _u32, C.POINTER(_u64), C.POINTER(_u64), _u64, _u32, C.POINTER(_u64), C.POINTER(_u64)]),

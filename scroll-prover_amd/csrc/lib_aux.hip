@@ -11,6 +11,7 @@
 #include "frscan.hpp"
 #include "g2.hpp"
 #include "lookup.hpp"
+#include "lookup_permute.hpp"
 #include "perm.hpp"
 #include "g1codec.hpp"
 #include "check.hpp"
@@ -171,6 +172,16 @@ template <bool ADD> int prefix_scan_entry(void *dst_dev, const void *src_dev, ui
   if (total_out_host) { HIPCHK(hipMemcpyAsync(total_out_host, total, sizeof(fe_t), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
   return MI355_OK;
   });
+}
+
+// scan of n u32 under OP (0: sum, 1: max) for mi355_fr_lookup_permute_dev (lookup_permute.hpp; in may be out); aux: room for the totals of every level (lp_scan_aux_words)
+static uint64_t lp_scan_aux_words(uint64_t n) { uint64_t w = 0; while (n > 1) { n = (n + LP_SCAN_TILE - 1) / LP_SCAN_TILE; w += n; } return w + 1; }
+template <int OP, bool INCL> static void lp_scan(const uint32_t *in, uint32_t *out, uint64_t n, uint32_t *aux, hipStream_t s) {
+  const uint32_t tiles = ceil_div(n, LP_SCAN_TILE);
+  hipLaunchKernelGGL((k_lp_scan_tile<OP, INCL>), dim3(tiles), dim3(LP_THREADS), 0, s, in, out, n, aux);
+  if (tiles <= 1) return;
+  lp_scan<OP, false>(aux, aux, tiles, aux + tiles, s);
+  hipLaunchKernelGGL(k_lp_scan_fix<OP>, dim3(tiles), dim3(LP_THREADS), 0, s, out, n, (const uint32_t *)aux);
 }
 
 extern "C" {
@@ -497,6 +508,103 @@ int mi355_fr_lookup_multiplicities_dev(void *m_dev, uint64_t n, const void *tabl
     if (missing_out) *missing_out = err_host;
     return fail(MI355_EBADARG, "fr_lookup_multiplicities: input " + std::to_string(err_host >> 40) + ", row " + std::to_string(err_host & ((1ull << 40) - 1)) + " is not in the table");
   }
+  return finish_async();
+  });
+}
+
+// ---- the permuted columns A' and S' of the classic lookup argument (lookup_permute.hpp).  The argument checks read host memory and the buffer registry only and
+// come before the device is asked for.  Workspace: ONE pooled mi355_buf block (PoolBlock; WsLayout): two header blocks, 4 B per hash slot (the next power of two
+// >= 2 x rows), two counts per row, two (key word, row) ping-pong pairs per row -- the key words serve again as the run / owner maps of the expansion --, five
+// u32 per row of scans, 1 KiB of histogram per 2 048 rows and the totals of the scans: 52 .. 60 B per row.  Synchronous, two synchronisations: one after the
+// counts (the missing row, the number of distinct values and the digits that need a pass come back), one at the end.
+int mi355_fr_lookup_permute_dev(void *perm_input, void *perm_table, const void *input, const void *table, uint64_t rows, uint64_t *missing_out) {
+  return guarded([&]() -> int {
+  if (missing_out) *missing_out = ~0ull;
+  if (rows >= (1ull << 31)) return fail(MI355_EBADARG, "fr_lookup_permute: rows must be < 2^31");
+  const uint64_t bytes = rows * sizeof(fe_t);
+  if (rows) {
+    if (!perm_input || !perm_table || !input || !table) return fail(MI355_EBADARG, "fr_lookup_permute: null pointer");
+    if (((uintptr_t)perm_input | (uintptr_t)perm_table | (uintptr_t)input | (uintptr_t)table) & 15) return fail(MI355_EBADARG, "fr_lookup_permute: device pointers must be 16-byte aligned");
+    if (ranges_overlap(perm_input, bytes, perm_table, bytes)) return fail(MI355_EBADARG, "fr_lookup_permute: the two outputs must not overlap");
+    for (const void *out : {(const void *)perm_input, (const void *)perm_table})
+      if (ranges_overlap(out, bytes, input, bytes) || ranges_overlap(out, bytes, table, bytes)) return fail(MI355_EBADARG, "fr_lookup_permute: an output must not overlap an input");
+    for (const void *p : {(const void *)perm_input, (const void *)perm_table, input, table}) CHK(buf_check_range(p, bytes, "fr_lookup_permute"));
+  }
+  int slot; CHK(common_slot({perm_input, perm_table, input, table}, &slot, "fr_lookup_permute"));
+  DevGuard lk(slot);
+  CHK(need_init(slot));
+  if (rows == 0) return MI355_OK;
+  const uint64_t S = std::max<uint64_t>(64, 1ull << log2_ceil(2 * rows));
+  const uint32_t mask = (uint32_t)(S - 1), nblk_max = ceil_div(rows, LP_CHUNK);
+  const uint64_t hist_words = 256ull * nblk_max;
+  WsLayout L;
+  const uint64_t off_ones = L.take(sizeof(LpHeadOnes)), off_slots = L.take(S * 4), off_zero = L.take(sizeof(LpHeadZero)), off_tcnt = L.take(rows * 4), off_icnt = L.take(rows * 4), off_end_zero = L.total();
+  uint64_t off_key[2], off_val[2], off_arr[5];
+  for (int i = 0; i < 2; i++) { off_key[i] = L.take(rows * 4); off_val[i] = L.take(rows * 4); }
+  for (int i = 0; i < 5; i++) off_arr[i] = L.take(rows * 4);
+  const uint64_t off_hist = L.take(hist_words * 4), off_aux = L.take(lp_scan_aux_words(std::max<uint64_t>(rows, hist_words)) * 4);
+  PoolBlock ws; CHK(ws.alloc(L.total(), slot));
+  hipStream_t s = g.stream;
+  LpHeadOnes *ones = (LpHeadOnes *)ws.at(off_ones), ones_host; LpHeadZero *zero = (LpHeadZero *)ws.at(off_zero), zero_host;
+  uint32_t *slots = (uint32_t *)ws.at(off_slots), *tcnt = (uint32_t *)ws.at(off_tcnt), *icnt = (uint32_t *)ws.at(off_icnt), *hist = (uint32_t *)ws.at(off_hist), *aux = (uint32_t *)ws.at(off_aux);
+  uint32_t *key[2] = {(uint32_t *)ws.at(off_key[0]), (uint32_t *)ws.at(off_key[1])}, *val[2] = {(uint32_t *)ws.at(off_val[0]), (uint32_t *)ws.at(off_val[1])};
+  uint32_t *in_cells = (uint32_t *)ws.at(off_arr[0]), *left = (uint32_t *)ws.at(off_arr[1]), *heads = (uint32_t *)ws.at(off_arr[2]), *run_start = (uint32_t *)ws.at(off_arr[3]), *left_start = (uint32_t *)ws.at(off_arr[4]);
+  const fe_t *T = (const fe_t *)table, *A = (const fe_t *)input;
+  HIPCHK(hipMemsetAsync(ws.at(off_ones), 0xff, off_zero - off_ones, s));       // the error words, the AND of the keys, the empty slots
+  HIPCHK(hipMemsetAsync(ws.at(off_zero), 0, off_end_zero - off_zero, s));      // the number of distinct values, the OR of the keys, the counts
+  {
+    Scope sc("lookup_permute");
+    hipLaunchKernelGGL(k_lk_insert<false>, dim3(grid_blocks(rows, LK_THREADS)), dim3(LK_THREADS), 0, s, T, rows, slots, mask);
+    const uint64_t wave_rows = std::max<uint64_t>(2048, (ceil_div(rows, 8192) + 63) & ~63ull);
+    const dim3 probe_grid(ceil_div(ceil_div(rows, wave_rows), LK_THREADS / 64));
+    hipLaunchKernelGGL(k_lk_probe, probe_grid, dim3(LK_THREADS), 0, s, T, rows, (uint64_t)0, T, (const uint32_t *)slots, mask, tcnt, &ones->err_table, wave_rows);
+    hipLaunchKernelGGL(k_lk_probe, probe_grid, dim3(LK_THREADS), 0, s, A, rows, (uint64_t)0, T, (const uint32_t *)slots, mask, icnt, &ones->err, wave_rows);
+    hipLaunchKernelGGL(k_lp_compact, dim3(grid_blocks(rows, LP_THREADS, 8)), dim3(LP_THREADS), 0, s, T, rows, (const uint32_t *)tcnt, val[0], ones, zero);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&ones_host, ones, sizeof ones_host, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&zero_host, zero, sizeof zero_host, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (ones_host.err != ~0ull) {
+    if (missing_out) *missing_out = ones_host.err;
+    return fail(MI355_EBADARG, "fr_lookup_permute: input row " + std::to_string(ones_host.err) + " is not in the table");
+  }
+  const uint32_t D = zero_host.distinct;
+  if (D == 0 || D > rows || ones_host.err_table != ~0ull) return fail(MI355_EHIP, "fr_lookup_permute: the table's hash set is inconsistent");
+  {
+    Scope sc("lookup_permute");
+    // LSD radix sort of the distinct values by canonical key; the passes that would move nothing are skipped
+    const uint32_t nblk = ceil_div(D, LP_CHUNK);
+    int cur = 0;
+    for (uint32_t word = 0; word < 8; word++) {
+      if (ones_host.key_and[word] == zero_host.key_or[word]) continue;
+      hipLaunchKernelGGL(k_lp_gather, dim3(grid_blocks(D, LP_THREADS)), dim3(LP_THREADS), 0, s, T, rows, (const uint32_t *)val[cur], D, word, key[cur]);
+      for (uint32_t pass = 4 * word; pass < 4 * word + 4; pass++) {
+        if (!lp_pass_needed(ones_host.key_and, zero_host.key_or, pass)) continue;
+        Scope one_pass("lookup_permute_pass");   // its launch count in the profile is the number of passes that ran
+        hipLaunchKernelGGL(k_lp_hist, dim3(nblk), dim3(LP_THREADS), 0, s, (const uint32_t *)key[cur], D, pass, hist, nblk);
+        lp_scan<0, false>(hist, hist, 256ull * nblk, aux, s);
+        hipLaunchKernelGGL(k_lp_scatter, dim3(nblk), dim3(LP_THREADS), 0, s, (const uint32_t *)key[cur], (const uint32_t *)val[cur], key[cur ^ 1], val[cur ^ 1], D, pass, (const uint32_t *)hist, nblk);
+        cur ^= 1;
+      }
+    }
+    const uint32_t *sorted = val[cur];
+    uint32_t *run_of_row = key[0], *owner_of_left = key[1];   // the key words are done with
+    const dim3 gd(grid_blocks(D, LP_THREADS));
+    hipLaunchKernelGGL(k_lp_counts, gd, dim3(LP_THREADS), 0, s, sorted, D, rows, (const uint32_t *)tcnt, (const uint32_t *)icnt, in_cells, left, heads);
+    lp_scan<0, false>(in_cells, run_start, D, aux, s);
+    lp_scan<0, false>(left, left_start, D, aux, s);
+    lp_scan<0, false>(heads, heads, D, aux, s);               // heads[i]: the runs in front of run i
+    HIPCHK(hipMemsetAsync(run_of_row, 0, rows * 4, s));
+    HIPCHK(hipMemsetAsync(owner_of_left, 0, rows * 4, s));
+    hipLaunchKernelGGL(k_lp_mark, gd, dim3(LP_THREADS), 0, s, D, rows, (const uint32_t *)in_cells, (const uint32_t *)left, (const uint32_t *)run_start, (const uint32_t *)left_start, run_of_row, owner_of_left);
+    lp_scan<1, true>(run_of_row, run_of_row, rows, aux, s);
+    lp_scan<1, true>(owner_of_left, owner_of_left, rows, aux, s);
+    hipLaunchKernelGGL(k_lp_expand, dim3(grid_blocks(rows, LP_THREADS)), dim3(LP_THREADS), 0, s, T, sorted, rows, D, (const uint32_t *)run_of_row, (const uint32_t *)owner_of_left,
+                       (const uint32_t *)run_start, (const uint32_t *)heads, (const uint32_t *)left_start, (const uint32_t *)left, (fe_t *)perm_input, (fe_t *)perm_table);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
   return finish_async();
   });
 }

@@ -155,6 +155,8 @@ bool fixed_part(Circuit &C, const std::string &what, uint32_t index, Span &out) 
   if (what == "m_blind") { index_below(index, C.m_blind.size(), "m_blind"); out = {C.m_blind[index].data(), bl}; return true; }
   if (what == "z_blind") { index_below(index, C.z_blind.size(), "z_blind"); out = {C.z_blind[index].data(), bl}; return true; }
   if (what == "phi_blind") { index_below(index, C.phi_blind.size(), "phi_blind"); out = {C.phi_blind[index].data(), bl}; return true; }
+  if (what == "perm_blind") { index_below(index, C.perm_blind.size(), "perm_blind"); out = {C.perm_blind[index].data(), 2 * (bl + 32)}; return true; }
+  if (what == "lz_blind") { index_below(index, C.lz_blind.size(), "lz_blind"); out = {C.lz_blind[index].data(), bl}; return true; }
   if (what == "random_poly") { index_below(index, 1, "random_poly"); out = {C.random_poly.data(), col}; return true; }
   return false;
 }
@@ -166,14 +168,19 @@ void check_shape(const Circuit &C) {
   for (uint32_t p = 0; p < P.num_pre; p++) if (!C.is_sigma(p) && C.pre[p].size() != n) bad("preprocessed");
   if (C.advice.size() != P.num_advice()) bad("advice");
   for (const auto &c : C.advice) if (c.size() != n) bad("advice");
-  if (C.m.size() != L || C.m_counts.size() != L || C.m_blind.size() != L || C.phi_blind.size() != L || C.z_blind.size() != P.perm.size()) bad("the lookup / permutation parts");
-  for (size_t l = 0; l < L; l++) if (C.m[l].size() != n || C.m_counts[l].size() != n || C.m_blind[l].size() != P.blind || C.phi_blind[l].size() != P.blind) bad("a lookup part");
+  if (P.permuted_lookups()) {   // no m and no phi: the blinding values of A', S' and the lookups' z
+    if (C.perm_blind.size() != L || C.lz_blind.size() != L || C.z_blind.size() != P.perm.size()) bad("the lookup / permutation parts");
+    for (size_t l = 0; l < L; l++) if (C.perm_blind[l].size() != 2 * ((size_t)P.blind + 1) || C.lz_blind[l].size() != P.blind) bad("a lookup part");
+  }
+  else if (C.m.size() != L || C.m_counts.size() != L || C.m_blind.size() != L || C.phi_blind.size() != L || C.z_blind.size() != P.perm.size()) bad("the lookup / permutation parts");
+  for (size_t l = 0; l < L && !P.permuted_lookups(); l++) if (C.m[l].size() != n || C.m_counts[l].size() != n || C.m_blind[l].size() != P.blind || C.phi_blind[l].size() != P.blind) bad("a lookup part");
   for (const auto &z : C.z_blind) if (z.size() != P.blind) bad("z_blind");
   if (C.random_poly.size() != n || C.omega_pow.size() != n || C.instances.size() > n) bad("random_poly / instances");
 }
 std::unique_ptr<Circuit> empty_circuit(const Protocol &P) {
   auto C = std::make_unique<Circuit>(); C->pr = &P;
-  const uint64_t n = P.n; const size_t L = P.lookups.size();
+  const uint64_t n = P.n; const size_t L = P.permuted_lookups() ? 0 : P.lookups.size();
+  if (P.permuted_lookups()) { C->perm_blind.assign(P.lookups.size(), std::vector<Fr>(2 * ((size_t)P.blind + 1), fr_zero())); C->lz_blind.assign(P.lookups.size(), std::vector<Fr>(P.blind, fr_zero())); }
   for (const auto &ch : P.perm) for (const auto &c : ch.columns) C->pcols.push_back(c);
   C->pre.resize(P.num_pre);
   for (uint32_t p = 0; p < P.num_pre; p++) if (!C->is_sigma(p)) C->pre[p].assign(n, fr_zero());
@@ -214,6 +221,7 @@ uint64_t protocol_field(const Protocol &P, const std::string &f) {
   if (f == "proof_bytes_evm") return points * 64 + ev * 32;
   if (f == "has_initial_state") return P.has_initial_state ? 1 : 0;
   if (f == "has_accumulator") return P.has_accumulator ? 1 : 0;
+  if (f == "lookup_permuted") return P.permuted_lookups() ? 1 : 0;
   throw std::invalid_argument("unknown protocol field '" + capi::Options::printable(f.c_str()) + "'");
 }
 }  // namespace

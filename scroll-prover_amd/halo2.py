@@ -339,6 +339,27 @@ def lookup_multiplicities(table, inputs, table_rows: int, input_rows: int, last:
     return m
 
 
+def lookup_permute(input, table, rows: int, perm_input=None, perm_table=None):
+    """the permuted columns (A', S') of the classic halo2 lookup argument (mi355_fr_lookup_permute_dev) on device tensors: rows < `rows` of `input` and `table`
+    are the theta-compressed columns.  A' is the input sorted ascending by canonical value; S' holds the run's value where a run of A' starts and the table's
+    leftover copies, ascending, from the last other row backwards.  Returns (perm_input, perm_table): new tensors like `input` unless given; rows >= `rows` are
+    not written.  A value missing from the table raises Mi355Error (EBADARG) whose `.row` is the smallest such row of `input`."""
+    import torch
+    for t in (input, table):
+        assert t.numel() * t.element_size() >= 32 * rows, "a column is shorter than rows"
+    if perm_input is None:
+        perm_input = torch.empty_like(input)
+    if perm_table is None:
+        perm_table = torch.empty_like(input)
+    missing = C.c_uint64(0)
+    rc = lib().mi355_fr_lookup_permute_dev(ptr(perm_input), ptr(perm_table), ptr(input), ptr(table), rows, C.byref(missing))
+    if rc != 0:
+        err = Mi355Error(rc, lib().mi355_last_error().decode())
+        err.row = missing.value if rc == 1 and missing.value != (1 << 64) - 1 else None
+        raise err
+    return perm_input, perm_table
+
+
 class PermutationAssembly:
     """the copy-constraint bookkeeping of permutation::keygen::Assembly [EXT-recalled halo2_proofs src/plonk/permutation/keygen.rs]; the twin of
     halo2::PermutationAssembly in include/mi355zk_halo2.hpp.  A cell is the integer column * n + row.  `mapping[cell]` is the cell's image, `aux[cell]` the

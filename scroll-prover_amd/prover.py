@@ -23,7 +23,8 @@ from . import _capi
 from ._capi import check, lib, Mi355Error  # noqa: F401
 from .halo2 import R_MOD, fr, fr_to_int
 
-CIRCUIT_PARTS = ("preprocessed", "advice", "m", "m_counts", "m_blind", "z_blind", "phi_blind", "random_poly", "instances", "copies")
+CIRCUIT_PARTS = ("preprocessed", "advice", "m", "m_counts", "m_blind", "z_blind", "phi_blind", "random_poly", "instances", "copies",
+                 "perm_blind", "lz_blind")   # the last two: protocols with the classic (permuted) lookup argument, which have no m, m_counts, m_blind, phi_blind
 MODE_BATCHED, MODE_ONE_BY_ONE, MODE_AGGREGATE, MODE_FOLD_ONLY = 0, 1, 2, 3
 
 
@@ -78,7 +79,7 @@ class Protocol(_Handle):
     kind = "protocol"
     FIELDS = ("k", "n", "layer", "num_preprocessed", "num_instance", "num_advice", "num_lookups", "num_perm_columns", "num_perm_chunks", "num_gates", "num_witness", "num_commitments",
               "blind", "usable", "quotient_pieces", "extended_k", "num_evaluations", "num_queries", "lookup_bits", "proof_bytes_poseidon", "proof_bytes_evm", "has_initial_state",
-              "has_accumulator")
+              "has_accumulator", "lookup_permuted")
 
     @classmethod
     def from_json(cls, protocol) -> "Protocol":

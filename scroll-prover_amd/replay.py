@@ -32,6 +32,8 @@ def write_protocol(layer: int, directory: str, k: int | None = None, protocol_fi
 
 
 def run(layer: int, k: int | None = None, out_dir: str | None = None, args=(), env=None, timeout: int = 1800, protocol_file: str | None = None, **shape) -> dict:
+    """shape: what protocols.layer_protocol takes besides layer and k; lookup_argument="permuted" proves the layer's circuit under the classic halo2 lookup argument
+    (the protocol file decides what the program proves: it takes no flag for it)"""
     out_dir = out_dir or tempfile.mkdtemp(prefix=f"mi355_replay_l{layer}_")
     os.makedirs(out_dir, exist_ok=True)
     proto = write_protocol(layer, out_dir, k, protocol_file, **shape)
